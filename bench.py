@@ -2,11 +2,21 @@
 """bench.py - individual-timesteps/s of the Geonomics hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the per-generation loop (age, movement, mate search,
 mating with bitmask crossover, density, selection, mortality) over the whole
 resident population.  Metric = sum_t N_t / wall time over K timed steps
 (SURVEY 8d), inputs resident in HBM before the timed region.
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.  `--dump-outputs DIR`
+also writes what the timed path leaves for its caller after its last step (the population's
+fields, per-locus allele counts, a seeded sample of genotypes) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.  `--full` adds everything measured
+beside the headline figure, each in runs of its own after the timed region: the other overlap
+modes of the crossover, per-kernel-family times and the step's roofline, the steady state, a
+measured device copy rate, the tile protocol's phases and RCCL certification (N > 1), the CPU
+baseline, the Model API and the other BASELINE workloads (N = 1).
 
 Workload `c4_metric` (default) is the configuration BASELINE.json's metric is
 quoted on: 2048x2048 two-layer landscape, 10^6 individuals, 10^5-locus genomes,
@@ -327,6 +337,41 @@ def kernel_profile(dev, do_step, n_steps=10):
     return fam
 
 
+def dump_outputs(dev, out_dir, n_inds=1 << 18, n_geno=256, n_loci=4096, seed=12345):
+    """what a caller of the timed path receives after its last step, as out_dir/<name>.npy in
+    float32 / float64 (about 25 MB at the metric workload): the population's fields in id order
+    (ids are unique; a seeded sample of n_inds individuals when there are more), the last step's
+    counts, per-locus allele counts over the whole population, and the genotypes of a seeded
+    n_geno of those individuals at n_loci seeded loci"""
+    from geonomics_amd import _native as nat
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.RandomState(seed)
+    c1, ch = dev.stats_locus_counts()       # (waits for a deferred crossover)
+    ids = dev.download(nat.F_ID)
+    rows = np.argsort(ids, kind='stable')
+    if rows.size > n_inds:
+        rows = rows[np.sort(rng.choice(rows.size, n_inds, replace=False))]
+    out = {'id': ids[rows].astype(np.float64),
+           'counts': np.array(dev.counts(), np.float64),        # N, births, deaths
+           'locus_count_1': c1.astype(np.float64), 'locus_count_het': ch.astype(np.float64)}
+    for name, f in (('x', nat.F_X), ('y', nat.F_Y), ('age', nat.F_AGE), ('sex', nat.F_SEX),
+                    ('fitness', nat.F_FIT)):
+        out[name] = dev.download(f)[rows].astype(np.float32)
+    out['env'] = dev.download(nat.F_E)[:, rows].astype(np.float32)
+    if dev.n_traits:
+        out['z'] = dev.download(nat.F_Z)[:, rows].astype(np.float32)
+    # genotypes [individual, homologue, locus] of a subset of the rows above (id order)
+    pick = np.sort(rng.choice(rows.size, min(n_geno, rows.size), replace=False))
+    loci = np.sort(rng.choice(dev.L, min(n_loci, dev.L), replace=False))
+    g = dev.download_genomes(rows[pick])
+    out['genotype_ids'] = out['id'][pick]
+    out['genotype_loci'] = loci.astype(np.float64)
+    out['genotypes'] = ((g[:, :, loci >> 6] >> (loci & 63).astype(np.uint64))
+                        & np.uint64(1)).astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def measure_other_workload(name, steps=30, warmup=5, steady_warm=1500):
     """a short run of another BASELINE configuration on the same box (N = 1): ms/step,
     individual-timesteps/s, the dominant kernel family and its rate"""
@@ -468,15 +513,22 @@ def main():
     ap.add_argument('--workload', default=None, choices=sorted(WORKLOADS))
     ap.add_argument('--scaling', default='c5', choices=['c5', 'weak2048'],
                     help='N > 1: tiles of BASELINE C5 (default) or 2048x2048 metric tiles')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline figure, after '
+                         'the timed region (the module docstring lists what)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed in its last step as DIR/<name>.npy '
+                         '(rank 0\'s tile when N > 1)')
     ap.add_argument('--steady-warmup', type=int, default=1500,
-                    help='N = 1: steps walked before the second, steady-state measurement '
+                    help='N = 1, --full: steps walked before the second, steady-state measurement '
                          '(c4_metric_steady in the line; 0 = skip)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='--full: skip the CPU baseline (N = 1 only)')
     ap.add_argument('--no-model-api', action='store_true',
-                    help='skip the second measurement through Model.walk (N = 1 only)')
+                    help='--full: skip the second measurement through Model.walk (N = 1 only)')
     ap.add_argument('--no-other-workloads', action='store_true',
-                    help='skip the short runs of BASELINE configs[1], [2] and the dense-mask '
-                         'variant (N = 1, default workload only)')
+                    help='--full: skip the short runs of BASELINE configs[1], [2] and the '
+                         'dense-mask variant (N = 1, default workload only)')
     args = ap.parse_args()
 
     env_world = os.environ.get('WORLD_SIZE')
@@ -626,6 +678,9 @@ def main():
     gc_in_timed = dev.genome_info()['gc_runs'] - gc_before
     kt = dev.kernel_times()
     dev.profiling(False)
+    # (before anything below steps the device further)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(dev, args.dump_outputs)
 
     mx = torch.tensor([elapsed], device='cuda')
     if dist is not None:
@@ -639,7 +694,7 @@ def main():
     # rate), 1 = a narrow crossover beside the WHOLE next step
     alt = None
     alone = None
-    if stepper is None and not os.environ.get('GNX_BENCH_NO_ALT'):
+    if stepper is None and args.full and not os.environ.get('GNX_BENCH_NO_ALT'):
         def other_mode(mode, label):
             dev.set_crossover_overlap(mode)
             for _ in range(5):
@@ -669,7 +724,7 @@ def main():
                              'for it but the next crossover')
     fam = None
     steady = None
-    if stepper is None:
+    if stepper is None and args.full:
         fam = kernel_profile(dev, do_step, 10)
         if args.steady_warmup > 0:
             # the metric workload at ITS steady state: the conductance surface piles the
@@ -692,7 +747,7 @@ def main():
                       'warmup_steps_before': args.steady_warmup,
                       'gc_runs_in_timed_region': dev.genome_info()['gc_runs'] - gc0}
     phases = None
-    if stepper is not None and not os.environ.get('GNX_BENCH_NO_PHASES'):
+    if stepper is not None and args.full and not os.environ.get('GNX_BENCH_NO_PHASES'):
         # per-phase host wall time of the tile protocol, from a few extra steps with a
         # device synchronisation at every phase mark (outside the timed region)
         stepper.profile = True
@@ -708,7 +763,7 @@ def main():
     # tile step): the line certifies the ranks it ran on
     comm_infos = None
     cert_errors = []
-    if stepper is not None and stepper.v3:
+    if stepper is not None and stepper.v3 and args.full:
         mine_info = dev.comm_info()
         mine_info['local_rank'] = local_rank
         mine_info['pid'] = os.getpid()
@@ -753,7 +808,7 @@ def main():
                     break
             except Exception:
                 continue
-        copy_gbps = measured_copy_bandwidth()
+        copy_gbps = measured_copy_bandwidth() if args.full else None
         dense = cfg.get('paths') == 'dense'
         per_gamete = (4.0 if dense else 2.0) * dev.W64 * 8.0
         # the crossover's algorithmic bytes per copied block: the block read and written, plus -
@@ -820,7 +875,7 @@ def main():
                 'work_avoided_factor': (births / args.steps * cfg['L']) /
                                        max(xo['bytes'] / max(xo['launches'], 1), 1.0),
                 # also quote a device-to-device copy measured on this box (the
-                # library's own 16-byte-per-lane copy kernel, two 8-GiB buffers)
+                # library's own 16-byte-per-lane copy kernel, two 8-GiB buffers; --full only)
                 'measured_copy_GBps': copy_gbps,
                 'frac_of_measured_copy': (ach / copy_gbps) if copy_gbps else None,
             },
@@ -902,7 +957,7 @@ def main():
             out['roofline']['kernel_alone'] = alone
         if alt is not None:
             out['whole_step_overlap'] = alt
-        if world == 1 and not args.no_cpu_baseline:     # rank 0 at N = 1 only
+        if world == 1 and args.full and not args.no_cpu_baseline:     # rank 0 at N = 1 only
             out['cpu_baseline'] = cpu_baseline()
             ref = ref_cpu_number()
             if ref is not None:
@@ -913,7 +968,7 @@ def main():
                     'tools/ref_cpu_baseline.py - the reference never reaches the GPU box' % (
                         ref.get('sample'), ref.get('host_cores'), ref.get('cpu')))
         model_api = None
-        if world == 1 and not args.no_model_api:
+        if world == 1 and args.full and not args.no_model_api:
             # the same workload through the drop-in API, at the model's own equilibrium.  Run
             # BEFORE the other workloads: after their allocate / free cycles of 100-GB tables in
             # this process the Model's genome table lands where its crossover runs 10 % slower
@@ -925,8 +980,8 @@ def main():
                 model_api, _ = model_api_measure(cfg, args.workload, min(args.steps, 40))
             except Exception as e:      # the contract line must still be printed
                 model_api = {'error': '%s: %s' % (type(e).__name__, e)}
-        if (world == 1 and args.workload == 'c4_metric' and not args.no_other_workloads
-                and stepper is None):
+        if (world == 1 and args.full and args.workload == 'c4_metric'
+                and not args.no_other_workloads and stepper is None):
             # BASELINE configs[1], [2] and the template's recombination default, short runs
             if dev is not None:
                 dev.close()

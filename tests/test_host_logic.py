@@ -476,26 +476,56 @@ def test_tree_tables_segments_and_genotypes(tmp_path):
     assert len(open(tmp_path / 'ped.edges.txt').read().splitlines()) == 1 + e['left'].size
 
 
-# ---- the reference's own parameter files (read in place; this container only) ------------------
-REF = '/root/reference'
+# ---- the reference's own parameter files ---------------------------------------------------------
+# their settings, stored by tests/golden/make_ref_params_fixture.py (JSON, tagged for dicts with
+# int keys, tuples and arrays), are written back out as a parameters file and read from there
+def _decode_params(o):
+    if isinstance(o, list):
+        return [_decode_params(v) for v in o]
+    if isinstance(o, dict):
+        if '__dict__' in o:
+            return {k: _decode_params(v) for k, v in o['__dict__']}
+        if '__tuple__' in o:
+            return tuple(_decode_params(v) for v in o['__tuple__'])
+        return np.array(o['__ndarray__'], dtype=o['dtype'])
+    return o
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='the reference is mounted in the build container only')
+def _params_source(o, ind=''):
+    if isinstance(o, dict):        # one key per line, as parameters files have them
+        return '{\n%s%s}' % (''.join('%s    %r: %s,\n' % (ind, k, _params_source(v, ind + '    '))
+                                     for k, v in o.items()), ind)
+    if isinstance(o, tuple):
+        return '(%s)' % ''.join(_params_source(v, ind) + ', ' for v in o)
+    if isinstance(o, list):
+        return '[%s]' % ', '.join(_params_source(v, ind) for v in o)
+    if isinstance(o, np.ndarray):
+        return 'np.array(%r, dtype=%r)' % (o.tolist(), str(o.dtype))
+    return repr(o)
+
+
 @pytest.mark.parametrize('rel', ['tests/runtime/runtime_params.py',
                                  'tests/runtime/runtime_params_selection.py',
                                  'tests/validation/bottleneck/bottleneck_params.py',
                                  'tests/validation/wf/wf_params.py'])
-def test_reference_parameter_files_load_unchanged(rel):
-    """drop-in for the parameters-file format: the files the reference's own runtime and
-    validation tests use are read as they are, and the host-side structures they describe
-    (landscape, genomic architecture, change events, data / stats schedules) build"""
+def test_reference_parameter_files_load_unchanged(rel, tmp_path):
+    """drop-in for the parameters-file format: the settings of the files the reference's own
+    runtime and validation tests use, as a parameters file, are read as they are, and the
+    host-side structures they describe (landscape, genomic architecture, change events,
+    data / stats schedules) build"""
+    import json
+    from conftest import GOLDEN
     import geonomics_amd as gnx
     from geonomics_amd.structs.landscape import _make_landscape
     from geonomics_amd.structs import genome as G
     from geonomics_amd.sim.stats import _StatsCollector
     from geonomics_amd.sim.data import _DataCollector
     from geonomics_amd.ops.change import _SpeciesChanger
-    p = gnx.read_parameters_file(os.path.join(REF, rel))
+    with open(os.path.join(GOLDEN, 'ref_param_files.json')) as f:
+        settings = _decode_params(json.load(f)[rel])
+    path = tmp_path / os.path.basename(rel)
+    path.write_text('import numpy as np\n\nparams = %s\n' % _params_source(settings))
+    p = gnx.read_parameters_file(str(path))
     land = _make_landscape(None, p)
     assert tuple(land.dim) == tuple(p.landscape.main.dim) and len(land) == len(p.landscape.layers)
     for name, sp in p.comm.species.items():
