@@ -48,6 +48,7 @@ EXPORTS = [
     'gnx_tile_put_gametes_dev', 'gnx_tile_bins_ptr', 'gnx_set_k_raster', 'gnx_last_births', 'gnx_set_positions', 'gnx_n_slots', 'gnx_stats_ld_counts',
     'gnx_set_defer_crossover', 'gnx_last_crossover_births', 'gnx_set_crossover_overlap', 'gnx_set_crossover_split', 'gnx_debug_halves', 'gnx_spatial_diff_sums', 'gnx_last_crossover_jobs',
     'gnx_genome_info', 'gnx_measure_copy', 'gnx_totals', 'gnx_reset_totals',
+    'gnx_path_counts', 'gnx_reset_path_counts',
     'gnx_step_begin', 'gnx_step_mid', 'gnx_step_end', 'gnx_step_many',
     'gnx_walk', 'gnx_walk_many', 'gnx_walk_history',
     'gnx_comm_unique_id', 'gnx_comm_init_rccl', 'gnx_comm_init_single', 'gnx_comm_local_create',
@@ -449,6 +450,20 @@ class Device:
 
     def reset_totals(self):
         self._chk(self.lib.gnx_reset_totals(self.h))
+
+    PATH_COUNTS = ('lazy_mortalities', 'xo_launch_p2', 'xo_flush', 'jobs_lanes_256',
+                   'jobs_lanes_512', 'sort_hist_gather', 'gc_with_pending_xo', 'make_dense')
+
+    def path_counts(self):
+        """dict of how often the host-driven steps took each path since the handle was made or
+        reset_path_counts() (gnx_path_counts) - host-side bookkeeping, no device access"""
+        out = np.zeros(len(self.PATH_COUNTS), np.int64)
+        n = self.lib.gnx_path_counts(self.h, _ptr(out, C.c_int64), len(out))
+        assert n == len(out), 'gnx_path_counts: the library has %d counters' % n
+        return dict(zip(self.PATH_COUNTS, (int(v) for v in out)))
+
+    def reset_path_counts(self):
+        self._chk(self.lib.gnx_reset_path_counts(self.h))
 
     @property
     def N(self):

@@ -1261,11 +1261,11 @@ extern "C" int gnx_step_mid(gnx_state* h, int32_t burn, int32_t with_selection) 
   // gnx_set_id_order: the pairs' offsets from this device's own counts - gnx_l_mate)
   GNXCHK(gnx_l_mate(h, burn != 0, false, 0, &B));
   h->last_births = B;
-  if (h->xo_launch_policy == 4) GNXCHK(gnx_xo_launch_pending(h));     // (behind the births)
+  if (h->xo_launch_policy == 4) GNXCHK(gnx_xo_launch_pending(h, -1));     // (behind the births)
   // N density of everyone incl. offspring (structs/species.py:845-882); d at each
   // individual's cell, fitness, death probability; mortality
   GNXCHK(gnx_l_density_N(h));
-  if (h->xo_launch_policy == 3) GNXCHK(gnx_xo_launch_pending(h));     // (behind the densities)
+  if (h->xo_launch_policy == 3) GNXCHK(gnx_xo_launch_pending(h, -1));     // (behind the densities)
   GNXCHK(gnx_wait_permute_rest(h));       // (GNX_PERMUTE_REST_AT=2: environment, phenotypes, rows arrive here)
   GNXCHK(gnx_l_death_probs(h, with_selection != 0 && !burn));
   return gnx_l_mortality_enqueue(h, nullptr);
@@ -1324,6 +1324,16 @@ extern "C" int gnx_totals(gnx_state* h, int64_t* out) {
 
 extern "C" int gnx_reset_totals(gnx_state* h) {
   for (int k = 0; k < 6; ++k) h->tot[k] = 0;
+  return 0;
+}
+
+extern "C" int gnx_path_counts(gnx_state* h, int64_t* out, int32_t n) {
+  for (int k = 0; k < n; ++k) out[k] = k < GNX_PC_COUNT ? h->pc[k] : 0;
+  return GNX_PC_COUNT;
+}
+
+extern "C" int gnx_reset_path_counts(gnx_state* h) {
+  for (int k = 0; k < GNX_PC_COUNT; ++k) h->pc[k] = 0;
   return 0;
 }
 

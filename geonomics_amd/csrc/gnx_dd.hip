@@ -16,6 +16,7 @@
 #include <atomic>
 #include <chrono>
 #include <map>
+#include <string>
 #include "gnx_internal.h"
 
 bool gnx_fused_bins(const gnx_state* h);
@@ -580,6 +581,18 @@ extern "C" int gnx_walk_many(gnx_state** hs, int32_t n, int64_t T, int32_t burn,
       const int r2 = gnx_dd_leave(hs[k]);
       if (!rc) rc = r2;
     }
+  // A walk cut short (a handle failed: the others stop with it) leaves every handle whose last
+  // step was not the walk's last with the dead of its lazy mortality still in their slots
+  // (gnx_internal.h: holes).  They are gathered back before anybody reads slots [0, N); the
+  // error that ended the walk is the one reported.
+  {
+    const std::string first_err = rc ? std::string(gnx_last_error()) : std::string();
+    for (int k = 0; k < n; ++k) {
+      const int r3 = gnx_l_make_dense(hs[k]);
+      if (!rc) rc = r3;
+    }
+    if (!first_err.empty()) gnx_set_error("%s", first_err.c_str());
+  }
   if (gnx_host_times()) {
     g_host_step_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     g_host_steps += T * n;

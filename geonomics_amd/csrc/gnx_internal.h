@@ -255,6 +255,19 @@ __device__ __forceinline__ int gnx_route_dest(const RouteGeo& g, int k, int orow
   return -1;
 }
 #endif
+// gnx_path_counts (include/gnx_hip.h): host-side counts of the code paths the steps took
+enum {
+  GNX_PC_LAZY_MORT = 0,      // mortalities that left the dead in place (holes)
+  GNX_PC_XO_P2,              // pending crossovers launched from launch policy 2's site
+  GNX_PC_XO_FLUSH,           // pending crossovers launched by anybody but a launch policy's site
+  GNX_PC_JOBS_256,           // job-builder launches, k_xo_jobs_lanes<256>
+  GNX_PC_JOBS_512,           // ... k_xo_jobs_lanes<512>
+  GNX_PC_SORT_GATHER,        // cell sorts whose first pass gathered through the index (k_move's counts)
+  GNX_PC_GC_PENDING_XO,      // collections while a crossover was built and not yet joined
+  GNX_PC_MAKE_DENSE,         // uncompacted populations gathered back by gnx_l_make_dense
+  GNX_PC_COUNT
+};
+
 struct gnx_state {
   gnx_config cfg{};
   gnx_species_params sp{};
@@ -271,6 +284,7 @@ struct gnx_state {
   int64_t step = 0;            // global step counter (RNG addressing)
   int64_t last_births = 0, last_deaths = 0;
   int64_t tot[6]{};            // gnx_totals: steps, sum of N at step start, births, deaths, crossover births
+  int64_t pc[GNX_PC_COUNT]{};  // gnx_path_counts: which code paths the steps took (GNX_PC_*)
   int64_t n_ghost = 0;         // ghosts currently resident (counted in N)
 
   GnxSoA soa[2]{};
@@ -738,8 +752,10 @@ int gnx_xo_join(gnx_state* h);
 // only the first half: offspring still waiting for their crossover get it now (their slots
 // are about to move); a crossover already in flight on stream2 is left alone
 int gnx_xo_flush_deferred(gnx_state* h);
-// launch the crossover whose jobs are ready (policy 1 / 2 hooks; no-op otherwise)
-int gnx_xo_launch_pending(gnx_state* h);
+// launch the crossover whose jobs are ready (policy 1 / 2 hooks; no-op otherwise).  site
+// (gnx_path_counts): GNX_PC_XO_P2 from launch policy 2's site, -1 from another policy's own
+// site, GNX_PC_XO_FLUSH (the default) from anybody else - a join, a genome access, a wait
+int gnx_xo_launch_pending(gnx_state* h, int site = GNX_PC_XO_FLUSH);
 // `stream` waits for the crossover in flight (not for one that is not launched yet)
 int gnx_xo_wait_inflight(gnx_state* h);
 int gnx_xo_prepare_jobs(gnx_state* h, int32_t** zero);
@@ -877,6 +893,11 @@ int gnx_prim_sort64_bits(void* tmp, size_t bytes, const uint64_t* kin, uint64_t*
 int gnx_prim_scan_bytes(size_t n, size_t* bytes);
 int gnx_prim_scan(void* tmp, size_t bytes, const int32_t* in, int32_t* out, size_t n,
                   hipStream_t s);
+
+// an uncompacted population (holes) gathered back into slots [0, N), in the order of the
+// id-ordered index; no-op otherwise.  Changes no later result: draws are keyed by id and the
+// next cell sort is canonical in (cell, id)
+int gnx_l_make_dense(gnx_state* h);
 
 // the slots in use: the population, or - uncompacted (holes) - the stretch it is spread over
 static inline int64_t gnx_extent(const gnx_state* h) { return h->holes ? h->holes_N : h->N; }

@@ -1830,6 +1830,8 @@ static void launch_jobs_fused(gnx_state* h, int64_t first_slot, const int32_t* d
     if (small) GNX_JL_LAUNCH(256);
     else GNX_JL_LAUNCH(GNX_JF_TPB);
 #undef GNX_JL_LAUNCH
+    // (gnx_path_counts; a device-driven step is launched once into its graph: not counted)
+    if (!ddm && (tpb == 256 || tpb == 512)) ++h->pc[tpb == 256 ? GNX_PC_JOBS_256 : GNX_PC_JOBS_512];
     h->jobs_inline[buf] = true;
     return;
   }
@@ -2452,6 +2454,7 @@ int gnx_l_mortality_enqueue(gnx_state* h, const uint8_t* d_dead_inject) {
     h->holes = true;
     h->holes_N = N;
     h->holes_flagged = N;
+    ++h->pc[GNX_PC_LAZY_MORT];
   } else if (fill) {
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_fill, 0));
     if (ahead) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_move, 0));

@@ -360,10 +360,11 @@ int gnx_l_crossover_pending(gnx_state* h, int64_t first_slot, int64_t B) {
   return 0;
 }
 
-int gnx_xo_launch_pending(gnx_state* h) {
+int gnx_xo_launch_pending(gnx_state* h, int site) {
   const int buf = h->xo_ready_buf;
   if (buf < 0) return 0;
   h->xo_ready_buf = -1;
+  if (site == GNX_PC_XO_P2 || site == GNX_PC_XO_FLUSH) ++h->pc[site];     // (gnx_path_counts)
   // behind everything `stream` has been given so far (the jobs, and with launch policy
   // 1 / 2 the sort that is meant to run alone)
   HIPCHK(hipEventRecord(h->ev_jobs, h->stream));
@@ -438,7 +439,7 @@ int gnx_l_crossover_survivors(gnx_state* h, int64_t first_slot, int64_t B, const
   h->jobs_cur ^= 1;
   // (tiles: the next step's routing reads the migrants' genome rows first thing - gnx_xo_join - so a
   // crossover held back would only be waited for there: at once)
-  if (h->xo_launch_policy == 0 || h->tiled || h->tile2_mode) GNXCHK(gnx_xo_launch_pending(h));
+  if (h->xo_launch_policy == 0 || h->tiled || h->tile2_mode) GNXCHK(gnx_xo_launch_pending(h, -1));
   return 0;
 }
 
@@ -890,6 +891,10 @@ int gnx_gc(gnx_state* h) {
   hipLaunchKernelGGL(k_gc_write, dim3(nb), dim3(256), 0, h->stream, n, per, h->row_spread,
                      h->half_mark, (const int32_t*)h->gc_off, nb, h->half_free, h->half_top);
   h->gc_runs += 1;
+  // (gnx_path_counts: a crossover whose jobs wait for their launch, or which runs on stream2
+  // and nobody has waited for yet)
+  if (!ddm && (h->xo_ready_buf >= 0 || h->xo_inflight[0] || h->xo_inflight[1]))
+    ++h->pc[GNX_PC_GC_PENDING_XO];
   if (ddm) {
     HIPCHK(hipGetLastError());
     return 0;
@@ -943,15 +948,17 @@ extern "C" int gnx_debug_halves(gnx_state* h, int64_t* out) {
     return 1;
   }
   GNXCHK(gnx_xo_join(h));
+  GNXCHK(gnx_l_make_dense(h));       // (the living in [0, N): gnx_internal.h, holes)
   unsigned long long* d = nullptr;
   HIPCHK(hipMalloc((void**)&d, 5 * sizeof(unsigned long long)));
   HIPCHK(hipMemsetAsync(d, 0, 5 * sizeof(unsigned long long), h->stream));
   const int64_t n_halves = (int64_t)h->cfg.cap_rows * h->row_spread * 2 * h->NB;
+  const int64_t n_slots = gnx_extent(h);
   // marks as the collector would set them (its sweep clears them again)
-  if (h->N > 0)
-    hipLaunchKernelGGL(k_gc_mark, dim3(2048), dim3(256), 0, h->stream, h->N, h->soa[h->cur].grow,
+  if (n_slots > 0)
+    hipLaunchKernelGGL(k_gc_mark, dim3(2048), dim3(256), 0, h->stream, n_slots, h->soa[h->cur].grow,
                        gnx_halves(h), h->half_mark, (const GnxDD*)nullptr);
-  hipLaunchKernelGGL(k_half_check, dim3(1024), dim3(256), 0, h->stream, h->N, h->soa[h->cur].grow,
+  hipLaunchKernelGGL(k_half_check, dim3(1024), dim3(256), 0, h->stream, n_slots, h->soa[h->cur].grow,
                      gnx_halves(h), n_halves, (const uint8_t*)h->half_mark, d);
   unsigned long long host[5];
   int rc = gnx_d2h(h, host, d, sizeof(host));

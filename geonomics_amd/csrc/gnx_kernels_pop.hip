@@ -835,6 +835,59 @@ int gnx_wait_permute_rest(gnx_state* h, bool late_ok) {
   return 0;
 }
 
+// the living of an uncompacted population (gnx_internal.h: holes) in the order of the id-ordered
+// index: entry k is slot ord[k] (the lazy mortality's index holds the living only, ord_n = N)
+__global__ void k_gather_ord(int64_t N, int64_t cap, const int32_t* __restrict__ ord, GnxSoA a,
+                             GnxSoA b, int n_layers, int n_traits, int tbw,
+                             int32_t* __restrict__ ord_new) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int64_t j = ord[i];
+  const GnxRec r = gnx_rec_load(a, j, cap, n_layers, n_traits, tbw);
+  gnx_rec_store(b, i, cap, n_layers, n_traits, tbw, r);
+  gnx_rec_rest(a, j, b, i, cap, n_layers, n_traits, tbw);
+  ord_new[i] = (int32_t)i;
+}
+
+// A walk that ends between two of its steps (gnx_walk_many: another handle failed) leaves the
+// dead of the last lazy mortality in their slots; whoever reads or writes slots [0, N) needs the
+// living there.  The cell sort cannot do it here (the movement's keys are not fresh), so the
+// living are gathered through the index instead - in id order, the index becomes the identity.
+// The dead's genome rows are back on the free stack already (k_dead_rows).
+int gnx_l_make_dense(gnx_state* h) {
+  if (!h->holes) return 0;
+  if (h->tile2_mode || h->mort_wait || h->pairs_wait || !h->ord_valid || h->ord_n != h->N) {
+    gnx_set_error("internal: an uncompacted population that cannot be gathered (tile %d, step "
+                  "open %d, index %d with %lld of %lld)", (int)h->tile2_mode,
+                  (int)(h->mort_wait || h->pairs_wait), (int)h->ord_valid, (long long)h->ord_n,
+                  (long long)h->N);
+    return 1;
+  }
+  const int64_t N = h->N;
+  gnx_bins_adults_drop(h);
+  GNXCHK(gnx_wait_permute_rest(h));
+  GNXCHK(gnx_xo_flush_deferred(h));
+  GNXCHK(gnx_os_hist_discard(h));
+  h->keys_fresh = false;
+  if (h->ord_inflight) {        // the index's own compaction (stream3) has finished
+    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_ord, 0));
+    h->ord_inflight = false;
+  }
+  const gnx_config& c = h->cfg;
+  GnxSoA a = h->soa[h->cur], b = h->soa[h->cur ^ 1];
+  hipLaunchKernelGGL(k_gather_ord, dim3(gnx_grid(N, 256)), dim3(256), 0, h->stream, N, c.cap_inds,
+                     (const int32_t*)h->ord[h->ord_cur], a, b, c.n_layers, c.n_traits,
+                     a.tb ? 2 * h->TW : 0, h->ord[h->ord_cur ^ 1]);
+  HIPCHK(hipGetLastError());
+  h->cur ^= 1;
+  h->ord_cur ^= 1;
+  h->holes = false;
+  h->holes_N = 0;
+  h->holes_flagged = 0;
+  ++h->pc[GNX_PC_MAKE_DENSE];
+  return 0;
+}
+
 // Sort of the whole SoA by (hash cell, id); cell size >= mating radius.
 int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
   int64_t N = h->N;
@@ -890,6 +943,7 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
       // k_move wrote the cells AND counted their digits: the passes alone, the first one
       // gathering its keys through the id-ordered index
       h->hist_fresh = false;
+      ++h->pc[GNX_PC_SORT_GATHER];
       GNXCHK(gnx_os_sort32_gather(h->os_scratch, h->os_ktmp, h->os_vtmp, h->keyk[1], h->valk[1],
                                   (size_t)N, h->key_bits, h->ord[h->ord_cur], h->ord_n, h->cell32,
                                   h->stream));
@@ -1032,7 +1086,7 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
     h->ord_valid = false;
     h->fb_adults = false;
   }
-  if (h->xo_launch_policy == 1) GNXCHK(gnx_xo_launch_pending(h));
+  if (h->xo_launch_policy == 1) GNXCHK(gnx_xo_launch_pending(h, -1));
   return 0;
 }
 
@@ -2129,7 +2183,7 @@ int gnx_l_find_pairs_finish(gnx_state* h, int64_t* n_pairs_out) {
   *n_pairs_out = h->n_pairs;
   if (!h->pairs_with_density) h->spl_P.valid = false;
   else if (h->n_pairs == 0) h->spl_P.valid = false;
-  if (h->xo_launch_policy == 2) GNXCHK(gnx_xo_launch_pending(h));
+  if (h->xo_launch_policy == 2) GNXCHK(gnx_xo_launch_pending(h, GNX_PC_XO_P2));
   return 0;
 }
 

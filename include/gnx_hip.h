@@ -229,6 +229,20 @@ int gnx_counts(gnx_state* h, int64_t* N, int64_t* births, int64_t* deaths);
  * bookkeeping only: no device access.                                                       */
 int gnx_totals(gnx_state* h, int64_t* out);
 int gnx_reset_totals(gnx_state* h);
+/* Which code paths the host-driven steps took since the handle was created or since the last
+ * gnx_reset_path_counts - so that a test can prove it reached the path it means to check.
+ * out[0 .. n) of: mortalities that left the dead in their slots (gnx_walk: every step but the
+ * last); pending crossovers launched from launch policy 2's site (behind the next step's pair
+ * list: capacities above 600 000 slots); pending crossovers launched by anybody else (a join,
+ * a genome access); job-builder launches of the 256-thread and of the 512-thread
+ * instantiation; cell sorts whose first pass gathered through the id-ordered index with the
+ * digit counts of the movement; block collections that ran while a crossover was built but
+ * not yet joined; uncompacted populations gathered back after a walk that was cut short.
+ * Returns how many counters there are.  Host-side integers only: no device access, no
+ * effect on any result (gnx_totals is separate).  Steps of the device-driven walk are
+ * captured once into a graph and replayed: they are not counted.                         */
+int gnx_path_counts(gnx_state* h, int64_t* out, int32_t n);
+int gnx_reset_path_counts(gnx_state* h);
 /* Where the new offspring's genomes are cut (ops/mating.py:130-214, the crossover).
  * on (default, one GPU): after the step's death draws, for the offspring that survive
  * them only, on a second HIP stream under the next step's kernels - offspring that die at

@@ -372,6 +372,16 @@ def test_small_path_equals_default_path(variant, monkeypatch):
     b.close()
 
 
+def _growing(cap):
+    """a small founder population that grows several-fold (K_factor 2), no genomes"""
+    W = H = 40
+    rasts = np.stack([np.ones((H, W)), np.tile(np.linspace(0, 1, W), (H, 1))]).astype(np.float32)
+    dev = make_dev(W, H, rasts=rasts, L=0, n_traits=0, cap=cap, seed=4, mating_radius=3.0,
+                   K_factor=2.0)
+    dev.init_population(400)
+    return dev
+
+
 @pytest.mark.parametrize('variant', ['device_driven', 'host_driven'])
 def test_walk_that_outgrows_the_capacity_fails_loudly(variant, monkeypatch):
     """a gnx_walk whose births do not fit the preallocated slots returns
@@ -382,15 +392,7 @@ def test_walk_that_outgrows_the_capacity_fails_loudly(variant, monkeypatch):
     if variant == 'host_driven':
         monkeypatch.setenv('GNX_DD', '0')
     nat = native()
-    W = H = 40
-    rasts = np.stack([np.ones((H, W)), np.tile(np.linspace(0, 1, W), (H, 1))]).astype(np.float32)
-
-    def mk(cap):
-        dev = make_dev(W, H, rasts=rasts, L=0, n_traits=0, cap=cap, seed=4, mating_radius=3.0,
-                       K_factor=2.0)
-        dev.init_population(400)
-        return dev
-
+    mk = _growing
     a, b = mk(16384), mk(1024)
     seq = []
     for _ in range(40):
@@ -407,6 +409,51 @@ def test_walk_that_outgrows_the_capacity_fails_loudly(variant, monkeypatch):
     assert got == seq[:len(got)]
     a.close()
     b.close()
+
+
+@pytest.mark.parametrize('variant', ['host_driven', 'device_driven'])
+def test_walk_many_failure_leaves_other_handles_dense(variant, monkeypatch):
+    """gnx_walk_many stops every handle when one fails.  Host-driven, every step of a walk but
+    its last leaves the dead in their slots (lazy mortality) - a handle cut short there must
+    still present its population in slots [0, N): the error exit gathers the living back.  The
+    handle that kept going equals a twin walked alone for as many steps, and walks on like it."""
+    if variant == 'host_driven':
+        monkeypatch.setenv('GNX_DD', '0')
+    nat = native()
+    a, b, c = _growing(16384), _growing(1024), _growing(16384)
+    with pytest.raises(nat.GnxError, match='capacity exceeded'):
+        nat.walk_many([a, b], 40, True, False)
+    k = len(a.walk_history()[0])
+    # (device-driven, a handle takes several steps per call: a may have finished its 40)
+    assert 0 < k < 40 if variant == 'host_driven' else 0 < k <= 40
+    c.walk(k, True, False)
+    assert a.N == c.N
+
+    def state(dev):
+        ids = dev.download(nat.F_ID)
+        o = np.argsort(ids)
+        return dict(ids=ids[o], x=dev.download(nat.F_X)[o], y=dev.download(nat.F_Y)[o],
+                    age=dev.download(nat.F_AGE)[o], sex=dev.download(nat.F_SEX)[o])
+
+    sa, sc = state(a), state(c)
+    assert np.unique(sa['ids']).size == a.N
+    for f in sa:
+        np.testing.assert_array_equal(sa[f], sc[f], err_msg=f)
+    pa = a.path_counts()
+    if variant == 'host_driven':
+        # every step of a's walk was lazy (none was its last): the bug's precondition was there,
+        # and the error exit gathered the population back once
+        assert pa['lazy_mortalities'] == k and pa['make_dense'] == 1, pa
+    else:
+        assert pa['lazy_mortalities'] == 0 and pa['make_dense'] == 0, pa
+    a.walk(5, True, False)
+    c.walk(5, True, False)
+    assert a.counts() == c.counts()
+    sa, sc = state(a), state(c)
+    for f in sa:
+        np.testing.assert_array_equal(sa[f], sc[f], err_msg=f)
+    for dev in (a, b, c):
+        dev.close()
 
 
 def test_small_path_burn_in_and_growth():

@@ -126,6 +126,75 @@ def test_step_invariants_at_baseline_sizes(workload):
     assert sig == run('walk')
 
 
+def test_metric_walk_equals_steps():
+    """The benchmark's own sequence at the metric workload (10^6 individuals in 2 x 10^6 slots,
+    10^5 loci): walk(4), walk(20), a host-side mutation, walk(7) - gnx_step per step with the
+    dead left in place between the steps of a walk, the crossover launched behind the next
+    step's pair list and the 512-thread job builder - against the same 31 steps as single
+    gnx_step calls (every mortality compacts).  Counts per step, every column in id order, the
+    per-locus allele counts of all 10^5 loci and 256 genomes bit for bit must be the same."""
+    MUT_AFTER = 24
+
+    def run(via):
+        bench, nat, cfg, dev = _build('c4_metric')
+        for _ in range(3):
+            dev.step(True, False)
+        bench.setup_genomes(dev, cfg, 42)
+        dev.reset_path_counts()
+        hist = []
+
+        def mutate():
+            rng = np.random.RandomState(17)
+            ids = np.sort(dev.download(nat.F_ID))
+            pick = rng.choice(ids, 16, replace=False)
+            loci = rng.randint(0, cfg['L'], 16).astype(np.int32)
+            homs = rng.randint(0, 2, 16).astype(np.uint8)
+            have = dev.download(nat.F_ID)
+            o = np.argsort(have)
+            dev.mutate(o[np.searchsorted(have[o], pick)].astype(np.int64), loci, homs)
+
+        if via == 'walk':
+            for T in (4, 20, 7):
+                dev.walk(T, False, True)
+                hist += [tuple(int(v) for v in r) for r in zip(*dev.walk_history())]
+                if T == 20:
+                    mutate()
+        else:
+            for t in range(31):
+                n0 = dev.N
+                dev.step(False, True)
+                hist.append((n0,) + dev.counts()[1:])
+                if t == MUT_AFTER - 1:
+                    mutate()
+        ids = dev.download(nat.F_ID)
+        o = np.argsort(ids)
+        out = dict(hist=hist, ids=ids[o])
+        for k, f in (('x', nat.F_X), ('y', nat.F_Y), ('age', nat.F_AGE), ('fit', nat.F_FIT)):
+            out[k] = dev.download(f)[o]
+        out['z'] = dev.download(nat.F_Z)[:, o]
+        out['c1'], out['ch'] = dev.stats_locus_counts()
+        pick = np.sort(np.random.RandomState(5).choice(ids.size, 256, replace=False))
+        out['g'] = dev.download_genomes(o[pick].astype(np.int64))
+        assert dev.debug_halves()[1] == 0            # no broken block references
+        out['paths'] = dev.path_counts()
+        dev.close()
+        return out
+
+    a = run('walk')
+    pa = a.pop('paths')
+    # the path the benchmark times: 3 + 19 + 6 lazy mortalities, the 512-thread job builder
+    # only, the crossover launched from launch policy 2's site
+    assert pa['lazy_mortalities'] >= 28, pa
+    assert pa['jobs_lanes_512'] > 0 and pa['jobs_lanes_256'] == 0, pa
+    assert pa['xo_launch_p2'] > 0, pa
+    b = run('step')
+    assert b.pop('paths')['lazy_mortalities'] == 0
+    assert len(a['hist']) == 31 and a['hist'] == b['hist']
+    assert a['ids'].size > 900_000
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
 def _tiles_equal_one_device(cfg, grid, n_paths, n_burn, n_main, nbits, library=False):
     """A landscape of grid[0] x grid[1] tiles of `cfg`, once on one device and once as
     tiles (threads of this process, tests/_local_comm.py in place of RCCL, device-resident

@@ -237,6 +237,96 @@ def test_fused_step_path_matches_oracle_crossover(dense, overlap):
     b.close()
 
 
+def _id_order(dev, nat):
+    """ids and the per-individual columns, in id order"""
+    ids = dev.download(nat.F_ID)
+    o = np.argsort(ids)
+    return dict(ids=ids[o], x=dev.download(nat.F_X)[o], y=dev.download(nat.F_Y)[o],
+                age=dev.download(nat.F_AGE)[o], fit=dev.download(nat.F_FIT)[o],
+                z=dev.download(nat.F_Z)[:, o])
+
+
+def _slots_of(dev, nat, ids):
+    have = dev.download(nat.F_ID)
+    o = np.argsort(have)
+    k = np.searchsorted(have[o], ids)
+    assert (have[o][k] == ids).all()
+    return o[k].astype(np.int64)
+
+
+# the walk in pieces: walk(1) takes no lazy step, walk(2) exactly one, the long pieces cross the
+# collector's own runs
+WALK_CHUNKS = [1, 2, 3, 7, 13, 26, 1, 40, 37]
+
+
+@pytest.mark.parametrize('dense', [False, True, 'clustered'])
+def test_large_capacity_walk_matches_oracle_crossover(dense):
+    """gnx_walk above 600 000 slots - what bench.py times: gnx_step per step with the dead left in
+    their slots between steps (lazy mortality), the deferred crossover launched behind the NEXT
+    step's pair list (launch policy 2: collections and reservations run while it is pending) and
+    the 512-thread job builder.  A handle with 2^20 slots and a population of ~1500 is walked in
+    pieces; a twin at 4096 slots (policy 0, 256 threads, no lazy step) driven through the split
+    step supplies the births the oracle replays.  Draws are keyed by id and step: the capacity
+    changes nothing - counts per step, every column in id order, and the genomes of both equal
+    the oracle's.  The path counters prove each handle took the path it stands for."""
+    nat = native()
+    paths = _paths(dense)
+    a, g = _make(paths, cap_inds=1 << 20)
+    b, _ = _make(paths)
+    assert sum(WALK_CHUNKS) == STEPS
+    host = HostGenomes(np.arange(N0), g, paths)
+    rng = np.random.RandomState(23)
+    t = 0
+    for c, T in enumerate(WALK_CHUNKS):
+        a.walk(T, False, True)
+        hist = []
+        for _ in range(T):
+            n0 = b.N
+            B, _ = _split_step(b, host, t)
+            hist.append((n0, B, b.counts()[2]))
+            t += 1
+        got = [tuple(int(v) for v in r) for r in zip(*a.walk_history())]
+        assert got == hist, 'piece %d (walk(%d))' % (c, T)
+        assert a.counts() == b.counts(), c
+        sa, sb = _id_order(a, nat), _id_order(b, nat)
+        for k in sa:
+            np.testing.assert_array_equal(sa[k], sb[k], err_msg='piece %d: %s' % (c, k))
+        host.check(a, nat, 'walk, piece %d' % c)
+        host.check(b, nat, 'split step, step %d' % (t - 1))
+        if c % 2 == 1:
+            # a host-side mutation of a few living individuals, the same on both devices
+            ids = rng.choice(sa['ids'], 6, replace=False)
+            loci = rng.randint(1, L, ids.size).astype(np.int32)
+            homs = rng.randint(0, 2, ids.size).astype(np.uint8)
+            for dev in (a, b):
+                dev.mutate(_slots_of(dev, nat, ids), loci, homs)
+            host.mutate(ids, loci, homs)
+        if c == 4:
+            for dev in (a, b):          # a collection forced between two walks
+                rows, broken, _, used, free, total = (int(v) for v in dev.debug_halves())
+                assert broken == 0 and used + free == total
+    for dev in (a, b):
+        gc = dev.genome_info()['gc_runs']       # (one of them forced)
+        assert gc >= 2, 'the collector never ran on its own (gc_runs = %d)' % gc
+    assert host.born > 25000
+    pa, pb = a.path_counts(), b.path_counts()
+    # a: every step of a walk but its last left its dead in place, and the next cell sort
+    # gathered the living with the movement's digit counts
+    assert pa['lazy_mortalities'] == sum(T - 1 for T in WALK_CHUNKS), pa
+    assert pa['jobs_lanes_512'] > 0 and pa['jobs_lanes_256'] == 0, pa
+    assert pa['xo_launch_p2'] > 0, pa
+    assert pa['sort_hist_gather'] >= pa['lazy_mortalities'], pa
+    # the reservation in the mortality runs while the previous step's crossover, launched
+    # behind this step's pair list, is still in flight: the collections it triggers see it
+    # (a forced collection or a mutation joins the crossover first: these are natural ones)
+    assert pa['gc_with_pending_xo'] >= 1, pa
+    assert pa['make_dense'] == 0, pa       # (no walk was cut short)
+    assert pb['lazy_mortalities'] == pb['jobs_lanes_512'] == pb['xo_launch_p2'] == 0, pb
+    assert pb['jobs_lanes_256'] > 0, pb
+    a.close()
+    b.close()
+
+
 @pytest.mark.parametrize('overlap,library', [(0, False), (1, False), (0, True), (1, True)])
 def test_two_tiles_match_oracle_crossover(overlap, library):
     """two tiles (threads of this process, device-resident transport) through gnx_tile_*:
