@@ -62,6 +62,7 @@ EXPORTS = [
     'gnx_tile_step_begin', 'gnx_tile_step_births', 'gnx_tile_step_end', 'gnx_comm_probe',
     'gnx_tile2_pairs_mode', 'gnx_tile2_pairs_settle', 'gnx_tile2_settle_births',
     'gnx_tile2_vt_counts', 'gnx_tile2_vt_bases', 'gnx_tile_step_abort', 'gnx_comm_info', 'gnx_tile_walk',
+    'gnx_geno_gram', 'gnx_geno_matmul', 'gnx_geno_rmatmul',
 ]
 
 
@@ -960,6 +961,69 @@ class Device:
         self._chk(self.lib.gnx_stats_ld_counts(self.h, int(loci.size), _ptr(loci, C.c_int32),
                                                _ptr(c, C.c_int64), _ptr(cc, C.c_int64)))
         return c, cc
+
+    # -- genetic PCA and distances (csrc/gnx_geno.hip) ---------------------------------
+    def _geno_slots(self, slots):
+        if slots is None:
+            return None, int(self.N)
+        s = _arr(slots, np.int64)
+        return s, int(s.size)
+
+    def geno_gram(self, slots=None, locus_mask=None):
+        """G = D D^T of the dosages of `slots` (all living slots by default), exact int64
+        [n][n]; locus_mask: uint64 [W64] bit mask of the loci to use (None: all)"""
+        s, n = self._geno_slots(slots)
+        m = None
+        if locus_mask is not None:
+            m = _arr(locus_mask, np.uint64)
+            if m.size != self.W64:
+                raise ValueError('locus_mask: %d words, not %d' % (m.size, self.W64))
+        # (the library refuses n outside 1..8192 before it writes: no n x n buffer for that)
+        out = np.zeros((n, n) if 1 <= n <= 8192 else (0, 0), np.int64)
+        self._chk(self.lib.gnx_geno_gram(self.h, C.c_int64(n), _ptr(s, C.c_int64),
+                                         _ptr(m, C.c_uint64), _ptr(out, C.c_int64)))
+        return out
+
+    @staticmethod
+    def _f32_dev(t, name):
+        import torch
+        if not torch.cuda.is_available():
+            raise GnxError('torch sees no HIP device: initialise it (torch.cuda.init()) before '
+                           'the first Device is created, as bench.py does')
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != 2:
+            raise ValueError('%s: a 2-d torch tensor on the device' % name)
+        return t.to(torch.float32).contiguous()
+
+    def geno_matmul(self, M, slots=None):
+        """Y = D M: M torch fp32 [L][k] on the handle's device -> Y torch fp32 [n][k] (rows in
+        the order of `slots`, all living slots by default).  The call waits for the current
+        torch stream before it reads M and returns with Y complete."""
+        import torch
+        M = self._f32_dev(M, 'M')
+        if M.shape[0] != self.L:
+            raise ValueError('M: %d rows, not L = %d' % (M.shape[0], self.L))
+        s, n = self._geno_slots(slots)
+        Y = torch.empty((n, M.shape[1]), dtype=torch.float32, device=M.device)
+        torch.cuda.current_stream(M.device).synchronize()
+        self._chk(self.lib.gnx_geno_matmul(self.h, int(M.shape[1]), C.c_void_p(M.data_ptr()),
+                                           C.c_void_p(Y.data_ptr() or None), C.c_int64(n),
+                                           _ptr(s, C.c_int64)))
+        return Y
+
+    def geno_rmatmul(self, Y, slots=None):
+        """Z = D^T Y: Y torch fp32 [n][k] on the handle's device -> Z torch fp32 [L][k]"""
+        import torch
+        Y = self._f32_dev(Y, 'Y')
+        s, n = self._geno_slots(slots)
+        if Y.shape[0] != n:
+            raise ValueError('Y: %d rows, not n = %d' % (Y.shape[0], n))
+        Z = torch.empty((self.L, Y.shape[1]), dtype=torch.float32, device=Y.device)
+        torch.cuda.current_stream(Y.device).synchronize()
+        self._chk(self.lib.gnx_geno_rmatmul(self.h, int(Y.shape[1]),
+                                            C.c_void_p(Y.data_ptr() or None),
+                                            C.c_void_p(Z.data_ptr() or None), C.c_int64(n),
+                                            _ptr(s, C.c_int64)))
+        return Z
 
     # -- measurement ---------------------------------------------------------
     def profiling(self, on):

@@ -768,3 +768,20 @@ class Model:
     def get_genotypes(self, spp=0, loci=None, individs=None, biallelic=False):
         spp = self.comm[self._get_spp_num(spp)]
         return spp._get_genotypes(loci=loci, individs=individs, biallelic=biallelic)
+
+    def calc_genetic_PCA(self, n_pcs=3, spp=0, individs=None, loci=None, method='auto',
+                         n_iter=8, oversample=10, seed=0):
+        """genetic PCA of the mean genotypes (reference Model.plot_genetic_PCA,
+        sim/model.py:2031-2041, without the plot) computed on the device:
+        -> (ids ascending, scores [n][n_pcs], explained_variance_ratio [n_pcs]).
+        The products run on torch buffers: initialise torch's device (torch.cuda.init())
+        before the model is made, or torch may not see the GPU the library holds."""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_genetic_PCA(n_pcs=n_pcs, individs=individs, loci=loci, method=method,
+                                     n_iter=n_iter, oversample=oversample, seed=seed)
+
+    def get_genetic_distances(self, spp=0, individs=None, loci=None):
+        """Euclidean distances between mean genotypes (reference demos/_IBD_IBE.py calc_dists,
+        dist_type='gen', biallelic=False) computed on the device: -> (ids, dist [n][n])"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_genetic_distances(individs=individs, loci=loci)

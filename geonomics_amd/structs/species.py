@@ -724,6 +724,95 @@ class Species:
             return {int(i): g for i, g in zip(out_ids, gts)}
         return gts
 
+    # -- genetic PCA and distances (sim/pca.py; csrc/gnx_geno.hip) -----------------------
+    def _geno_sample(self, individs):
+        """(ids ascending, their slots) of the listed living individuals (all by default)"""
+        all_ids = self._field(nat.F_ID)
+        order = np.argsort(all_ids, kind='stable')
+        srt = all_ids[order]
+        if individs is None:
+            return srt, order.astype(np.int64)
+        ids = np.sort(np.asarray(individs, dtype=np.int64).ravel())
+        if (np.diff(ids) == 0).any():
+            raise ValueError('individs lists an individual more than once')
+        pos = np.searchsorted(srt, ids)
+        alive = pos < srt.size
+        alive[alive] = srt[pos[alive]] == ids[alive]
+        if not alive.all():
+            raise ValueError('individuals not alive: %s' % ids[~alive][:10].tolist())
+        return ids, order[pos].astype(np.int64)
+
+    def _geno_loci(self, loci):
+        """(ascending loci, uint64 [W64] bit mask of them), or (None, None) for all loci"""
+        if loci is None:
+            return None, None
+        L = self._dev.L
+        loci = np.unique(np.asarray(loci, dtype=np.int64).ravel())
+        if loci.size == 0 or loci[0] < 0 or loci[-1] >= L:
+            raise ValueError('loci: a non-empty list of loci in 0..%d' % (L - 1))
+        mask = np.zeros(self._dev.W64, np.uint64)
+        np.bitwise_or.at(mask, loci >> 6, np.uint64(1) << (loci & 63).astype(np.uint64))
+        return loci, mask
+
+    def _calc_genetic_PCA(self, n_pcs=3, individs=None, loci=None, method='auto', n_iter=8,
+                          oversample=10, seed=0):
+        """PCA of the mean genotypes of the living individuals asked for (reference
+        Model.plot_genetic_PCA, sim/model.py:2031-2041: sklearn PCA of the speciome, ids
+        ascending), on the device.  method 'exact': the Gram matrix (gnx_geno_gram, up to
+        8192 individuals) and eigh in fp64; 'randomized': subspace iteration over
+        gnx_geno_matmul / gnx_geno_rmatmul (the whole population); 'auto': exact for
+        n <= 8192.  -> (ids, scores [n][n_pcs], explained_variance_ratio [n_pcs])"""
+        from ..sim import pca as _pca
+        if method not in ('auto', 'exact', 'randomized'):
+            raise ValueError("method: 'auto', 'exact' or 'randomized', not %r" % (method,))
+        ids, slots = self._geno_sample(individs)
+        if self._dev.L == 0:
+            self._dev.geno_gram(slots[:1])            # the library's error: no genomes
+        loci, mask = self._geno_loci(loci)
+        n = ids.size
+        n_pcs = _pca.check_n_pcs(n_pcs, n, self._dev.L if loci is None else loci.size,
+                                 oversample)
+        if method == 'auto':
+            method = 'exact' if n <= 8192 else 'randomized'
+        if method == 'randomized':
+            if n != len(self):
+                raise NotImplementedError(
+                    'randomized genetic PCA of a subset of the individuals (its total variance '
+                    'needs per-sample locus counts); use the exact method (up to 8192)')
+            scores, ratio = _pca.device_randomized_pca(self._dev, n_pcs, loci=loci,
+                                                       oversample=oversample, n_iter=n_iter,
+                                                       seed=seed)
+            return ids, scores[slots], ratio
+        if n > 8192:
+            raise ValueError('the exact genetic PCA takes at most 8192 individuals (got %d)' % n)
+        import torch
+        G = self._dev.geno_gram(slots, mask)
+        tdev = torch.device('cuda', int(self._dev.cfg.device))
+
+        def rmatmul(U):
+            Z = self._dev.geno_rmatmul(torch.as_tensor(U, dtype=torch.float32, device=tdev),
+                                       slots)
+            return Z if loci is None else Z[torch.as_tensor(loci, device=tdev)]
+
+        scores, ratio = _pca.pca_from_gram(G, n_pcs, rmatmul=rmatmul)
+        return ids, scores, ratio
+
+    def _calc_genetic_distances(self, individs=None, loci=None):
+        """Euclidean distances between the mean genotypes of the living individuals asked for
+        (reference demos/_IBD_IBE.py calc_dists, dist_type='gen', biallelic=False,
+        return_flat=False): 0.5 sqrt(G_ii + G_jj - 2 G_ij) from the exact Gram matrix (up to
+        8192 individuals).  -> (ids ascending, dist [n][n])"""
+        ids, slots = self._geno_sample(individs)
+        if ids.size > 8192:
+            raise ValueError('genetic distances of at most 8192 individuals per call (got %d)'
+                             % ids.size)
+        if self._dev.L == 0:
+            self._dev.geno_gram(slots[:1])            # the library's error: no genomes
+        loci, mask = self._geno_loci(loci)
+        G = self._dev.geno_gram(slots, mask)
+        g = np.diag(G)
+        return ids, 0.5 * np.sqrt((g[:, None] + g[None, :] - 2 * G).astype(np.float64))
+
     def _calc_fitness(self, trait_num=None, set_fit=True):
         """reference ops/selection.py:51-112.  Overall fitness (trait_num None) is what
         the death-probability kernel of the last _do_pop_dynamics stored; the fitness of

@@ -39,6 +39,17 @@ class TiledSpecies(Species):
         self._stepper = None
         self._glob_N = 0
 
+    # -- genetic PCA and distances: not over tiles --------------------------------------
+    # (each tile's products are row-local, but they would need an all-reduce of L x k and
+    # k x k, and the Gram matrix a gather of the sample)
+    def _calc_genetic_PCA(self, *args, **kw):
+        raise NotImplementedError('genetic PCA of a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
+    def _calc_genetic_distances(self, *args, **kw):
+        raise NotImplementedError('genetic distances of a Species tiled over several GPUs are '
+                                  'not implemented; run the model on one GPU')
+
     # -- construction -----------------------------------------------------------------
     def _capacities(self, cap, N0):
         """Every rank draws the whole initial population before keeping its tile, so the

@@ -616,6 +616,25 @@ int gnx_stats_ld(gnx_state* h, int32_t n_loci, const int32_t* loci, double* r2);
 int gnx_stats_ld_counts(gnx_state* h, int32_t n_loci, const int32_t* loci, int64_t* c /*[n]*/,
                         int64_t* cc /*[n][n]*/);
 
+/* ---- genetic PCA and distances (reference sim/model.py:2031-2041 plot_genetic_PCA,
+ *      demos/_IBD_IBE.py:38-192 calc_dists) ---------------------------------------
+ * D = dosages d = a + b in {0, 1, 2} of the individuals in `slots` (rows in that order;
+ * slots == NULL: all living slots [0, N), and n must equal N).  Every call refuses a handle
+ * without genomes or with ghost records (tiles), cuts a pending crossover first and gathers
+ * an uncompacted population before it reads.  The padding bits past L never count.       */
+/* G = D D^T, exact, int64 [n][n] on the HOST, n <= 8192; locus_mask: u64 [W64] bit mask of
+ * the loci to use (NULL: all L)                                                         */
+int gnx_geno_gram(gnx_state* h, int64_t n, const int64_t* slots, const uint64_t* locus_mask,
+                  int64_t* G);
+/* Y = D M: M fp32 [L][k] and Y fp32 [n][k] are DEVICE pointers (e.g. torch tensors on the
+ * handle's device), 1 <= k <= 64.  The caller's writes of M must be complete (synchronise its
+ * stream); the call returns when Y is complete, and any stream may read it.               */
+int gnx_geno_matmul(gnx_state* h, int32_t k, const float* M, float* Y, int64_t n,
+                    const int64_t* slots);
+/* Z = D^T Y: Y fp32 [n][k] and Z fp32 [L][k] DEVICE pointers, as gnx_geno_matmul         */
+int gnx_geno_rmatmul(gnx_state* h, int32_t k, const float* Y, float* Z, int64_t n,
+                     const int64_t* slots);
+
 /* ---- measurement ------------------------------------------------------------ */
 int gnx_profiling(gnx_state* h, int32_t on);
 /* accumulated HIP-event time (ms) and launch count of one kernel family,
