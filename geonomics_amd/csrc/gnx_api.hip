@@ -40,10 +40,8 @@ static hipEvent_t timer_event(gnx_state* h) {
   }
   hipEvent_t e = nullptr;
   // (timing only: no system-scope fence when it is recorded - the header's own advice, and
-  // 2 us less per record on the stream that is being timed; GNX_EVENT_FLAGS=0: the default)
-  static const bool nofence = !(getenv("GNX_EVENT_FLAGS") && atoi(getenv("GNX_EVENT_FLAGS")) == 0);
-  if (nofence) (void)hipEventCreateWithFlags(&e, hipEventDisableSystemFence);
-  else (void)hipEventCreate(&e);
+  // 2 us less per record on the stream that is being timed)
+  (void)hipEventCreateWithFlags(&e, hipEventDisableSystemFence);
   return e;
 }
 
@@ -52,7 +50,7 @@ static hipEvent_t timer_event(gnx_state* h) {
 double g_host_step_s = 0.0, g_host_wait_s = 0.0;
 long long g_host_steps = 0;
 bool gnx_host_times() {
-  static const bool on = getenv("GNX_HOST_TIMES") && atoi(getenv("GNX_HOST_TIMES")) != 0;
+  static const bool on = gnx_env_int("GNX_HOST_TIMES", 0) != 0;
   return on;
 }
 // GNX_HOST_TIMES=2: the host's clock where a wait for the device returns (the moment the GPU has
@@ -60,7 +58,7 @@ bool gnx_host_times() {
 // of the step is slow without a profiler in the way
 static std::vector<std::pair<int, long long>> g_marks;
 void gnx_host_mark(int id) {
-  static const bool on = getenv("GNX_HOST_TIMES") && atoi(getenv("GNX_HOST_TIMES")) == 2;
+  static const bool on = gnx_env_int("GNX_HOST_TIMES", 0) == 2;
   if (!on) return;
   g_marks.emplace_back(id, (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(
                                std::chrono::steady_clock::now().time_since_epoch()).count());
@@ -96,21 +94,11 @@ struct GnxHostWait {
 // the step's main stream: a record costs that stream 5.5 us with the fence and 3.5 without, a
 // wait ~6; the step's own ten went from 0.621 to 0.606 ms (hipEventReleaseToDevice: nothing).
 // Events the HOST synchronises on (ev_counts) keep the fence.
-unsigned gnx_order_event_flags() {
-  static const int mode = getenv("GNX_EVENT_FLAGS") ? atoi(getenv("GNX_EVENT_FLAGS")) : 1;
-  if (mode == 1) return hipEventDisableTiming | hipEventDisableSystemFence;
-  if (mode == 2) return hipEventDisableTiming | hipEventReleaseToDevice;
-  return hipEventDisableTiming;
-}
+unsigned gnx_order_event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
 
 int gnx_wait_published(gnx_state* h, int slot, int64_t seq) {
   GnxHostWait hw;
   volatile int64_t* word = h->h_pin + slot + 3;
-  static const bool poll = !(getenv("GNX_POLL") && atoi(getenv("GNX_POLL")) == 0);
-  if (!poll) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  }
   const auto t0 = std::chrono::steady_clock::now();
   for (int spin = 0; *word != seq; ++spin) {
     if ((spin & 1023) == 1023 &&
@@ -301,30 +289,13 @@ extern "C" int gnx_create(const gnx_config* cfg, gnx_state** out) {
   // `stream` carries the step's many small latency-bound kernels, `stream2` the deferred
   // crossover (one long bandwidth-bound kernel per step, under the NEXT step's small
   // kernels): the small kernels get the higher dispatch priority so that they are not
-  // queued behind the crossover's workgroups, and the crossover can be kept off a few
-  // CUs of every XCD (GNX_XO_DROP=d: d of every 8 CUs; it is HBM-bound, not CU-bound)
+  // queued behind the crossover's workgroups (keeping the crossover off a few CUs of every XCD
+  // with a CU mask was measured and removed: profiles/r02_xo_overlap_*.txt)
   {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    const bool prio = !(getenv("GNX_XO_PRIO") && atoi(getenv("GNX_XO_PRIO")) == 0);
-    const int drop = getenv("GNX_XO_DROP") ? atoi(getenv("GNX_XO_DROP")) : 0;
-    if (prio) HIPCHK(hipStreamCreateWithPriority(&h->stream, hipStreamDefault, hi));
-    else HIPCHK(hipStreamCreate(&h->stream));
-    if (drop > 0 && drop < 8) {
-      hipDeviceProp_t prop;
-      HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
-      const int ncu = prop.multiProcessorCount;
-      std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-      // rotate the dropped CUs so that every XCD loses the same number whichever way the
-      // mask bits map to XCDs (striped or blocked)
-      for (int i = 0; i < ncu; ++i)
-        if ((i + i / 8) % 8 >= drop) mask[i / 32] |= 1u << (i % 32);
-      HIPCHK(hipExtStreamCreateWithCUMask(&h->stream2, (uint32_t)mask.size(), mask.data()));
-    } else if (prio) {
-      HIPCHK(hipStreamCreateWithPriority(&h->stream2, hipStreamDefault, lo));
-    } else {
-      HIPCHK(hipStreamCreate(&h->stream2));
-    }
+    HIPCHK(hipStreamCreateWithPriority(&h->stream, hipStreamDefault, hi));
+    HIPCHK(hipStreamCreateWithPriority(&h->stream2, hipStreamDefault, lo));
   }
   h->own_stream = true;
   for (int k = 0; k < 2; ++k) GNXCHK(alloc_soa(&h->soa[k], cap, cfg->n_layers, cfg->n_traits));
@@ -341,7 +312,7 @@ extern "C" int gnx_create(const gnx_config* cfg, gnx_state** out) {
     {
       const int lines = h->W64 / 16;
       const bool asked = getenv("GNX_HALF_BLOCKS") != nullptr;
-      int want = asked ? atoi(getenv("GNX_HALF_BLOCKS")) : 16;      // (more only when asked for)
+      int want = gnx_env_int("GNX_HALF_BLOCKS", 16);                // (more only when asked for)
       want = std::max(1, std::min(want, GNX_MAX_NB));
       while (want > 1 && (lines % want || (!asked && lines / want < 2) ||
                           (double)h->cfg.cap_rows * 4 * 2.0 * want >= 2.0e9))
@@ -356,7 +327,7 @@ extern "C" int gnx_create(const gnx_config* cfg, gnx_state** out) {
       // 2.7, the crossover launch 0.147 ms instead of 0.178 for 0.49 GB instead of 0.70; with 25
       // blocks it shrinks further (0.132 ms) but the job builder's tables grow as much.
       // GNX_BLOCK_LINES=k: blocks of exactly k lines; 0: the divisor rule above whatever the length
-      int bl = getenv("GNX_BLOCK_LINES") ? atoi(getenv("GNX_BLOCK_LINES")) : -1;
+      int bl = gnx_env_int("GNX_BLOCK_LINES", -1);
       if (bl < 0) bl = (!asked && lines >= 40) ? std::max(5, (lines + GNX_MAX_NB - 1) / GNX_MAX_NB) : 0;
       if (bl > 0 && (double)h->cfg.cap_rows * 4 * 2.0 * ((lines + bl - 1) / bl) >= 2.0e9) bl = 0;
       if (bl > 0 && (lines + bl - 1) / bl <= GNX_MAX_NB && (lines + bl - 1) / bl >= 1) {
@@ -374,7 +345,7 @@ extern "C" int gnx_create(const gnx_config* cfg, gnx_state** out) {
       const size_t need = (size_t)h->cfg.cap_rows * 2 * std::max(h->W64, h->NB * h->BW) * 8;
       size_t free_b = 0, total_b = 0;
       (void)hipMemGetInfo(&free_b, &total_b);
-      int want = getenv("GNX_ROW_SPREAD") ? atoi(getenv("GNX_ROW_SPREAD")) : 4;
+      int want = gnx_env_int("GNX_ROW_SPREAD", 4);
       want = std::max(1, std::min(want, 8));
       while (want > 1 && ((double)need * want > 0.75 * (double)free_b ||
                           (double)h->cfg.cap_rows * want > 1.0e9))
@@ -408,7 +379,7 @@ extern "C" int gnx_create(const gnx_config* cfg, gnx_state** out) {
     HIPCHK(hipMemset(h->xo_jobs_acc, 0, 2 * sizeof(unsigned long long)));
     HIPCHK(hipMemset(h->hmap, 0xff, halves * sizeof(int32_t)));
     HIPCHK(hipMemset(h->half_top, 0, sizeof(int32_t)));
-    if (getenv("GNX_XO_ALIAS")) h->alias_xo = atoi(getenv("GNX_XO_ALIAS")) != 0;
+    h->alias_xo = gnx_env_int("GNX_XO_ALIAS", 1) != 0;
   }
   for (int k = 0; k < 2; ++k) {
     GNXCHK(dalloc(&h->key[k], cap));
@@ -439,17 +410,10 @@ extern "C" int gnx_create(const gnx_config* cfg, gnx_state** out) {
   GNXCHK(dalloc(&h->cell32, cap));
   GNXCHK(dalloc(&h->ord_cnt, cap / GNX_CB + 2));
   GNXCHK(dalloc(&h->ord_off, cap / GNX_CB + 2));
-  {
-    // (k_ord_compact: one look-back word per workgroup of 1 024 entries, the tickets behind them
-    // at [blk_stride]; zero between launches)
-    const size_t words = (size_t)((cap + 1023) / 1024) + 2 + 16;
-    GNXCHK(dalloc(&h->ord_state, words));
-    HIPCHK(hipMemset(h->ord_state, 0, words * sizeof(uint32_t)));
-  }
   HIPCHK(hipEventCreateWithFlags(&h->ev_ord, gnx_order_event_flags()));
   HIPCHK(hipStreamCreate(&h->stream3));
   HIPCHK(hipEventCreateWithFlags(&h->ev_compact, gnx_order_event_flags()));
-  if (getenv("GNX_ORD_SORT")) h->ord_mode = atoi(getenv("GNX_ORD_SORT")) != 0;
+  h->ord_mode = gnx_env_int("GNX_ORD_SORT", 1) != 0;
   GNXCHK(dalloc(&h->tag, cap));
   HIPCHK(hipMalloc(&h->cand, (size_t)cap * 16));
   GNXCHK(dalloc(&h->flag, cap + 1));
@@ -517,26 +481,18 @@ extern "C" int gnx_create(const gnx_config* cfg, gnx_state** out) {
     HIPCHK(hipEventCreateWithFlags(&h->ev_jobs, gnx_order_event_flags()));
   }
   HIPCHK(hipEventCreateWithFlags(&h->ev_counts, hipEventDisableTiming));
-  h->defer_xo = !(getenv("GNX_DEFER_XO") && atoi(getenv("GNX_DEFER_XO")) == 0);
   // When the deferred crossover of step t goes on its stream (csrc/gnx_kernels_genome.hip:
-  // gnx_xo_launch_pending): 0 as soon as its jobs are built (it runs beside the next step's
-  // movement), 1 / 2 behind the next step's cell sort / pair list.  Since gnx_walk leaves no
+  // gnx_xo_launch_pending): as soon as its jobs are built (it runs beside the next step's
+  // movement), or (xo_launch_late) behind the next step's pair list.  Since gnx_walk leaves no
   // compaction between its steps (round 6) the head of a step is the movement alone, and a
   // crossover that runs beside the births, the densities, the death draws and the next job
   // builder instead - latency-bound chains that leave the memory system idle - costs the step
   // least: 0.502 against 0.518 ms at the metric workload (profiles/r06_ab_runs.txt).  Large
   // populations only: the device-driven step of the small ones (gnx_dd.hip) schedules its own.
-  {
-    static const int64_t dd_cap = getenv("GNX_DD_MAX_CAP") ? atoll(getenv("GNX_DD_MAX_CAP")) : 600000;
-    h->xo_launch_policy = cap > dd_cap ? 2 : 0;
-    if (getenv("GNX_XO_LAUNCH")) h->xo_launch_policy = atoi(getenv("GNX_XO_LAUNCH"));
-    h->xo_launch_default = h->xo_launch_policy;
-  }
-  if (getenv("GNX_COMPACT_FILL")) h->compact_fill = atoi(getenv("GNX_COMPACT_FILL")) != 0;
-  if (getenv("GNX_PERMUTE_SPLIT")) h->permute_split = atoi(getenv("GNX_PERMUTE_SPLIT")) != 0;
-  if (getenv("GNX_XO_SORT_WAIT")) h->xo_sort_waits = atoi(getenv("GNX_XO_SORT_WAIT")) != 0;
-  if (getenv("GNX_XO_WAIT")) h->xo_wait_at = atoi(getenv("GNX_XO_WAIT"));
-  if (getenv("GNX_XO_SPLIT")) h->xo_split = std::min(1024, std::max(0, atoi(getenv("GNX_XO_SPLIT"))));
+  // (behind the cell sort, the births or the densities: measured and removed, profiles/r06_ab_runs.txt)
+  h->xo_launch_late = h->xo_launch_late_default = cap > gnx_dd_max_cap();
+  h->compact_fill = gnx_env_int("GNX_COMPACT_FILL", 1) != 0;
+  h->permute_split = gnx_env_int("GNX_PERMUTE_SPLIT", 1) != 0;
   *out = h;
   return 0;
 }
@@ -573,7 +529,7 @@ extern "C" void gnx_destroy(gnx_state* h) {
     (void)hipFree(h->perm[k]);
     (void)hipFree(h->counts_rast[k]);
   }
-  void* ptrs[] = {h->os_scratch, h->os_ktmp, h->os_vtmp, h->fill_cnt, h->ord[0], h->ord[1], h->keyk[0], h->keyk[1], h->valk[0], h->valk[1], h->newslot, h->cell32, h->ord_cnt, h->ord_off, h->ord_state, h->route_geo_dev, h->xo_plan, h->gc_cnt, h->gc_off, h->half_mark, h->hmap, h->half_free, h->half_top, h->xo_jobs_acc, h->rast, h->G, h->free_rows, h->paths, h->bp_off, h->bp_loci, h->dom,
+  void* ptrs[] = {h->os_scratch, h->os_ktmp, h->os_vtmp, h->fill_cnt, h->ord[0], h->ord[1], h->keyk[0], h->keyk[1], h->valk[0], h->valk[1], h->newslot, h->cell32, h->ord_cnt, h->ord_off, h->route_geo_dev, h->xo_plan, h->gc_cnt, h->gc_off, h->half_mark, h->hmap, h->half_free, h->half_top, h->xo_jobs_acc, h->rast, h->G, h->free_rows, h->paths, h->bp_off, h->bp_loci, h->dom,
                   h->delet_loci, h->delet_s, h->cell_start, h->tag, h->cand, h->sort64_tmp, h->key64[0], h->key64[1], h->pairs2,
                   h->pair_goff, h->st_rec, h->st_z, h->st_geno, h->st_slots, h->req_pid, h->req_k, h->req_key, h->req_start, h->req_px, h->req_py,
                   h->req_count, h->sort_tmp, h->scan_tmp, h->mate,
@@ -603,11 +559,6 @@ extern "C" void gnx_destroy(gnx_state* h) {
     (void)hipStreamDestroy(h->stream3);
   }
   if (h->ev_ord) (void)hipEventDestroy(h->ev_ord);
-  if (h->ev_move) (void)hipEventDestroy(h->ev_move);
-  if (h->stream4) {
-    (void)hipStreamSynchronize(h->stream4);
-    (void)hipStreamDestroy(h->stream4);
-  }
   if (h->ev_compact) (void)hipEventDestroy(h->ev_compact);
   if (h->ev_fill) (void)hipEventDestroy(h->ev_fill);
   if (h->ev_alive) (void)hipEventDestroy(h->ev_alive);
@@ -634,7 +585,6 @@ extern "C" int gnx_set_stream(gnx_state* h, void* hip_stream) {
 extern "C" int gnx_synchronize(gnx_state* h) {
   GNXCHK(gnx_xo_launch_pending(h));
   if (h->stream3) HIPCHK(hipStreamSynchronize(h->stream3));
-  if (h->stream4) HIPCHK(hipStreamSynchronize(h->stream4));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (h->stream2) HIPCHK(hipStreamSynchronize(h->stream2));
   return 0;
@@ -762,8 +712,7 @@ static int setup_hash_grid(gnx_state* h) {
   // C2 / C3 unchanged, the metric workload 4 % slower (two more key bits, four times the cell
   // bounds, against a rejection rate that falls from 65 to 50 %) - so the default stays 1.
   else if (r > 0) {
-    const char* e = getenv("GNX_CELL_DIV");
-    const int cell_div = e ? std::max(1, std::min(2, atoi(e))) : 1;
+    const int cell_div = std::max(1, std::min(2, gnx_env_int("GNX_CELL_DIV", 1)));
     cs /= (double)cell_div;
   }
   // bound the number of cells (<= 2048 per axis)
@@ -1158,8 +1107,7 @@ extern "C" int gnx_pop_dynamics_mate(gnx_state* h, int32_t burn) {
   GNXCHK(gnx_l_sort_by_cell(h, true));
   // 2. n_pairs density of the pair midpoints (ops/demography.py:60-91), launched inside
   //    find_pairs while the pair count travels to the host
-  static const bool early = !(getenv("GNX_EARLY_DENSITY") && atoi(getenv("GNX_EARLY_DENSITY")) == 0);
-  int rc_pairs = gnx_l_find_pairs(h, nullptr, &P, early);
+  int rc_pairs = gnx_l_find_pairs(h, nullptr, &P, true);
   GNXCHK(gnx_wait_permute_rest(h));
   GNXCHK(rc_pairs);
   if (P > 0 && !h->spl_P.valid)
@@ -1219,15 +1167,7 @@ extern "C" int gnx_step_begin(gnx_state* h, int32_t burn) {
   h->last_xo_births = 0;
   h->step_burn = burn != 0;
   h->tile2_mode = false;        // (a handle that stepped through the tile protocol before)
-  if (h->moved_ahead) {
-    // gnx_walk: the last step's mortality has moved everybody already (gnx_l_move_ahead) and
-    // the compaction carried the sort's keys along
-    h->moved_ahead = false;
-    h->keys_fresh = h->sp.mating_radius >= 0;
-    h->keys_ordmode = true;
-    h->fb_adults = false;
-    h->fb_pending = false;
-  } else if (h->sp.move) {
+  if (h->sp.move) {
     h->move_writes_keys = h->sp.mating_radius >= 0;     // the cell sort follows at once
     int rc = gnx_l_move(h, true, nullptr, nullptr, nullptr, nullptr, true);
     h->move_writes_keys = false;
@@ -1239,21 +1179,15 @@ extern "C" int gnx_step_begin(gnx_state* h, int32_t burn) {
   // not read are permuted on the side stream meanwhile, and waited for before the births);
   // the n_pairs density of the pair midpoints (ops/demography.py:60-91) is launched with the
   // pair list, while the pair count travels to the host
-  h->perm_rest_late_ok = true;
-  int rc_sort = gnx_l_sort_by_cell(h, true);
-  h->perm_rest_late_ok = false;
-  GNXCHK(rc_sort);
-  static const bool early = !(getenv("GNX_EARLY_DENSITY") && atoi(getenv("GNX_EARLY_DENSITY")) == 0);
-  int rc_pairs = gnx_l_find_pairs_enqueue(h, nullptr, early);
-  GNXCHK(gnx_wait_permute_rest(h, true));
+  GNXCHK(gnx_l_sort_by_cell(h, true));
+  int rc_pairs = gnx_l_find_pairs_enqueue(h, nullptr, true);
+  GNXCHK(gnx_wait_permute_rest(h));
   return rc_pairs;
 }
 
 extern "C" int gnx_step_mid(gnx_state* h, int32_t burn, int32_t with_selection) {
   GnxStepTimer timer(false);
   int64_t P = 0, B = 0;
-  // (the births go on the stream before the host has the pair count: gnx_l_offspring_ahead)
-  GNXCHK(gnx_l_offspring_ahead(h, burn != 0));
   GNXCHK(gnx_l_find_pairs_finish(h, &P));
   if (P > 0 && !h->spl_P.valid)
     GNXCHK(gnx_l_density(h, P, h->mid_x, h->mid_y, &h->spl_P, nullptr));
@@ -1261,12 +1195,9 @@ extern "C" int gnx_step_mid(gnx_state* h, int32_t burn, int32_t with_selection) 
   // gnx_set_id_order: the pairs' offsets from this device's own counts - gnx_l_mate)
   GNXCHK(gnx_l_mate(h, burn != 0, false, 0, &B));
   h->last_births = B;
-  if (h->xo_launch_policy == 4) GNXCHK(gnx_xo_launch_pending(h, -1));     // (behind the births)
   // N density of everyone incl. offspring (structs/species.py:845-882); d at each
   // individual's cell, fitness, death probability; mortality
   GNXCHK(gnx_l_density_N(h));
-  if (h->xo_launch_policy == 3) GNXCHK(gnx_xo_launch_pending(h, -1));     // (behind the densities)
-  GNXCHK(gnx_wait_permute_rest(h));       // (GNX_PERMUTE_REST_AT=2: environment, phenotypes, rows arrive here)
   GNXCHK(gnx_l_death_probs(h, with_selection != 0 && !burn));
   return gnx_l_mortality_enqueue(h, nullptr);
 }
@@ -1410,11 +1341,10 @@ extern "C" int gnx_last_crossover_jobs(gnx_state* h, void* dst, int64_t max_jobs
 extern "C" int gnx_set_crossover_overlap(gnx_state* h, int32_t mode) {
   h->cfg_epoch += 1;
   GNXCHK(gnx_xo_join(h));
-  static const int wait_env = getenv("GNX_XO_WAIT") ? atoi(getenv("GNX_XO_WAIT")) : 1;
   h->xo_sort_waits = mode != 1;
-  h->xo_wait_at = mode == 2 ? 2 : wait_env;      // 2: nothing else runs beside the crossover
+  h->xo_wait_at = mode == 2 ? 2 : 1;      // 2: nothing else runs beside the crossover
   // (the other modes launch the crossover as soon as its jobs are built)
-  h->xo_launch_policy = mode == 0 ? h->xo_launch_default : 0;
+  h->xo_launch_late = mode == 0 && h->xo_launch_late_default;
   return 0;
 }
 

@@ -26,13 +26,11 @@ using GraphMap = std::map<uint32_t, hipGraphExec_t>;
 
 struct DDExtra {             // host-side state of the device-driven mode
   GraphMap graphs;
-  hipEvent_t ev[8]{};
-  bool have_ev = false;
-  // Streams the step is CAPTURED on (the graph is launched on the handle's own stream).  They
-  // are non-blocking: while a blocking stream captures, any hipMemcpy on the legacy stream -
+  // The stream the step is CAPTURED on (the graph is launched on the handle's own stream).  It
+  // is non-blocking: while a blocking stream captures, any hipMemcpy on the legacy stream -
   // another handle's, on another host thread - fails ("would make the legacy stream depend on
   // a capturing blocking stream").
-  hipStream_t cap[3]{};
+  hipStream_t cap = nullptr;
   bool capturing = false;
   uint64_t epoch = 0;        // h's configuration epoch the graphs were captured under
 };
@@ -42,23 +40,17 @@ DDExtra* extra(gnx_state* h) {
   return (DDExtra*)h->dd_graph[0];
 }
 
-bool env_on(const char* name, bool dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) != 0 : dflt;
-}
+bool dd_debug() { return gnx_env_int("GNX_DD_DEBUG", 0) != 0; }
 }  // namespace
-
-unsigned gnx_order_event_flags();
 
 bool gnx_dd_eligible(const gnx_state* h, bool burn) {
   // GNX_DD=0: never; 2: whatever the size.  By default populations whose step the host cannot
   // enqueue as fast as the GPU runs it (capacity up to GNX_DD_MAX_CAP slots, 600 000): at 10^6
   // individuals the host-driven step is the faster one - its crossover runs under the next
   // step's movement and its grids fit the population (0.60 against 0.70 ms per step)
-  const int mode = getenv("GNX_DD") ? atoi(getenv("GNX_DD")) : 1;
-  static const int64_t max_cap = getenv("GNX_DD_MAX_CAP") ? atoll(getenv("GNX_DD_MAX_CAP")) : 600000;
+  const int mode = gnx_env_int("GNX_DD", 1);
   if (mode == 0 || !h->have_sp || h->tiled || h->profiling) return false;
-  if (mode != 2 && h->cfg.cap_inds > max_cap) return false;
+  if (mode != 2 && h->cfg.cap_inds > gnx_dd_max_cap()) return false;
   const gnx_species_params& sp = h->sp;
   if (sp.mating_radius < 0 || !sp.n_births_fixed || !sp.move) return false;
   if (!h->ord_mode || h->key_bits > 24 || !h->compact_fill || !h->defer_xo) return false;
@@ -67,37 +59,29 @@ bool gnx_dd_eligible(const gnx_state* h, bool burn) {
   // classification inside k_pair_compact, one more node for the blocks' offsets)
   if (h->NB > GNX_MAX_NB || h->n_ghost != 0) return false;
   if (h->cfg.cap_inds >= (1ll << 30)) return false;
-  // (a launch policy other than the handle's own default was asked for: the host-driven step honours it)
-  if ((h->xo_launch_policy != 0 && h->xo_launch_policy != h->xo_launch_default) || h->xo_split != 0)
-    return false;
+  // (a split crossover launch was asked for: the host-driven step honours it)
+  if (h->xo_split != 0) return false;
   (void)burn;
   return true;
 }
 
-static int dd_events(gnx_state* h) {
+static int dd_capture_stream(gnx_state* h) {
   DDExtra* x = extra(h);
-  if (x->have_ev) return 0;
-  for (int k = 0; k < 8; ++k) HIPCHK(hipEventCreateWithFlags(&x->ev[k], gnx_order_event_flags()));
-  for (int k = 0; k < 3; ++k) HIPCHK(hipStreamCreateWithFlags(&x->cap[k], hipStreamNonBlocking));
-  x->have_ev = true;
+  if (!x->cap) HIPCHK(hipStreamCreateWithFlags(&x->cap, hipStreamNonBlocking));
   return 0;
 }
 
-// one step, enqueued on the handle's three streams (inside a stream capture: the body of the
-// step's graph).  Host state only flips its buffer parities.
+// one step, enqueued on ONE stream (inside a stream capture: the body of the step's graph).  A
+// linear graph replays at ~2 us per node, one with side branches at ~30 (ROCm 7.2,
+// tools/launch_micro.hip and DESIGN 4.4: 0.21 against 1.0 ms per step at 10^5 individuals) - the
+// densities and the lists on side streams as in gnx_step were measured and removed (1.325 against
+// 0.549 ms, profiles/r06_ab_runs.txt).  Host state only flips its buffer parities.
 static int dd_enqueue_step(gnx_state* h, bool burn, bool sel) {
   DDExtra* x = extra(h);
   const gnx_config& c = h->cfg;
-  // The whole step on ONE stream: a linear graph replays at ~2 us per node, one with side
-  // branches at ~30 (ROCm 7.2, tools/launch_micro.hip and DESIGN 4.4: 0.21 against 1.0 ms per
-  // step at 10^5 individuals) - and an event hand-over costs the host 12 us where a launch
-  // costs 3.  GNX_DD_STREAMS=3: the densities and the lists on the side streams as in gnx_step.
-  const bool one = !(getenv("GNX_DD_STREAMS") && atoi(getenv("GNX_DD_STREAMS")) == 3);
-  hipStream_t s1 = x->capturing ? x->cap[0] : h->stream;
-  hipStream_t s2 = one ? s1 : (x->capturing ? x->cap[1] : h->stream2);
-  hipStream_t s3 = one ? s1 : (x->capturing ? x->cap[2] : h->stream3);
+  hipStream_t st = x->capturing ? x->cap : h->stream;
   hipStream_t own = h->stream;
-  h->stream = s1;                 // (the launchers that take no stream argument)
+  h->stream = st;                 // (the launchers that take no stream argument)
   struct Restore {
     gnx_state* h;
     hipStream_t s;
@@ -113,43 +97,23 @@ static int dd_enqueue_step(gnx_state* h, bool burn, bool sel) {
   int rc = gnx_l_move(h, true, nullptr, nullptr, nullptr, nullptr, true);
   h->move_writes_keys = false;
   GNXCHK(rc);
-  // mating pairs over the cell-sorted population; the adults' density bins beside the search
-  // (one stream: the two fields' bins are counted by k_permute and k_pair_compact themselves -
-  // two launches of ~5 us less on a chain of ~20; GNX_DD_FUSE_BINS=0: launches of their own)
-  const bool fuse_bins = one && !(getenv("GNX_DD_FUSE_BINS") && atoi(getenv("GNX_DD_FUSE_BINS")) == 0);
-  GNXCHK(gnx_dd_l_sort(h, fuse_bins ? h->fb[par] : nullptr, s1));
-  HIPCHK(hipEventRecord(x->ev[0], s1));
-  HIPCHK(hipStreamWaitEvent(s3, x->ev[0], 0));
-  if (!fuse_bins) GNXCHK(gnx_dd_l_bins_adults(h, par, s3));
-  GNXCHK(gnx_dd_l_pairs(h, fuse_bins ? h->fb[2] : nullptr, s1));
-  // the pairs' density beside the births
-  HIPCHK(hipEventRecord(x->ev[1], s1));
-  HIPCHK(hipStreamWaitEvent(s3, x->ev[1], 0));
-  if (!fuse_bins) GNXCHK(gnx_dd_l_density_pairs(h, s3));
-  HIPCHK(hipEventRecord(x->ev[2], s3));
-  GNXCHK(gnx_dd_l_offspring(h, genomes, h->fb[par], s1));
+  // mating pairs over the cell-sorted population; the two density fields' bins are counted by
+  // k_permute and k_pair_compact themselves (two launches of ~5 us less on a chain of ~20)
+  GNXCHK(gnx_dd_l_sort(h, h->fb[par], st));
+  GNXCHK(gnx_dd_l_pairs(h, h->fb[2], st));
+  GNXCHK(gnx_dd_l_offspring(h, genomes, h->fb[par], st));
   // densities, death probabilities, death draws
-  HIPCHK(hipStreamWaitEvent(s1, x->ev[2], 0));
-  GNXCHK(gnx_dd_l_density_N(h, par, s1));
-  GNXCHK(gnx_dd_l_death_probs(h, sel && !burn, par, s1));
-  GNXCHK(gnx_dd_l_alive(h, xo, buf, s1));
-  // the compaction's lists beside the crossover's job builder; the crossover beside the
-  // compaction and the index's own compaction
-  HIPCHK(hipEventRecord(x->ev[3], s1));
-  HIPCHK(hipStreamWaitEvent(s3, x->ev[3], 0));
-  GNXCHK(gnx_dd_l_fill_lists(h, has_rows, s3));
-  HIPCHK(hipEventRecord(x->ev[4], s3));
+  GNXCHK(gnx_dd_l_density_N(h, par, st));
+  GNXCHK(gnx_dd_l_death_probs(h, sel && !burn, par, st));
+  GNXCHK(gnx_dd_l_alive(h, xo, buf, st));
+  // the compaction's lists, the crossover's jobs and the crossover, the compaction, the index
+  GNXCHK(gnx_dd_l_fill_lists(h, has_rows, st));
   if (xo) {
-    GNXCHK(gnx_dd_l_jobs(h, buf, s1));
-    HIPCHK(hipEventRecord(x->ev[5], s1));
-    HIPCHK(hipStreamWaitEvent(s2, x->ev[5], 0));
-    GNXCHK(gnx_dd_l_crossover(h, buf, s2));
-    HIPCHK(hipEventRecord(x->ev[6], s2));
+    GNXCHK(gnx_dd_l_jobs(h, buf, st));
+    GNXCHK(gnx_dd_l_crossover(h, buf, st));
   }
-  HIPCHK(hipStreamWaitEvent(s1, x->ev[4], 0));
-  GNXCHK(gnx_dd_l_fill(h, has_rows, xo, s1));
-  if (xo) HIPCHK(hipStreamWaitEvent(s1, x->ev[6], 0));
-  GNXCHK(gnx_dd_l_ord_end(h, has_rows, xo, s1));
+  GNXCHK(gnx_dd_l_fill(h, has_rows, xo, st));
+  GNXCHK(gnx_dd_l_ord_end(h, has_rows, xo, st));
   if (xo) h->jobs_cur ^= 1;
   h->fb_cur ^= 1;
   return 0;
@@ -178,8 +142,7 @@ static void dd_drop_graphs(gnx_state* h) {
 // k consecutive steps in ONE graph (between two replays the GPU idles ~9 us - the start of a
 // graph - whatever it holds: four steps per graph share that)
 static int dd_launch_step(gnx_state* h, bool burn, bool sel, int k) {
-  const bool use_graph = env_on("GNX_DD_GRAPH", true);
-  if (!use_graph) {
+  if (gnx_env_int("GNX_DD_GRAPH", 1) == 0) {
     for (int q = 0; q < k; ++q) GNXCHK(dd_enqueue_step(h, burn, sel));
     return 0;
   }
@@ -190,12 +153,12 @@ static int dd_launch_step(gnx_state* h, bool burn, bool sel, int k) {
     const auto tc0 = std::chrono::steady_clock::now();
     hipGraph_t g = nullptr;
     const int cur0 = h->cur, ord0 = h->ord_cur, jobs0 = h->jobs_cur, fb0 = h->fb_cur;
-    HIPCHK(hipStreamBeginCapture(x->cap[0], hipStreamCaptureModeThreadLocal));
+    HIPCHK(hipStreamBeginCapture(x->cap, hipStreamCaptureModeThreadLocal));
     x->capturing = true;
     int rc = 0;
     for (int q = 0; q < k && !rc; ++q) rc = dd_enqueue_step(h, burn, sel);
     x->capturing = false;
-    hipError_t e = hipStreamEndCapture(x->cap[0], &g);
+    hipError_t e = hipStreamEndCapture(x->cap, &g);
     // (the capture enqueued nothing: the host's parities are those before it)
     h->cur = cur0;
     h->ord_cur = ord0;
@@ -217,7 +180,7 @@ static int dd_launch_step(gnx_state* h, bool burn, bool sel, int k) {
       return 1;
     }
     it = x->graphs.emplace(key, ex).first;
-    if (env_on("GNX_DD_DEBUG", false))
+    if (dd_debug())
       fprintf(stderr, "[gnx dd] graph %u captured and instantiated in %.2f ms\n", key,
               1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tc0).count());
   }
@@ -310,7 +273,7 @@ static int dd_enter(gnx_state* h) {
   struct Report {
     std::chrono::steady_clock::time_point t0;
     ~Report() {
-      if (env_on("GNX_DD_DEBUG", false))
+      if (dd_debug())
         fprintf(stderr, "[gnx dd] enter took %.2f ms\n",
                 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     }
@@ -322,7 +285,7 @@ static int dd_enter(gnx_state* h) {
   HIPCHK(hipStreamSynchronize(h->stream2));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->latP_inflight = h->binsN_inflight = h->ord_inflight = false;
-  GNXCHK(dd_events(h));
+  GNXCHK(dd_capture_stream(h));
   if (!h->dd) {
     HIPCHK(hipMalloc((void**)&h->dd, sizeof(GnxDD)));
     HIPCHK(hipHostMalloc((void**)&h->dd_ring, GNX_DD_RING * sizeof(GnxDDRec),
@@ -363,7 +326,7 @@ static int dd_enter(gnx_state* h) {
 
 int gnx_dd_leave(gnx_state* h) {
   if (!h->dd_active) return 0;
-  if (env_on("GNX_DD_DEBUG", false))
+  if (dd_debug())
     fprintf(stderr, "[gnx dd] leave: %lld steps enqueued, %lld seen, collections so far %lld\n",
             (long long)h->dd_seq, (long long)h->dd_seen, (long long)h->gc_runs);
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -410,10 +373,7 @@ void gnx_dd_destroy(gnx_state* h) {
   if (h->dd_graph[0]) {
     dd_drop_graphs(h);
     DDExtra* x = extra(h);
-    if (x->have_ev) {
-      for (int k = 0; k < 8; ++k) (void)hipEventDestroy(x->ev[k]);
-      for (int k = 0; k < 3; ++k) (void)hipStreamDestroy(x->cap[k]);
-    }
+    if (x->cap) (void)hipStreamDestroy(x->cap);
     delete x;
     h->dd_graph[0] = nullptr;
   }
@@ -466,11 +426,11 @@ static int dd_blocks(gnx_state* h, bool burn) {
   return 0;
 }
 
-// up to `most` steps; *taken = how many were enqueued (GNX_DD_STEPS_PER_GRAPH at a time, 4 by
-// default, while the free blocks are certain to last; one otherwise)
+// up to `most` steps; *taken = how many were enqueued (GNX_DD_STEPS_PER_GRAPH at a time while the
+// free blocks are certain to last; one otherwise)
+constexpr int GNX_DD_STEPS_PER_GRAPH = 4;
 static int dd_some(gnx_state* h, bool burn, bool sel, int64_t most, int64_t* taken) {
-  static const int per_graph =
-      std::max(1, std::min(16, getenv("GNX_DD_STEPS_PER_GRAPH") ? atoi(getenv("GNX_DD_STEPS_PER_GRAPH")) : 4));
+  constexpr int per_graph = GNX_DD_STEPS_PER_GRAPH;
   dd_consume(h);
   GNXCHK(dd_check(h));
   GNXCHK(dd_blocks(h, burn));
@@ -561,8 +521,8 @@ extern "C" int gnx_walk_many(gnx_state** hs, int32_t n, int64_t T, int32_t burn,
         rc = dd_some(hs[k], burn != 0, with_selection != 0, left[k], &taken);
       } else {
         const int64_t n0 = hs[k]->N - hs[k]->n_ghost;
-        // (every step but the walk's last moves the population for the next one with its own
-        // mortality: nobody looks at it in between - gnx_l_move_ahead)
+        // (every step but the walk's last leaves its dead in place for the next one's cell sort:
+        // nobody looks at the population in between - gnx_l_mortality_enqueue: lazy)
         hs[k]->eager_move = left[k] > 1;
         rc = gnx_step(hs[k], burn, with_selection);
         hs[k]->eager_move = false;

@@ -18,6 +18,18 @@
 
 void gnx_set_error(const char* fmt, ...);
 
+// the GNX_* environment switches that are left (DESIGN.md lists them): an integer, or dflt when unset
+static inline int gnx_env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+// slots up to which gnx_walk takes the device-driven step (gnx_dd.hip) - and above which the
+// host-driven step launches its crossover late (gnx_create)
+static inline int64_t gnx_dd_max_cap() {       // (64 bits: a capacity)
+  static const int64_t v = getenv("GNX_DD_MAX_CAP") ? atoll(getenv("GNX_DD_MAX_CAP")) : 600000;
+  return v;
+}
+
 #define HIPCHK(expr)                                                          \
   do {                                                                        \
     hipError_t _e = (expr);                                                   \
@@ -351,7 +363,7 @@ struct gnx_state {
   // crossover jobs (csrc/gnx_xo.h).  Deferred mode (one GPU): the offspring of a step get
   // their genome rows and their crossover only after the step's death draws, survivors
   // only, on stream2 - under the next step's latency-bound kernels on `stream`.
-  bool defer_xo = true;          // GNX_DEFER_XO=0: crossover of every birth at once
+  bool defer_xo = true;          // gnx_set_defer_crossover(0): crossover of every birth at once
   bool xo_deferred = false;      // births of this step still wait for their crossover
   int64_t xo_first = 0, xo_B = 0;
   void* jobs[2]{};               // GnxXoJob [2 * cap] each, double-buffered
@@ -373,15 +385,15 @@ struct gnx_state {
   // bandwidth-bound kernel saturates HBM, and the crossover loses a third of its rate to
   // them.  Default: the crossover is launched as soon as its jobs are built, at full
   // width, and runs under the compaction, the next step's movement and sort keys; `stream`
-  // then WAITS for it before the cell sort (xo_sort_waits).  GNX_XO_SORT_WAIT=0 lets the
-  // whole next step run beside a narrow crossover (2 workgroups per CU): ~10 % more
+  // then WAITS for it before the cell sort (xo_sort_waits).  gnx_set_crossover_overlap(1) lets
+  // the whole next step run beside a narrow crossover (2 workgroups per CU): ~10 % more
   // individual-timesteps/s, but the crossover then stretches over the whole step.
-  // xo_launch_policy 1 / 2 launch it after the next step's cell sort / pair sort instead.
-  int xo_launch_policy = 0;
-  int xo_launch_default = 0;     // ... as chosen at gnx_create (gnx_set_crossover_overlap(0) returns to it)
+  // xo_launch_late: it is launched behind the next step's pair list instead (large capacities).
+  bool xo_launch_late = false;
+  bool xo_launch_late_default = false;   // ... as chosen at gnx_create (gnx_set_crossover_overlap(0) returns to it)
   bool xo_sort_waits = true;
-  // where `stream` waits for the full-width crossover (GNX_XO_WAIT): 1 before the next cell
-  // sort, 2 right after launching it (strictly serial), 3 after the compaction
+  // where `stream` waits for the full-width crossover (gnx_set_crossover_overlap): 1 before the
+  // next cell sort, 2 right after launching it (strictly serial)
   int xo_wait_at = 1;
   int xo_ready_buf = -1;         // jobs built, kernel not launched yet
   int64_t xo_ready_jobs = 0;
@@ -424,7 +436,6 @@ struct gnx_state {
   int64_t* vt_base = nullptr;
   int64_t n_births_pending = 0;  // births of the current pair list
   bool step_burn = false;        // gnx_step_begin: this step is a burn-in step
-  bool births_ahead = false;     // k_offspring of the current pair list is already on the stream (gnx_l_offspring_ahead)
   // gamete requests (tiled runs)
   int64_t* req_pid = nullptr;
   int32_t* req_k = nullptr;
@@ -554,8 +565,6 @@ struct gnx_state {
   bool permute_split = true;        // GNX_PERMUTE_SPLIT=0 (read at gnx_create): one k_permute for every column
   bool perm_rest_inflight = false;  // k_permute_rest (stream3) has not been waited for
   bool perm_rest_pending = false;   // ... has not been launched yet
-  bool perm_rest_late_ok = false;   // set by gnx_step around its cell sort: nothing reads the columns before the death probabilities
-  bool perm_rest_late = false;      // this sort's columns follow beside the births (GNX_PERMUTE_REST_AT=2)
   GnxSoA perm_rest_a{}, perm_rest_b{};
   int64_t perm_rest_N = 0;
   hipEvent_t ev_perm_rest = nullptr;
@@ -569,10 +578,9 @@ struct gnx_state {
   uint32_t* cell32 = nullptr;    // [cap] hash cell of each slot (k_move / k_keys)
   uint32_t* keyk[2]{};           // cells in id order / sorted
   int32_t* valk[2]{};            // id ranks in id order / sorted
-  void* os_scratch = nullptr;    // gnx_os_sort32: histograms, look-back states, block counters
+  void* os_scratch = nullptr;    // gnx_os_sort32_*: histograms, look-back states, block counters
   uint32_t* os_ktmp = nullptr;   // ... and the pairs between two digit places
   int32_t* os_vtmp = nullptr;
-  uint32_t* ord_state = nullptr; // k_ord_compact: [blk_stride] look-back words + [8] tickets, zero between launches
   int32_t* ord_cnt = nullptr;    // block counts / offsets of the index's own compaction
   int32_t* ord_off = nullptr;
   hipEvent_t ev_ord = nullptr;
@@ -584,7 +592,6 @@ struct gnx_state {
   // passes.  Whoever uses os_scratch otherwise, or drops the keys, clears the counts first
   // (gnx_os_hist_discard).
   bool hist_fresh = false;
-  // gnx_walk: the next step's movement runs with this step's mortality (gnx_l_move_ahead)
   // gnx_walk, between two of its steps: the mortality leaves the dead where they are - no
   // compaction at all (k_fill_lists, k_fill: ~40 us alone, 130 beside the crossover, and the next
   // movement behind them).  The next step's movement skips the dead (their flags: h->flag), the
@@ -606,9 +613,6 @@ struct gnx_state {
   bool tile_lazy_ok = false;     // set by gnx_tile_walk for every step but its last
   int64_t holes_flagged = 0;
   bool eager_move = false;       // set by gnx_walk for every step but the last
-  bool moved_ahead = false;      // the coming step's age + movement are done, cell32 written
-  hipEvent_t ev_move = nullptr;
-  hipStream_t stream4 = nullptr; // ... on a stream of its own
   bool move_writes_keys = false;     // set around the movement of gnx_step           // k_move has written this step's sort keys
   int n_bin_blocks = 0;
   double* nodes = nullptr;           // [Jy][Jx] scratch node values
@@ -716,9 +720,8 @@ int gnx_l_gather_e(gnx_state* h, int64_t first, int64_t n);
 int gnx_l_age(gnx_state* h);
 int gnx_l_move(gnx_state* h, bool inc_age, const float* inj_theta, const float* inj_dist,
                float* out_theta, float* out_dist, bool apply);
-int gnx_l_move_ahead(gnx_state* h, int64_t N_all, const int32_t* d_alive, hipStream_t st);
 int gnx_l_sort_by_cell(gnx_state* h, bool split_rest = false);
-int gnx_wait_permute_rest(gnx_state* h, bool late_ok = false);
+int gnx_wait_permute_rest(gnx_state* h);
 int gnx_permute_rest_launch(gnx_state* h);
 // with_density: the n_pairs density (ops/demography.py:60-91) is launched before the host
 // has read the pair count back, so the GPU works through the round trip
@@ -728,7 +731,6 @@ int gnx_l_find_pairs(gnx_state* h, const uint8_t* d_keep, int64_t* n_pairs_out,
 int gnx_l_find_pairs_enqueue(gnx_state* h, const uint8_t* d_keep, bool with_density);
 int gnx_l_find_pairs_finish(gnx_state* h, int64_t* n_pairs_out);
 int gnx_l_births(gnx_state* h, int64_t* births_out);
-int gnx_l_offspring_ahead(gnx_state* h, bool burn, bool inside_enqueue = false);
 int gnx_l_pair_cls(gnx_state* h, int64_t P, bool local);
 int gnx_vt_buffers(gnx_state* h);      // (allocated by gnx_set_id_order: never inside a stream capture)
 int gnx_l_mate(gnx_state* h, bool burn, bool inject, int64_t B_inject, int64_t* births_out,
@@ -752,9 +754,10 @@ int gnx_xo_join(gnx_state* h);
 // only the first half: offspring still waiting for their crossover get it now (their slots
 // are about to move); a crossover already in flight on stream2 is left alone
 int gnx_xo_flush_deferred(gnx_state* h);
-// launch the crossover whose jobs are ready (policy 1 / 2 hooks; no-op otherwise).  site
-// (gnx_path_counts): GNX_PC_XO_P2 from launch policy 2's site, -1 from another policy's own
-// site, GNX_PC_XO_FLUSH (the default) from anybody else - a join, a genome access, a wait
+// launch the crossover whose jobs are ready (no-op otherwise).  site (gnx_path_counts):
+// GNX_PC_XO_P2 from launch policy 2's site (xo_launch_late: behind the next pair list), -1 right
+// behind the job builder, GNX_PC_XO_FLUSH (the default) from anybody else - a join, a genome
+// access, a wait
 int gnx_xo_launch_pending(gnx_state* h, int site = GNX_PC_XO_FLUSH);
 // `stream` waits for the crossover in flight (not for one that is not launched yet)
 int gnx_xo_wait_inflight(gnx_state* h);
@@ -826,8 +829,6 @@ int gnx_l_scatter_genomes(gnx_state* h, int64_t n, const uint64_t* d_in, int64_t
 int gnx_dd_l_sort(gnx_state* h, int32_t* d_bins, hipStream_t st);
 int gnx_dd_l_pairs(gnx_state* h, int32_t* d_bins, hipStream_t st);
 int gnx_dd_l_offspring(gnx_state* h, bool genomes, int32_t* d_bins, hipStream_t st);
-int gnx_dd_l_bins_adults(gnx_state* h, int par, hipStream_t st);
-int gnx_dd_l_density_pairs(gnx_state* h, hipStream_t st);
 int gnx_dd_l_density_N(gnx_state* h, int par, hipStream_t st);
 int gnx_dd_l_death_probs(gnx_state* h, bool with_selection, int par, hipStream_t st);
 int gnx_dd_l_alive(gnx_state* h, bool xo, int buf, hipStream_t st);
@@ -858,7 +859,7 @@ size_t gnx_os_scratch_bytes(size_t n, int end_bit);
 size_t gnx_os_words_used64(size_t n, int end_bit);
 int gnx_os_sort64_clean(void* scratch, void* tmp, const uint64_t* kin, uint64_t* kout,
                         const int32_t* vin, int32_t* vout, size_t n, int end_bit, hipStream_t s);
-size_t gnx_os_words_used(size_t n, int end_bit, int geometry = 0);
+size_t gnx_os_words_used(size_t n, int end_bit);
 int gnx_os_keys_hist(void* scratch, unsigned int* ticket, int64_t N, int64_t ord_n,
                      const int32_t* ord, const uint32_t* cell32, uint32_t* key, int32_t* val,
                      int end_bit, hipStream_t s, const GnxDD* dd = nullptr, int geometry = 0);
@@ -868,10 +869,7 @@ int gnx_os_sort32_gather(void* scratch, uint32_t* ktmp, int32_t* vtmp, uint32_t*
                          const uint32_t* cell32, hipStream_t s);
 int gnx_os_sort32_ranked(void* scratch, uint32_t* ktmp, int32_t* vtmp, const uint32_t* kin,
                          uint32_t* kout, const int32_t* vin, int32_t* vout, size_t n, int end_bit,
-                         hipStream_t s, int geometry = 0);
-int gnx_os_sort32(void* scratch, uint32_t* ktmp, int32_t* vtmp, const uint32_t* kin,
-                  uint32_t* kout, const int32_t* vin, int32_t* vout, size_t n, int end_bit,
-                  hipStream_t s, int variant);
+                         hipStream_t s);
 int gnx_prim_sort32_bits(void* tmp, size_t bytes, const uint32_t* kin, uint32_t* kout,
                          const int32_t* vin, int32_t* vout, size_t n, int end_bit,
                          hipStream_t s, bool alone);

@@ -381,8 +381,7 @@ static size_t gnx_nmax_lds_doubles(int Jx, int R) {
 }
 // GNX_NMAX_SCAN_ALL=1 (read per call; tests): every cell of every node interval is evaluated
 static int gnx_nmax_scan_min() {
-  const char* e = getenv("GNX_NMAX_SCAN_ALL");
-  return e && atoi(e) ? 0x7fffffff : GNX_NMAX_SCAN;
+  return gnx_env_int("GNX_NMAX_SCAN_ALL", 0) ? 0x7fffffff : GNX_NMAX_SCAN;
 }
 
 __device__ __forceinline__ int nmax_seg_of(int cx, double inv_hww, int Jx) {
@@ -724,22 +723,24 @@ static int launch_nmax(gnx_state* h) {
   if (!h->nmax_zeroed)
     HIPCHK(hipMemsetAsync(h->nmax_bits, 0, sizeof(unsigned long long), h->stream));
   h->nmax_zeroed = false;
-  static const int nmax_blocks = getenv("GNX_NMAX_BLOCKS") ? atoi(getenv("GNX_NMAX_BLOCKS")) : 512;
+  constexpr int GNX_NMAX_BLOCKS = 512;       // workgroups of k_nmax at most (one per raster row)
   const int R = gnx_nmax_rows_fit(h->lat.Jx, 0);
-  hipLaunchKernelGGL(k_nmax, dim3(std::min(h->cfg.H, nmax_blocks)), dim3(256),
+  hipLaunchKernelGGL(k_nmax, dim3(std::min(h->cfg.H, GNX_NMAX_BLOCKS)), dim3(256),
                      gnx_nmax_lds_doubles(h->lat.Jx, R) * sizeof(double), h->stream,
                      make_splinec(h, h->spl_N), h->cfg.W, h->cfg.H, h->nmax_bits, R, gnx_nmax_scan_min());
   h->nmax_cur = h->nmax_bits;
   return 0;
 }
 
+// workgroups of k_lattice_nmax's N.max() share at most (one per raster row)
+constexpr int GNX_LATN_BLOCKS = 256;
+
 // ---- the density path without a counting pass (gnx_bins.h, gnx_internal.h: fb) ----------
 bool gnx_fused_bins(const gnx_state* h) {
-  static const bool on = !(getenv("GNX_FUSED_BINS") && atoi(getenv("GNX_FUSED_BINS")) == 0);
   const int64_t nn = (int64_t)h->lat.Jx * h->lat.Jy;
   const size_t lds = ((size_t)4 * nn + std::max(h->lat.Jx, h->lat.Jy) + 1 +
                       gnx_nmax_lds_doubles(h->lat.Jx, 1)) * sizeof(double);
-  return on && !h->tiled && !h->tile2_mode && h->fb[0] != nullptr && h->stream3 != nullptr && lds <= 64 * 1024 &&
+  return !h->tiled && !h->tile2_mode && h->fb[0] != nullptr && h->stream3 != nullptr && lds <= 64 * 1024 &&
          (size_t)h->lat.nbx * h->lat.nby * sizeof(int32_t) <= 48 * 1024;
 }
 
@@ -856,9 +857,8 @@ int gnx_l_density_N(gnx_state* h) {
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_binsN, 0));
     h->binsN_inflight = false;
   }
-  static const int blocks_env = getenv("GNX_LATN_BLOCKS") ? atoi(getenv("GNX_LATN_BLOCKS")) : 256;
   gnx_time_begin(h);
-  hipLaunchKernelGGL(k_lattice_nmax, dim3(std::max(1, std::min(h->cfg.H, blocks_env))), dim3(256),
+  hipLaunchKernelGGL(k_lattice_nmax, dim3(std::max(1, std::min(h->cfg.H, GNX_LATN_BLOCKS))), dim3(256),
                      lds_bytes, h->stream, L.Jx, L.Jy, L.nbx, (const int32_t*)h->fb[cur], L.areas,
                      L.hww, L.cprime, h->spl_N.c, h->cfg.W, h->cfg.H, h->nmax2 + cur,
                      h->fb[cur ^ 1], h->nmax2 + (cur ^ 1), (int32_t*)nullptr, (double*)nullptr,
@@ -880,17 +880,15 @@ int gnx_l_density_N(gnx_state* h) {
 // counter words and checks published from it - three launches of one field each and a
 // publishing kernel otherwise.  false: the lattice is too fine for it, nothing was launched.
 bool gnx_l_lattices_tiled(gnx_state* h, bool have_pairs, const GnxPubWords& pub) {
-  static const bool on = !(getenv("GNX_TILE_LATN") && atoi(getenv("GNX_TILE_LATN")) == 0);
   const GnxLattice& L = h->lat;
   const int64_t nn = (int64_t)L.Jx * L.Jy;
   const size_t lat_doubles = (size_t)4 * nn + std::max(L.Jx, L.Jy) + 1;
   const int nmax_R = gnx_nmax_rows_fit(L.Jx, lat_doubles);
   const size_t lds_bytes = (lat_doubles + gnx_nmax_lds_doubles(L.Jx, nmax_R)) * sizeof(double);
-  if (!on || lds_bytes > 64 * 1024 || !h->nmax_bits || !h->nmax_zeroed) return false;
-  static const int blocks_env = getenv("GNX_LATN_BLOCKS") ? atoi(getenv("GNX_LATN_BLOCKS")) : 256;
+  if (lds_bytes > 64 * 1024 || !h->nmax_bits || !h->nmax_zeroed) return false;
   gnx_time_begin(h);
   hipLaunchKernelGGL(k_lattice_nmax,
-                     dim3(std::max(1, std::min(h->cfg.H, blocks_env)) + (have_pairs ? 1 : 0)),
+                     dim3(std::max(1, std::min(h->cfg.H, GNX_LATN_BLOCKS)) + (have_pairs ? 1 : 0)),
                      dim3(256), lds_bytes, h->stream, L.Jx, L.Jy, L.nbx,
                      (const int32_t*)h->bin_partials, L.areas, L.hww, L.cprime, h->spl_N.c, h->cfg.W,
                      h->cfg.H, h->nmax_bits, (int32_t*)nullptr, (unsigned long long*)nullptr,
@@ -1154,337 +1152,29 @@ k_xo_jobs_write(int64_t B, GnxHalves H, const GnxXoPlan* __restrict__ plan,
   }
 }
 
-// The two kernels above in one (NB <= 16): one thread per offspring SLOT (256 per
-// workgroup - four times the workgroups of k_xo_jobs_surv, which left a third of the CUs
-// idle), the plan stays in registers, and the thread walks its own 2 x NB table entries
-// with every load of a stage issued before the first result is used: the parent's 2 x NB
-// entries are NB 8-byte loads, the child's NB 8-byte stores.  One thread per logical block
-// (k_xo_jobs_write: 3.3 M threads, each a chain of three dependent loads) took 52 us,
-// k_xo_jobs_surv 23.
+// The most blocks per homologue the one-kernel builder below (k_xo_jobs_lanes) takes; longer
+// tables go through the two kernels above.
 #define GNX_JF_NB 28
-__device__ __forceinline__ int32_t gnx_fresh_at(int fr, int32_t f0, int32_t f1, int32_t f2, int32_t f3,
-                                                int32_t f4, int32_t f5,
-                                                const int32_t* __restrict__ stack, int pop) {
-  int32_t d = f0;
-  d = fr == 1 ? f1 : d;
-  d = fr == 2 ? f2 : d;
-  d = fr == 3 ? f3 : d;
-  d = fr == 4 ? f4 : d;
-  d = fr == 5 ? f5 : d;
-  if (fr >= 6) d = stack[pop - fr];
-  return d;
-}
 // threads per workgroup: every workgroup takes its stretch of the free-block stack and of the
 // job list with one atomic each, all on the same two words - 815 workgroups of 256 threads
 // queue up there (64 us; 512 threads: 58 us; 1024 threads spill: 64 us)
 #ifndef GNX_JF_TPB
 #define GNX_JF_TPB 512
 #endif
-template <int NB, int TPB>
-__global__ void __launch_bounds__(TPB)
-k_xo_jobs_fused(int64_t N, int64_t first, int32_t* __restrict__ grow,
-                const int32_t* __restrict__ alive, const int32_t* __restrict__ blk_off3,
-                const int32_t* __restrict__ off_parent, const int32_t* __restrict__ off_keys,
-                const uint8_t* __restrict__ off_start, const int32_t* __restrict__ free_rows,
-                int64_t n_free, GnxHalves H, const int32_t* __restrict__ bp_off,
-                const int32_t* __restrict__ bp_loci, int32_t* __restrict__ n_jobs,
-                GnxXoJob* __restrict__ jobs, GnxJobBp* __restrict__ jobs_bp,
-                const int32_t* __restrict__ cnt3, GnxDD* __restrict__ dd) {
-  constexpr int WAVES = TPB / 64;
-  if (dd) {
-    N = (int64_t)dd->N + dd->B;
-    first = dd->N;
-    n_free = dd->n_free;
-    if ((first / TPB + blockIdx.x) * TPB >= N) return;         // (block-uniform)
-  }
-  __shared__ int wsum[3][WAVES];
-  __shared__ int prev_s[WAVES];
-  __shared__ int psum[WAVES];
-  __shared__ int s_pop, s_job;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t base = (first / TPB + blockIdx.x) * TPB;
-  const int64_t i = base + tid;
-  const int64_t b = base / GNX_CB;                 // the compaction block of these TPB slots
-  const int round = (int)((base - b * GNX_CB) / TPB);
-  // stage 1: who is a surviving offspring without a row, here and in the earlier rounds of
-  // the same compaction block (their number comes before this round's ranks)
-  const bool fx = i < N && (alive[i] & 2) != 0;
-  int prev = 0;
-  for (int r = 0; r < round; ++r) {
-    const int64_t j = b * GNX_CB + r * TPB + tid;
-    prev += __popcll(__ballot(j < N && (alive[j] & 2) != 0));
-  }
-  // cnt3 != null: the block counts have not been scanned (the scan runs on the side stream,
-  // for the compaction and the host) - this workgroup adds up the counts before its
-  // compaction block itself: a few coalesced loads, and one launch less on the step's chain
-  int part = 0;
-  if (cnt3)
-    for (int q = tid; q < (int)b; q += TPB) part += cnt3[q];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d);
-  const unsigned long long bal = __ballot(fx);
-  if (lane == 0) {
-    wsum[0][wave] = __popcll(bal);
-    prev_s[wave] = prev;
-    psum[wave] = part;
-  }
-  __syncthreads();
-  int rank = __popcll(bal & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) rank += wsum[0][w];
-  if (cnt3) {
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) rank += psum[w];
-  } else {
-    rank += blk_off3[b];
-  }
-#pragma unroll
-  for (int w = 0; w < WAVES; ++w) rank += prev_s[w];
-  // (device-driven step: nobody checked the rows on the host - running out of them is
-  // reported, the indices stay inside the stacks, the run is invalid and ends with an error)
-  if (dd && fx && rank >= n_free) {
-    dd->err |= GNX_DD_ERR_ROWS;
-    rank = 0;
-  }
-  // stage 2: row, parents, keys, start homologues (unconditional loads from clamped indices)
-  const int64_t k = fx ? i - first : 0;
-  int32_t row = free_rows[max((int64_t)0, n_free - 1 - (fx ? rank : 0))];
-  int32_t par[2], key[2], st[2];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    par[p] = off_parent[2 * k + p];
-    key[p] = off_keys[2 * k + p];
-    st[p] = off_start[2 * k + p];
-  }
-  if (fx) grow[i] = row;
-  else row = -1;
-  // stage 3: the parents' rows, the paths' breakpoint ranges
-  int32_t prow[2], b0[2], b1[2];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    prow[p] = grow[par[p]];
-    b0[p] = bp_off ? bp_off[key[p]] : 0;
-    b1[p] = bp_off ? bp_off[key[p] + 1] : 0;
-  }
-  // stage 4: which blocks hold a switch point.  The first four switch points of each path are
-  // loaded once into registers (stage 7 looks them up again, block by block), and the block of
-  // a locus comes from a float reciprocal with an exact correction (loci < 2^24) instead of an
-  // integer division
-  const unsigned int all = (1u << NB) - 1u;
-  const int lpb = H.BW * 64;
-  const float inv_lpb = 1.0f / (float)lpb;
-  auto blk_of = [&](int l) __attribute__((always_inline)) {
-    int q = (int)((float)l * inv_lpb);
-    q -= (q * lpb > l) ? 1 : 0;
-    q += ((q + 1) * lpb <= l) ? 1 : 0;
-    return min(q, NB - 1);
-  };
-  unsigned int mixed[2], sel[2];
-  int32_t bl[2][4];
-  int nbp[2];
-  int cf = 0, cj = 0;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    if (!fx) prow[p] = -1;
-    nbp[p] = (bp_off && prow[p] >= 0) ? b1[p] - b0[p] : 0;
-#pragma unroll
-    for (int z = 0; z < 4; ++z) bl[p][z] = z < nbp[p] ? bp_loci[b0[p] + z] : 0;
-  }
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    mixed[p] = all;                              // dense masks, ghost parent: cut everything
-    sel[p] = 0u;
-    if (fx && prow[p] >= 0 && bp_off) {
-      unsigned int mx = 0u, sl = st[p] ? all : 0u;
-#pragma unroll
-      for (int z = 0; z < 4; ++z)
-        if (z < nbp[p]) {
-          const int blk = blk_of(bl[p][z]);
-          mx |= 1u << blk;
-          sl ^= all & ~((2u << blk) - 1u);        // every later block starts on the other homologue
-        }
-      for (int z = 4; z < nbp[p]; ++z) {
-        const int blk = blk_of(bp_loci[b0[p] + z]);
-        mx |= 1u << blk;
-        sl ^= all & ~((2u << blk) - 1u);
-      }
-      mixed[p] = mx;
-      sel[p] = sl & all;
-    }
-    if (fx) {
-      const int nf = __popc(mixed[p]);
-      cf += nf;
-      cj += prow[p] >= 0 ? nf : 0;
-    }
-  }
-  // stage 5: this workgroup's stretch of the free-block stack and of the job list, with
-  // ONE atomic each; exclusive sums of cf / cj over the TPB threads
-  int xf = cf, xj = cj;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int yf = __shfl_up(xf, d), yj = __shfl_up(xj, d);
-    if (lane >= d) {
-      xf += yf;
-      xj += yj;
-    }
-  }
-  if (lane == 63) {
-    wsum[1][wave] = xf;
-    wsum[2][wave] = xj;
-  }
-  __syncthreads();
-  int of = xf - cf, oj = xj - cj;
-  for (int w = 0; w < wave; ++w) {
-    of += wsum[1][w];
-    oj += wsum[2][w];
-  }
-  if (tid == 0) {
-    int tf = 0, tj = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-      tf += wsum[1][w];
-      tj += wsum[2][w];
-    }
-    // (without these two contended words - a timing experiment with wrong results - the kernel
-    // takes the same time: profiles/r05_ab_runs.txt)
-    s_pop = tf ? atomicSub(H.top, tf) : 0;
-    s_job = tj ? atomicAdd(n_jobs, tj) : 0;
-  }
-  __syncthreads();
-  if (dd && tid == 0) {
-    int tf = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) tf += wsum[1][w];
-    if (s_pop < tf) dd->err |= GNX_DD_ERR_BLOCKS;
-  }
-  if (!fx) return;
-  // stack index of my first fresh block (dd: never below what this thread walks down)
-  const int pop = dd ? max(s_pop - 1 - of, cf) : s_pop - 1 - of;
-  const int job = s_job + oj;
-  // stage 6: the parents' table entries (2 x NB each, 8-byte loads) and my first six fresh
-  // blocks, all issued before anything is used.  (All 2 NB fresh blocks in registers cost a
-  // (2 NB)^2 select chain - PMC: 4 300 vector instructions per wave at NB = 14; one load per
-  // block inside stage 7 put a memory round trip into each of its 2 NB iterations.)
-  int32_t pe[2][2 * NB];                           // [parent][hom * NB + q]
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int2* src = (const int2*)(H.hmap + (int64_t)max(prow[p], 0) * 2 * NB);
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const int2 v = src[q];
-      pe[p][2 * q] = v.x;
-      pe[p][2 * q + 1] = v.y;
-    }
-  }
-  // (six scalars, not an array: the compiler turns a select chain over an array captured by
-  // reference into an indexed load from scratch)
-  const int32_t f0 = 0 < cf ? H.stack[pop] : 0, f1 = 1 < cf ? H.stack[pop - 1] : 0,
-                f2 = 2 < cf ? H.stack[pop - 2] : 0, f3 = 3 < cf ? H.stack[pop - 3] : 0,
-                f4 = 4 < cf ? H.stack[pop - 4] : 0, f5 = 5 < cf ? H.stack[pop - 5] : 0;
-  const int32_t* stack = H.stack;
-  // (a function of scalars, not a closure: with more than 20 blocks per homologue the closure
-  // object stayed in scratch and the compiler chose between its address and the stack's)
-#define fresh_at(fr_) gnx_fresh_at((fr_), f0, f1, f2, f3, f4, f5, stack, pop)
-  // stage 7a: my table (NB 8-byte stores); the parents' blocks that are shared from now on
-  // lose their never-shared flag (only the first child to share one writes).  Branch-free but
-  // for the stores: every wave has some lane on either side of every block.
-  int32_t ce[2 * NB];
-  int fr = 0;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const bool cut = ((mixed[p] >> q) & 1u) != 0u;
-      const int hsel = (sel[p] >> q) & 1u;
-      const int32_t pv = hsel ? pe[p][NB + q] : pe[p][q];
-      const int32_t sv = GNX_BLK(pv);
-      if (fx && !cut && pv < 0) H.hmap[((int64_t)prow[p] * 2 + hsel) * NB + q] = sv;
-      const int32_t fv = (int32_t)((uint32_t)fresh_at(cut ? fr : 0) | GNX_OWN);
-      ce[p * NB + q] = cut ? fv : sv;
-      fr += cut ? 1 : 0;
-    }
-  }
-  {
-    int2* dstp = (int2*)(H.hmap + (int64_t)row * 2 * NB);
-#pragma unroll
-    for (int q = 0; q < NB; ++q) dstp[q] = make_int2(ce[2 * q], ce[2 * q + 1]);
-  }
-  // stage 7b: one job per cut block of a local parent, walking the set bits (about two per
-  // homologue) rather than all 2 NB blocks; the switch points inside the block ride with the
-  // job (gnx_xo.h: GnxJobBp), taken from the registers of stage 4
-  int jr = 0;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    if (prow[p] < 0) continue;
-    const int fbase = p ? __popc(mixed[0]) : 0;
-    unsigned int m = mixed[p];
-    while (m) {
-      const int q = __ffs(m) - 1;
-      m &= m - 1u;
-      const int32_t dst = fresh_at(fbase + __popc(mixed[p] & ((1u << q) - 1u)));
-      int32_t e0 = pe[p][0], e1 = pe[p][NB];
-      if constexpr (NB <= 16) {
-#pragma unroll
-        for (int q2 = 1; q2 < NB; ++q2) {
-          e0 = q == q2 ? pe[p][q2] : e0;
-          e1 = q == q2 ? pe[p][NB + q2] : e1;
-        }
-      } else {
-        // (more blocks: the select chain over the registers outgrows the unroller and the table
-        // in registers would move to scratch - the two entries are read again, from L2)
-        const int32_t* prw = H.hmap + (int64_t)prow[p] * 2 * NB;
-        e0 = prw[q];
-        e1 = prw[NB + q];
-      }
-      GnxXoJob j;
-      j.ph0 = GNX_BLK(e0);
-      j.ph1 = GNX_BLK(e1);
-      j.dst = dst;
-      j.ks = (key[p] * 2 + st[p]) | (q << 24);
-      jobs[job + jr] = j;
-      unsigned int o0 = 0, o1 = 0, o2 = 0;
-      int nin = 0;
-      const int lo = q * lpb, hi = (q == NB - 1) ? 0x7fffffff : lo + lpb;
-      auto take = [&](int l) __attribute__((always_inline)) {
-        if (l >= lo && l < hi) {
-          const unsigned int o = (unsigned int)(l - lo);
-          o0 = nin == 0 ? o : o0;
-          o1 = nin == 1 ? o : o1;
-          o2 = nin == 2 ? o : o2;
-          ++nin;
-        }
-      };
-#pragma unroll
-      for (int z = 0; z < 4; ++z)
-        if (z < nbp[p]) take(bl[p][z]);
-      for (int z = 4; z < nbp[p]; ++z) take(bp_loci[b0[p] + z]);
-      // (offsets are 16 bits: a block of more than 65 536 loci looks its path up)
-      const bool inl = bp_off != nullptr && nin <= 3 && lpb <= 65536;
-      const unsigned int meta = (inl ? (unsigned int)nin : 0u) | (((sel[p] >> q) & 1u) << 2) |
-                                (inl ? 0u : GNX_BP_MORE);
-      *(uint2*)(jobs_bp + job + jr) = make_uint2((o0 & 0xffffu) | (o1 << 16),
-                                                 (o2 & 0xffffu) | (meta << 16));
-      ++jr;
-    }
-  }
-}
-
-#undef fresh_at
 
 // ---- the job builder with a gamete's table laid across lanes (round 6) ------------------------
-// k_xo_jobs_fused above gives every surviving offspring ONE thread that walks 2 x 2 NB parent
-// entries and NB child entries by itself: 60 loads and stores of 8 bytes per thread at NB = 20,
-// every one of them a request of its own (the lanes of a wave sit in 64 different rows) - ~3 200
-// requests per wave for 30 KB, 49 % of the waves' cycles waiting for them (SQ counters,
-// profiles/r05_pmc_job_builder.txt).  Here the per-offspring PLAN (row, parents' rows, which
-// blocks are cut, which homologue the others follow, where its fresh blocks and jobs start) is
-// worked out one thread per slot as before (stages 1-5, same arithmetic), left in LDS (64 bytes
-// per slot), and the TABLES are then walked by the wave together: a gamete's NB entries lie in NB
-// adjacent lanes - lane q loads the parent's two entries for block q (two coalesced 4 NB-byte
-// rows per gamete), picks or takes a fresh block, stores the child's entry (one coalesced row) and
-// writes the job of a cut block; 64 / NB gametes per wave-instruction, four instructions' loads
-// in flight before the first store.  NB is a run-time value here: one kernel for every genome
-// length.  Same plan, same stack / job indices as k_xo_jobs_fused: bit-identical tables and job
-// lists (tests/test_gpu_product_path.py, test_gpu_halves.py, test_gpu_deferred.py).
+// One thread per surviving offspring that walks 2 x 2 NB parent entries and NB child entries by
+// itself (measured and removed: 60 loads and stores of 8 bytes per thread at NB = 20, every one a
+// request of its own, 49 % of the waves' cycles waiting for them - profiles/r05_pmc_job_builder.txt,
+// r06_pmc_job_builder.txt).  Here the per-offspring PLAN (row, parents' rows, which blocks are cut,
+// which homologue the others follow, where its fresh blocks and jobs start) is worked out one
+// thread per slot (stages 1-5), left in LDS (64 bytes per slot), and the TABLES are then walked by
+// the wave together: a gamete's NB entries lie in NB adjacent lanes - lane q loads the parent's two
+// entries for block q (two coalesced 4 NB-byte rows per gamete), picks or takes a fresh block,
+// stores the child's entry (one coalesced row) and writes the job of a cut block; 64 / NB gametes
+// per wave-instruction, four instructions' loads in flight before the first store.  NB is a
+// run-time value: one kernel for every genome length.  Tables and job lists are pinned by
+// tests/test_gpu_product_path.py, test_gpu_halves.py, test_gpu_deferred.py.
 struct alignas(16) GnxJobPlan {
   int32_t row, pop, job, m0cnt;      // m0cnt: cut blocks of gamete 0
   int32_t prow[2];
@@ -1541,7 +1231,7 @@ k_xo_jobs_lanes(int64_t N, int64_t first, int32_t* __restrict__ grow,
   const int64_t i = base + tid;
   const int64_t b = base / GNX_CB;                 // the compaction block of these TPB slots
   const int round = (int)((base - b * GNX_CB) / TPB);
-  // stages 1-5: as in k_xo_jobs_fused
+  // stages 1-5: the plan, one thread per slot
   const bool fx = i < N && (alive[i] & 2) != 0;
   int prev = 0;
   for (int r = 0; r < round; ++r) {
@@ -1803,47 +1493,31 @@ k_xo_jobs_lanes(int64_t N, int64_t first, int32_t* __restrict__ grow,
 #endif
 }
 
-template <int NB>
 static void launch_jobs_fused(gnx_state* h, int64_t first_slot, const int32_t* d_alive,
                               const int32_t* d_blk_off, int buf) {
   const int64_t N = h->N;
   // (device-driven step: first slot and N come from the device, the grid covers what a step's
   // births can take - half the capacity - and the workgroups behind them leave at once)
   const bool ddm = h->dd_active;
-  // GNX_JF_LANES=0: one thread per offspring walks its tables alone (k_xo_jobs_fused)
-  static const bool lanes = !(getenv("GNX_JF_LANES") && atoi(getenv("GNX_JF_LANES")) == 0);
-  if (lanes) {
-    // small populations (the device-driven step's sizes): 256-thread workgroups - at 10^5 individuals
-    // 26 000 births are 51 workgroups of 512 on 256 CUs (C3 steady 0.2023 against 0.2054 ms/step)
-    const bool small = h->cfg.cap_inds <= 600000 && GNX_JF_TPB > 256;      // (GNX_DD_MAX_CAP's default)
-    const int tpb = small ? 256 : GNX_JF_TPB;
-    const int nbl = ddm ? (int)(h->cfg.cap_inds / 2 / tpb + 2)
-                        : (int)((N - 1) / tpb - first_slot / tpb + 1);
+  // small populations (the device-driven step's sizes): 256-thread workgroups - at 10^5 individuals
+  // 26 000 births are 51 workgroups of 512 on 256 CUs (C3 steady 0.2023 against 0.2054 ms/step)
+  const bool small = h->cfg.cap_inds <= 600000 && GNX_JF_TPB > 256;      // (GNX_DD_MAX_CAP's default)
+  const int tpb = small ? 256 : GNX_JF_TPB;
+  const int nbl = ddm ? (int)(h->cfg.cap_inds / 2 / tpb + 2)
+                      : (int)((N - 1) / tpb - first_slot / tpb + 1);
 #define GNX_JL_LAUNCH(TPB_)                                                                         \
-    hipLaunchKernelGGL((k_xo_jobs_lanes<TPB_>), dim3(nbl), dim3(TPB_), 0, h->stream, N, first_slot,  \
-                       h->soa[h->cur].grow, d_alive, d_blk_off + 2 * h->blk_stride, h->off_parent,  \
-                       h->off_keys, h->off_start, h->free_rows, h->n_free, gnx_halves(h),           \
-                       gnx_alias_bp(h), gnx_alias_loci(h), h->n_jobs_dev[buf],                      \
-                       (GnxXoJob*)h->jobs[buf], (GnxJobBp*)h->jobs_bp[buf],                         \
-                       h->jobs_self_scan ? (const int32_t*)(h->blk_cnt + 2 * h->blk_stride)         \
-                                         : (const int32_t*)nullptr, ddm ? h->dd : (GnxDD*)nullptr)
-    if (small) GNX_JL_LAUNCH(256);
-    else GNX_JL_LAUNCH(GNX_JF_TPB);
+  hipLaunchKernelGGL((k_xo_jobs_lanes<TPB_>), dim3(nbl), dim3(TPB_), 0, h->stream, N, first_slot,  \
+                     h->soa[h->cur].grow, d_alive, d_blk_off + 2 * h->blk_stride, h->off_parent,  \
+                     h->off_keys, h->off_start, h->free_rows, h->n_free, gnx_halves(h),           \
+                     gnx_alias_bp(h), gnx_alias_loci(h), h->n_jobs_dev[buf],                      \
+                     (GnxXoJob*)h->jobs[buf], (GnxJobBp*)h->jobs_bp[buf],                         \
+                     h->jobs_self_scan ? (const int32_t*)(h->blk_cnt + 2 * h->blk_stride)         \
+                                       : (const int32_t*)nullptr, ddm ? h->dd : (GnxDD*)nullptr)
+  if (small) GNX_JL_LAUNCH(256);
+  else GNX_JL_LAUNCH(GNX_JF_TPB);
 #undef GNX_JL_LAUNCH
-    // (gnx_path_counts; a device-driven step is launched once into its graph: not counted)
-    if (!ddm && (tpb == 256 || tpb == 512)) ++h->pc[tpb == 256 ? GNX_PC_JOBS_256 : GNX_PC_JOBS_512];
-    h->jobs_inline[buf] = true;
-    return;
-  }
-  const int nbf = ddm ? (int)(h->cfg.cap_inds / 2 / GNX_JF_TPB + 2)
-                      : (int)((N - 1) / GNX_JF_TPB - first_slot / GNX_JF_TPB + 1);
-  hipLaunchKernelGGL((k_xo_jobs_fused<NB, GNX_JF_TPB>), dim3(nbf), dim3(GNX_JF_TPB), 0, h->stream, N, first_slot,
-                     h->soa[h->cur].grow, d_alive, d_blk_off + 2 * h->blk_stride, h->off_parent,
-                     h->off_keys, h->off_start, h->free_rows, h->n_free, gnx_halves(h),
-                     gnx_alias_bp(h), gnx_alias_loci(h), h->n_jobs_dev[buf],
-                     (GnxXoJob*)h->jobs[buf], (GnxJobBp*)h->jobs_bp[buf],
-                     h->jobs_self_scan ? (const int32_t*)(h->blk_cnt + 2 * h->blk_stride)
-                                       : (const int32_t*)nullptr, ddm ? h->dd : (GnxDD*)nullptr);
+  // (gnx_path_counts; a device-driven step is launched once into its graph: not counted)
+  if (!ddm && (tpb == 256 || tpb == 512)) ++h->pc[tpb == 256 ? GNX_PC_JOBS_256 : GNX_PC_JOBS_512];
   h->jobs_inline[buf] = true;
 }
 
@@ -2005,7 +1679,7 @@ k_fill(int64_t cap, const int32_t* __restrict__ n_move, const int32_t* __restric
        const int32_t* __restrict__ movers, const int32_t* __restrict__ cnts, GnxSoA a, int n_layers,
        int n_traits, int tbw, const int32_t* __restrict__ rows_tmp, int32_t* __restrict__ free_rows,
        int64_t n_free, int has_rows, int xo, int32_t* __restrict__ newslot,
-       const GnxDD* __restrict__ dd, uint32_t* __restrict__ cell32) {
+       const GnxDD* __restrict__ dd) {
   if (dd) n_free = dd->n_free;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2014,8 +1688,6 @@ k_fill(int64_t cap, const int32_t* __restrict__ n_move, const int32_t* __restric
     const int64_t i = movers[r], k = holes[r];
     GnxRec rec = gnx_rec_load(a, i, cap, n_layers, n_traits, tbw);
     rec.ghost = 0;
-    // (the next step's movement has run already - gnx_l_move_ahead: its sort key moves too)
-    if (cell32) cell32[k] = cell32[i];
     if (newslot) newslot[i] = (int32_t)k;
     gnx_rec_store(a, k, cap, n_layers, n_traits, tbw, rec);
     gnx_rec_rest(a, i, a, k, cap, n_layers, n_traits, tbw);
@@ -2028,47 +1700,17 @@ k_fill(int64_t cap, const int32_t* __restrict__ n_move, const int32_t* __restric
   }
 }
 
-static bool jobs_fused_ok(const gnx_state* h) {
-  static const bool fused_env = !(getenv("GNX_JOBS_FUSED") && atoi(getenv("GNX_JOBS_FUSED")) == 0);
-  // (the two-kernel builder's plan packs the block masks into 16 bits each)
-  return (fused_env || h->NB > 16) && h->NB <= GNX_JF_NB;
-}
+// GNX_JF_NB equals GNX_MAX_NB (gnx_half.h), which gnx_create clamps NB to: true for every layout the
+// library builds today.  The two-kernel builder below (its plan packs the block masks into 16
+// bits each: NB <= 16) and the scan on the main stream are what a layout beyond GNX_JF_NB would take.
+static bool jobs_fused_ok(const gnx_state* h) { return h->NB <= GNX_JF_NB; }
 
 void gnx_launch_xo_jobs_surv(gnx_state* h, int64_t first_slot, const int32_t* d_alive,
                              const int32_t* d_blk_off, int buf) {
   const int64_t N = h->N;
   const int nbj = (int)((N - 1) / GNX_CB - first_slot / GNX_CB + 1);
   if (jobs_fused_ok(h)) {
-    switch (h->NB) {
-      case 1: launch_jobs_fused<1>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 2: launch_jobs_fused<2>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 3: launch_jobs_fused<3>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 4: launch_jobs_fused<4>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 5: launch_jobs_fused<5>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 6: launch_jobs_fused<6>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 7: launch_jobs_fused<7>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 8: launch_jobs_fused<8>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 9: launch_jobs_fused<9>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 10: launch_jobs_fused<10>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 11: launch_jobs_fused<11>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 12: launch_jobs_fused<12>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 13: launch_jobs_fused<13>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 14: launch_jobs_fused<14>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 15: launch_jobs_fused<15>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 16: launch_jobs_fused<16>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 17: launch_jobs_fused<17>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 20: launch_jobs_fused<20>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 18: launch_jobs_fused<18>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 19: launch_jobs_fused<19>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 21: launch_jobs_fused<21>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 22: launch_jobs_fused<22>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 23: launch_jobs_fused<23>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 24: launch_jobs_fused<24>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 25: launch_jobs_fused<25>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 26: launch_jobs_fused<26>(h, first_slot, d_alive, d_blk_off, buf); break;
-      case 27: launch_jobs_fused<27>(h, first_slot, d_alive, d_blk_off, buf); break;
-      default: launch_jobs_fused<28>(h, first_slot, d_alive, d_blk_off, buf); break;
-    }
+    launch_jobs_fused(h, first_slot, d_alive, d_blk_off, buf);
     return;
   }
   h->jobs_inline[buf] = false;
@@ -2217,92 +1859,6 @@ k_dead_rows(int64_t N, const int32_t* __restrict__ dead_row, const int32_t* __re
   }
 }
 
-// k_ord_flags + k_ord_write in ONE launch: the stable compaction of the id-ordered index with a
-// decoupled look-back over the workgroups' counts (one status | count word per workgroup, 64
-// predecessors per round trip: the lanes of wave 0 read them together) instead of a counting
-// kernel, a scan by its last workgroup and a writing kernel - one gather of the flags through
-// the index instead of two.  Tickets give the workgroups their order; the last one to finish
-// clears the words for the next launch.  state: [nb] zero on entry, tick: [2] zero on entry.
-__global__ void __launch_bounds__(256)
-k_ord_compact(int64_t N, int64_t ord_n, const int32_t* __restrict__ ord,
-              const int32_t* __restrict__ newslot, const int32_t* __restrict__ alive,
-              int32_t* __restrict__ ord_new, uint32_t* __restrict__ state,
-              uint32_t* __restrict__ tick) {
-  constexpr uint32_t PART = 1u << 30, INCL = 2u << 30, VAL = (1u << 30) - 1u;
-  __shared__ int lds[16];
-  __shared__ uint32_t s_bid, s_off, s_last;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_bid = __hip_atomic_fetch_add(&tick[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  const uint32_t bid = s_bid;
-  const int64_t base = (int64_t)bid * GNX_CB;
-  bool f[4];
-  int32_t ns[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int64_t k = base + r * 256 + tid;
-    const int32_t slot = k < N ? (int32_t)(k < ord_n ? ord[k] : k) : -1;
-    if (alive) ns[r] = (slot >= 0 && (alive[slot] & 1) != 0) ? slot : -1;
-    else ns[r] = slot >= 0 ? newslot[slot] : -1;
-    f[r] = ns[r] >= 0;
-  }
-  int rank[4], tot;
-  gnx_block_ranks(f, rank, tot, lds);
-  if (wave == 0) {
-    if (lane == 0)
-      __hip_atomic_store(&state[bid], (bid == 0 ? INCL : PART) | (uint32_t)tot, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t prefix = 0;
-    int b = (int)bid - 1;
-    while (b >= 0) {
-      const int idx = b - lane;
-      const uint32_t v = idx >= 0 ? __hip_atomic_load(&state[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                  : INCL;
-      const unsigned long long notready = __ballot(v == 0u);
-      const unsigned long long incl = __ballot(v != 0u && (v & INCL) != 0u);
-      const int first_nr = notready ? __ffsll((long long)notready) - 1 : 64;
-      const int first_in = incl ? __ffsll((long long)incl) - 1 : 64;
-      if (first_nr == 0) {                     // the nearest predecessor has not published yet
-        __builtin_amdgcn_s_sleep(1);
-        continue;
-      }
-      const bool done = first_in < first_nr;
-      const int limit = done ? first_in : first_nr - 1;
-      uint32_t c = lane <= limit ? (v & VAL) : 0u;
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-      prefix += c;
-      if (done) break;
-      b -= limit + 1;
-    }
-    if (lane == 0) {
-      if (bid > 0)
-        __hip_atomic_store(&state[bid], INCL | (prefix + (uint32_t)tot), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      s_off = prefix;
-    }
-  }
-  __syncthreads();
-  const uint32_t o = s_off;
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    if (f[r]) ord_new[o + rank[r]] = ns[r];
-  // the last workgroup to get here (everybody has finished looking back by then) leaves the
-  // words zero for the next launch
-  if (tid == 0) {
-    const uint32_t d = __hip_atomic_fetch_add(&tick[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = d == gridDim.x - 1u ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  for (unsigned int q = tid; q < gridDim.x; q += 256)
-    __hip_atomic_store(&state[q], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (tid == 0) {
-    __hip_atomic_store(&tick[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&tick[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
 int gnx_l_mortality(gnx_state* h, const uint8_t* d_dead_inject, int64_t* deaths_out) {
   *deaths_out = 0;
   GNXCHK(gnx_l_mortality_enqueue(h, d_dead_inject));
@@ -2336,65 +1892,28 @@ int gnx_l_mortality_enqueue(gnx_state* h, const uint8_t* d_dead_inject) {
                      GnxScanOut{});
   // survivors, rows freed and (deferred crossover) the surviving offspring that need a
   // row: block offsets on the device, totals also straight into pinned host memory.
-  // (Measured and dropped: death probabilities + death draws + the scan by the last
-  // workgroup in ONE kernel took 73 us against 34 + 13 + 10 apart, 0.820 against 0.808
-  // ms/step - four individuals per thread starve the f64 spline gathers of parallelism;
-  // with one individual per thread of a 1024-thread workgroup and the scan left apart the
-  // step takes the same 0.766 ms either way: the launches are not what the chain costs.)
-  // in-place compaction (k_fill_lists above): its lists are made on stream3 while this stream
-  // builds the crossover's jobs
-  // (a caller that names the dead by position - gnx_op_mortality - gets the survivors back in
-  // their order: the stable compaction)
-  // (tiles too since round 4: the ghosts are dead to the compaction like anybody the draws took,
-  // and nothing on a tile depends on the survivors' order either - GNX_TILE_FILL=0: the stable
-  // copy there)
-  static const bool tile_fill = !(getenv("GNX_TILE_FILL") && atoi(getenv("GNX_TILE_FILL")) == 0);
-  const bool fill = h->compact_fill && (tile_fill || (!h->tiled && h->n_ghost == 0)) &&
-                    h->stream3 != nullptr && d_dead_inject == nullptr;
-  // ... and then the scan of the block counts moves there too: the job builder adds up the
-  // counts it needs itself (k_xo_jobs_fused: cnt3), the lists and the host get theirs from
+  // (death probabilities + death draws + scan in ONE kernel: measured and removed, 0.820 against
+  // 0.808 ms/step - profiles/HISTORY.md)
+  // fill: the in-place compaction (k_fill_lists above), its lists made on stream3 while this stream
+  // builds the crossover's jobs; tiles too (the ghosts are dead to it like anybody the draws took).
+  // A caller that names the dead by position - gnx_op_mortality - gets the survivors back in
+  // their order: the stable compaction (k_compact).
+  const bool fill = h->compact_fill && h->stream3 != nullptr && d_dead_inject == nullptr;
+  // side_scan: the scan of the block counts moves to stream3 too - the job builder adds up the
+  // counts it needs itself (k_xo_jobs_lanes: cnt3), the lists and the host get theirs from
   // stream3, and this stream goes from the death draws straight to the job builder
-  static const bool side_scan_env = !(getenv("GNX_SIDE_SCAN") && atoi(getenv("GNX_SIDE_SCAN")) == 0);
-  const bool side_scan = side_scan_env && fill && xo && xo_B > 0 && jobs_fused_ok(h);
-  // gnx_walk: the NEXT step's age + movement now, on the crossover's stream (idle until the jobs
-  // are built), beside the job builder - over slots still in this step's cell order, the dead
-  // skipped; the compaction below moves the moved records (gnx_l_move_ahead)
-  // (measured, profiles/r05_ab_runs.txt: 0.590 ms/step on the crossover's stream - the movement
-  // then holds the crossover back - and 0.70 on a stream of its own against 0.568 without: the
-  // movement is bound by its own arithmetic, ~1 200 vector instructions per individual, wherever
-  // it runs.  Off unless GNX_MOVE_AHEAD=1 / 2.)
-  static const bool ahead_env = getenv("GNX_MOVE_AHEAD") && atoi(getenv("GNX_MOVE_AHEAD")) != 0;
-  const bool ahead = ahead_env && h->eager_move && fill && ord_keep && h->sp.move && h->stream2 != nullptr &&
-                     h->key_bits <= 24 && h->n_ghost == 0 && !h->tile2_mode;
-  // gnx_walk, every step but the last: NO compaction (gnx_internal.h: holes) - GNX_LAZY_COMPACT=0: off
-  static const bool lazy_env = !(getenv("GNX_LAZY_COMPACT") && atoi(getenv("GNX_LAZY_COMPACT")) == 0);
-  // (tiles: inside gnx_tile_walk, without an index - gnx_internal.h)
-  // (measured with two tiles sharing one GPU, profiles/r06_ab_runs.txt: 1.64 ms/step with, 1.59-1.64
-  // without - what the compaction cost comes back as 20 % more slots for the movement, the two
-  // routing passes and the 64-bit sort to look at; parity-green, GNX_TILE_LAZY=1 turns it on)
-  const bool tile_lazy_env = getenv("GNX_TILE_LAZY") && atoi(getenv("GNX_TILE_LAZY")) != 0;   // (read per call: the tests switch it)
-  const bool lazy_tile = lazy_env && tile_lazy_env && h->tile_lazy_ok && h->tile2_mode &&
-                         h->tile_R * h->tile_C > 1 &&
-                         fill && !ord_keep &&
-                         h->sp.move && h->sp.mating_radius >= 0 && !ahead;
-  const bool lazy = lazy_tile ||
-                    (lazy_env && h->eager_move && !ahead && fill && ord_keep && h->sp.move &&
-                     h->sp.mating_radius >= 0 && h->key_bits <= 24 && h->n_ghost == 0 && !h->tile2_mode);
-  if (side_scan || ahead) HIPCHK(hipEventRecord(h->ev_alive, h->stream));
-  if (ahead) {
-    if (!h->ev_move)
-      HIPCHK(hipEventCreateWithFlags(&h->ev_move, hipEventDisableTiming | hipEventDisableSystemFence));
-    // (a stream of its own: on the crossover's it would hold the crossover back - the movement
-    // takes as long as the job builder it runs beside; GNX_MOVE_AHEAD=2: on the crossover's)
-    static const int ahead_mode = getenv("GNX_MOVE_AHEAD") ? atoi(getenv("GNX_MOVE_AHEAD")) : 1;
-    if (!h->stream4) HIPCHK(hipStreamCreateWithFlags(&h->stream4, hipStreamNonBlocking));
-    hipStream_t sm = ahead_mode == 2 ? h->stream2 : h->stream4;
-    HIPCHK(hipStreamWaitEvent(sm, h->ev_alive, 0));
-    GNXCHK(gnx_l_move_ahead(h, N, h->flag, sm));
-    HIPCHK(hipEventRecord(h->ev_move, sm));
-    h->moved_ahead = true;
-  }
+  const bool side_scan = fill && xo && xo_B > 0 && jobs_fused_ok(h);
+  // lazy: gnx_walk, every step but the last - NO compaction (gnx_internal.h: holes).  (The next
+  // step's movement beside the job builder instead: measured and removed, profiles/r05_ab_runs.txt)
+  // lazy_tile: the same inside gnx_tile_walk, without an index, when GNX_TILE_LAZY=1 asks for it
+  // (read per call: the tests switch it; 1.64 ms/step with, 1.59-1.64 without, profiles/r06_ab_runs.txt)
+  const bool lazy_common = fill && h->sp.move && h->sp.mating_radius >= 0;
+  const bool lazy_tile = lazy_common && gnx_env_int("GNX_TILE_LAZY", 0) != 0 && h->tile_lazy_ok &&
+                         h->tile2_mode && h->tile_R * h->tile_C > 1 && !ord_keep;
+  const bool lazy = lazy_tile || (lazy_common && h->eager_move && ord_keep && h->key_bits <= 24 &&
+                                  h->n_ghost == 0 && !h->tile2_mode);
   if (side_scan) {
+    HIPCHK(hipEventRecord(h->ev_alive, h->stream));
     HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_alive, 0));
     GNXCHK(gnx_block_scan(h, 3, N, h->blk_cnt, h->blk_off, h->cnt_dev, h->h_pin_dev, 0, h->stream3));
     gnx_time_end(h, GNX_K_COMPACT, 0.0);
@@ -2408,23 +1927,15 @@ int gnx_l_mortality_enqueue(gnx_state* h, const uint8_t* d_dead_inject) {
   }
   h->jobs_self_scan = side_scan;
   int has_rows = (h->genomes_assigned && c.L > 0) ? 1 : 0;
-  // GNX_ORD_FUSED=1: the index's flags and block offsets with the compaction's lists (they need
-  // the death draws, not the compaction) - what the device-driven step does; here it lengthens
-  // the lists the compaction and with it the next movement wait for: 0.587 against 0.582 ms/step
-  // (profiles/r04_ab_runs.txt), so k_ord_flags stays a launch of its own beside the crossover
-  static const bool ord_fused_env = getenv("GNX_ORD_FUSED") && atoi(getenv("GNX_ORD_FUSED")) != 0;
-  const bool ord_fused = ord_fused_env && fill && ord_keep && !lazy;
+  // (the index's flags with these lists, as the device-driven step does it: measured and removed
+  // here, 0.587 against 0.582 ms/step - profiles/r04_ab_runs.txt; k_ord_flags is a launch of its own)
   if (fill && !lazy) {
     if (!side_scan) HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_counts, 0));
     hipLaunchKernelGGL(k_fill_lists, dim3(nb), dim3(256), 0, h->stream3, N, h->flag, h->flag2,
                        h->blk_off, h->blk_stride, h->cnt_dev, a.grow, has_rows,
                        (int32_t*)h->os_ktmp, (int32_t*)h->os_ktmp + c.cap_inds / 2,
                        (int32_t*)h->os_vtmp, ord_keep ? h->newslot : nullptr, h->fill_cnt,
-                       (const GnxDD*)nullptr,
-                       ord_fused ? GnxOrdF{h->ord[h->ord_cur], nullptr, h->flag, h->ord_cnt,
-                                           GnxScanOut{h->ord_off, nullptr, nullptr, 0, nullptr,
-                                                      h->tickets + 2, h->blk_stride}, h->ord_n, 0}
-                                 : GnxOrdF{});
+                       (const GnxDD*)nullptr, GnxOrdF{});
     HIPCHK(hipEventRecord(h->ev_fill, h->stream3));
   }
   // deferred crossover of this step's births: rows and jobs for the survivors, the kernel
@@ -2457,48 +1968,36 @@ int gnx_l_mortality_enqueue(gnx_state* h, const uint8_t* d_dead_inject) {
     ++h->pc[GNX_PC_LAZY_MORT];
   } else if (fill) {
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_fill, 0));
-    if (ahead) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_move, 0));
     const int64_t guess = std::max<int64_t>(h->fill_guess * 2, 4096);      // (grid-stride: any count)
     const int fb_ = (int)std::min<int64_t>(gnx_grid(std::min<int64_t>(guess, N), 256), 8192);
     hipLaunchKernelGGL(k_fill, dim3(fb_), dim3(256), 0, h->stream, c.cap_inds, h->fill_cnt,
                        (const int32_t*)h->os_ktmp, (const int32_t*)h->os_ktmp + c.cap_inds / 2,
                        h->cnt_dev, a, c.n_layers, c.n_traits, a.tb ? 2 * h->TW : 0,
                        (const int32_t*)h->os_vtmp, h->free_rows, h->n_free, has_rows, xo ? 1 : 0,
-                       ord_keep ? h->newslot : nullptr, (const GnxDD*)nullptr,
-                       ahead ? h->cell32 : (uint32_t*)nullptr);
+                       ord_keep ? h->newslot : nullptr, (const GnxDD*)nullptr);
     // flags and offsets of everybody, the records of about as many movers as the last round had deaths
     gnx_time_end(h, GNX_K_COMPACT, (double)N * 16.0 + (double)h->fill_guess * (16.0 + 2.0 * rec_bytes));
   } else {
-  hipLaunchKernelGGL(k_compact, dim3(nb), dim3(256), 0, h->stream, N, c.cap_inds, h->flag,
-                     h->flag2, h->blk_off, h->blk_stride, h->cnt_dev, a, b, c.n_layers, c.n_traits,
-                     a.tb ? 2 * h->TW : 0, h->free_rows, h->n_free, has_rows, xo ? 1 : 0,
-                     ord_keep ? h->newslot : nullptr);
-  gnx_time_end(h, GNX_K_COMPACT, (double)N * (24.0 + 2.0 * rec_bytes));
+    hipLaunchKernelGGL(k_compact, dim3(nb), dim3(256), 0, h->stream, N, c.cap_inds, h->flag,
+                       h->flag2, h->blk_off, h->blk_stride, h->cnt_dev, a, b, c.n_layers, c.n_traits,
+                       a.tb ? 2 * h->TW : 0, h->free_rows, h->n_free, has_rows, xo ? 1 : 0,
+                       ord_keep ? h->newslot : nullptr);
+    gnx_time_end(h, GNX_K_COMPACT, (double)N * (24.0 + 2.0 * rec_bytes));
   }
   if (ord_keep) {
     HIPCHK(hipEventRecord(h->ev_compact, h->stream));
     HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_compact, 0));
     if (h->ord_inflight) h->ord_inflight = false;       // (stream3 runs them in order)
     GnxScanOut So{h->ord_off, nullptr, nullptr, 0, nullptr, h->tickets + 2, h->blk_stride};
-    // GNX_ORD_ONE=1: the one-launch compaction (k_ord_compact) instead of counting kernel + scan by
-    // its last workgroup + writing kernel - measured 0.526 against 0.519 ms/step beside the
-    // crossover (its look-back waits where the two-kernel form just streams): off by default
-    static const bool ord_one = getenv("GNX_ORD_ONE") && atoi(getenv("GNX_ORD_ONE")) != 0;
-    if (ord_one && !ord_fused && h->ord_state) {
-      hipLaunchKernelGGL(k_ord_compact, dim3(nb), dim3(256), 0, h->stream3, N, h->ord_n,
-                         (const int32_t*)h->ord[h->ord_cur], (const int32_t*)h->newslot,
-                         lazy ? (const int32_t*)h->flag : (const int32_t*)nullptr,
-                         h->ord[h->ord_cur ^ 1], h->ord_state, h->ord_state + h->blk_stride);
-    } else {
-    if (!ord_fused)
-      hipLaunchKernelGGL(k_ord_flags, dim3(nb), dim3(256), 0, h->stream3, N, h->ord_n,
-                         h->ord[h->ord_cur], h->newslot, h->ord_cnt, So, (const GnxDD*)nullptr,
-                         lazy ? (const int32_t*)h->flag : (const int32_t*)nullptr);
+    // (one launch with a decoupled look-back instead of these two: measured and removed, 0.526
+    // against 0.519 ms/step beside the crossover - profiles/r06_ab_runs.txt)
+    hipLaunchKernelGGL(k_ord_flags, dim3(nb), dim3(256), 0, h->stream3, N, h->ord_n,
+                       h->ord[h->ord_cur], h->newslot, h->ord_cnt, So, (const GnxDD*)nullptr,
+                       lazy ? (const int32_t*)h->flag : (const int32_t*)nullptr);
     hipLaunchKernelGGL(k_ord_write, dim3(nb), dim3(256), 0, h->stream3, N, h->ord_n,
                        h->ord[h->ord_cur], h->newslot, h->ord_off, h->ord[h->ord_cur ^ 1],
                        (const GnxDD*)nullptr, GnxDDEnd{}, 0,
                        lazy ? (const int32_t*)h->flag : (const int32_t*)nullptr);
-    }
     // the cell sort waits for the crossover AND for this: stream3 waits for the crossover here,
     // where nothing waits for stream3, and the sort's stream waits for one event instead of two
     h->ord_covers_xo = false;
@@ -2514,7 +2013,6 @@ int gnx_l_mortality_enqueue(gnx_state* h, const uint8_t* d_dead_inject) {
     h->ord_valid = false;
   }
   HIPCHK(hipGetLastError());
-  if (xo && h->xo_sort_waits && h->xo_wait_at == 3) GNXCHK(gnx_xo_wait_inflight(h));
   h->mort_wait = true;
   h->mort_xo = xo;
   h->mort_fill = fill;
@@ -2559,32 +2057,6 @@ int gnx_l_mortality_finish(gnx_state* h, int64_t* deaths_out) {
 // ---------------------------------------------------------------- device-driven step
 // (gnx_dd.hip) the density, death and mortality kernels with capacity-sized grids and their
 // counts read from h->dd; `par` = the step's parity (which of the alternating buffers)
-int gnx_dd_l_bins_adults(gnx_state* h, int par, hipStream_t st) {
-  const GnxLattice& L = h->lat;
-  const int nb = L.nbx * L.nby;
-  GnxSoA s = h->soa[h->cur];
-  const int64_t cap = h->cfg.cap_inds;
-  const int blocks = (int)std::min<int64_t>(BIN_BLOCKS, std::max<int64_t>(1, (cap + 255) / 256));
-  hipLaunchKernelGGL(k_bins, dim3(blocks), dim3(256), (size_t)nb * sizeof(int32_t), st, cap,
-                     (const int32_t*)&h->dd->N, (const float*)s.x, (const float*)s.y,
-                     (const uint8_t*)nullptr, 1.0 / L.hww, L.nbx, L.nby, h->fb[par], GnxSetWords{});
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// the pair midpoints' bins (fb[2]); their lattice is built by an extra workgroup of
-// k_lattice_nmax (gnx_dd_l_density_N), which clears fb[2] again
-int gnx_dd_l_density_pairs(gnx_state* h, hipStream_t st) {
-  const GnxLattice& L = h->lat;
-  const int nb = L.nbx * L.nby;
-  const int64_t cap = h->cfg.cap_inds;
-  const int blocks = (int)std::min<int64_t>(BIN_BLOCKS, std::max<int64_t>(1, (cap / 2 + 255) / 256));
-  hipLaunchKernelGGL(k_bins, dim3(blocks), dim3(256), (size_t)nb * sizeof(int32_t), st, cap,
-                     (const int32_t*)&h->dd->P, (const float*)h->mid_x, (const float*)h->mid_y,
-                     (const uint8_t*)nullptr, 1.0 / L.hww, L.nbx, L.nby, h->fb[2], GnxSetWords{});
-  HIPCHK(hipGetLastError());
-  return 0;
-}
 
 // lattice + N.max() of everybody (adults + newborns in fb[par]) and, in one more workgroup,
 // the pairs' lattice; clears the other parity's bins and N.max() word for the next step
@@ -2594,8 +2066,7 @@ int gnx_dd_l_density_N(gnx_state* h, int par, hipStream_t st) {
   const size_t lat_doubles = (size_t)4 * nn + std::max(L.Jx, L.Jy) + 1;
   const int nmax_R = gnx_nmax_rows_fit(L.Jx, lat_doubles);
   const size_t lds_bytes = (lat_doubles + gnx_nmax_lds_doubles(L.Jx, nmax_R)) * sizeof(double);
-  static const int blocks_env = getenv("GNX_LATN_BLOCKS") ? atoi(getenv("GNX_LATN_BLOCKS")) : 256;
-  hipLaunchKernelGGL(k_lattice_nmax, dim3(std::max(1, std::min(h->cfg.H, blocks_env)) + 1), dim3(256),
+  hipLaunchKernelGGL(k_lattice_nmax, dim3(std::max(1, std::min(h->cfg.H, GNX_LATN_BLOCKS)) + 1), dim3(256),
                      lds_bytes, st, L.Jx, L.Jy, L.nbx, (const int32_t*)h->fb[par], L.areas, L.hww,
                      L.cprime, h->spl_N.c, h->cfg.W, h->cfg.H, h->nmax2 + par, h->fb[par ^ 1],
                      h->nmax2 + (par ^ 1), h->fb[2], h->spl_P.c, GnxPubWords{}, nmax_R, gnx_nmax_scan_min());
@@ -2663,7 +2134,7 @@ int gnx_dd_l_fill(gnx_state* h, int has_rows, bool xo, hipStream_t st) {
                      (const int32_t*)h->os_ktmp, (const int32_t*)h->os_ktmp + c.cap_inds / 2,
                      h->cnt_dev, a, c.n_layers, c.n_traits, a.tb ? 2 * h->TW : 0,
                      (const int32_t*)h->os_vtmp, h->free_rows, (int64_t)0, has_rows, xo ? 1 : 0,
-                     h->newslot, (const GnxDD*)h->dd, (uint32_t*)nullptr);
+                     h->newslot, (const GnxDD*)h->dd);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2748,11 +2219,3 @@ int gnx_l_spatial_diff(gnx_state* h, double* mean, double* sd, double* sums) {
   h->counts_cur = nowi;
   return 0;
 }
-
-#ifdef GNX_JF_TRY
-// (compile test of one more instantiation of the fused job builder: hipcc -DGNX_JF_TRY=25 -c ...)
-template __global__ void k_xo_jobs_fused<GNX_JF_TRY, GNX_JF_TPB>(
-    int64_t, int64_t, int32_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
-    const uint8_t*, const int32_t*, int64_t, GnxHalves, const int32_t*, const int32_t*, int32_t*,
-    GnxXoJob*, GnxJobBp*, const int32_t*, GnxDD*);
-#endif

@@ -47,41 +47,26 @@ k_xo_jobs_all(int64_t B, int64_t first, int32_t* __restrict__ grow,
 void gnx_launch_xo_jobs_surv(gnx_state* h, int64_t first_slot, const int32_t* d_alive,
                              const int32_t* d_blk_off, int buf);
 
+// (non-temporal loads throughout: +2 %, profiles/r02b_xo_lab_*.txt)
 template <int U>
-static void xo_launch_sparse(gnx_state* h, hipStream_t st, int grid, int buf, bool nt, int lo,
-                             int hi, unsigned long long* acc) {
+static void xo_launch_sparse(gnx_state* h, hipStream_t st, int grid, int buf, int lo, int hi,
+                             unsigned long long* acc) {
   const int W16 = (h->BW > 0 ? h->BW : h->W64 / h->NB) / 2;       // chunks per block
-  static const bool inline_env = !(getenv("GNX_XO_INLINE_BP") && atoi(getenv("GNX_XO_INLINE_BP")) == 0);
-  const GnxJobBp* ib = (h->jobs_inline[buf] && inline_env) ? (const GnxJobBp*)h->jobs_bp[buf] : nullptr;
+  const GnxJobBp* ib = h->jobs_inline[buf] ? (const GnxJobBp*)h->jobs_bp[buf] : nullptr;
   // two jobs per wave and iteration (gnx_xo.h: k_xo_sparse_pair) when something runs beside
   // the crossover - the step's normal state: 0.625 against 0.636 ms/step, the launch 0.181
   // against 0.188 ms.  With the chip to itself (gnx_set_crossover_overlap(2)) one job per
-  // iteration is the faster kernel (0.142 against 0.165 ms): GNX_XO_PAIR=0 / 2 force one.
-  static const int pair_env = getenv("GNX_XO_PAIR") ? atoi(getenv("GNX_XO_PAIR")) : 1;
-  if (U == 1 && W16 <= 64 && ib && (pair_env == 2 || (pair_env == 1 && h->xo_wait_at != 2))) {
-    static const int kj = getenv("GNX_XO_GROUP") ? atoi(getenv("GNX_XO_GROUP")) : 2;
-#define GNX_XO_PAIR_LAUNCH(NT, KK)                                                                \
-  hipLaunchKernelGGL((k_xo_sparse_pair<NT, KK>), dim3(grid), dim3(256), 0, st, h->n_jobs_dev[buf], \
-                     W16, (const u64x2*)h->G, (u64x2*)h->G, (const GnxXoJob*)h->jobs[buf],        \
-                     h->bp_off, h->bp_loci, lo, hi, acc, ib)
-    if (nt) {
-      if (kj == 3) GNX_XO_PAIR_LAUNCH(true, 3);
-      else if (kj == 4) GNX_XO_PAIR_LAUNCH(true, 4);
-      else GNX_XO_PAIR_LAUNCH(true, 2);
-    } else {
-      GNX_XO_PAIR_LAUNCH(false, 2);
-    }
-#undef GNX_XO_PAIR_LAUNCH
+  // iteration is the faster kernel (0.142 against 0.165 ms).  (Three or four jobs per
+  // iteration: measured and removed, profiles/r03_ab_runs.txt)
+  if (U == 1 && W16 <= 64 && ib && h->xo_wait_at != 2) {
+    hipLaunchKernelGGL((k_xo_sparse_pair<true, 2>), dim3(grid), dim3(256), 0, st, h->n_jobs_dev[buf],
+                       W16, (const u64x2*)h->G, (u64x2*)h->G, (const GnxXoJob*)h->jobs[buf],
+                       h->bp_off, h->bp_loci, lo, hi, acc, ib);
     return;
   }
-  if (nt)
-    hipLaunchKernelGGL((k_xo_sparse<U, true>), dim3(grid), dim3(256), 0, st, h->n_jobs_dev[buf],
-                       W16, (const u64x2*)h->G, (u64x2*)h->G, (const GnxXoJob*)h->jobs[buf],
-                       h->bp_off, h->bp_loci, lo, hi, acc, ib);
-  else
-    hipLaunchKernelGGL((k_xo_sparse<U, false>), dim3(grid), dim3(256), 0, st, h->n_jobs_dev[buf],
-                       W16, (const u64x2*)h->G, (u64x2*)h->G, (const GnxXoJob*)h->jobs[buf],
-                       h->bp_off, h->bp_loci, lo, hi, acc, ib);
+  hipLaunchKernelGGL((k_xo_sparse<U, true>), dim3(grid), dim3(256), 0, st, h->n_jobs_dev[buf],
+                     W16, (const u64x2*)h->G, (u64x2*)h->G, (const GnxXoJob*)h->jobs[buf],
+                     h->bp_off, h->bp_loci, lo, hi, acc, ib);
 }
 
 // the crossover of job buffer `buf` on stream `st` (the share [lo, hi) / 1024 of its jobs);
@@ -91,46 +76,37 @@ static int xo_launch(gnx_state* h, hipStream_t st, int buf, int64_t max_jobs, bo
                      int lo = 0, int hi = 1024) {
   // one wave per gamete, 4 waves per block, job-strided beyond 32 blocks per CU
   // (measured: profiles/r02b_xo_lab_*.txt - time is flat in the grid size from 16 to 64
-  // blocks per CU and in the unroll from 4 to 8; non-temporal loads +2 %); beside a whole
-  // step of small kernels (GNX_XO_SORT_WAIT=0) 2 blocks per CU, 6 chunks in flight
-  static const int bpc_env = getenv("GNX_XO_BPC") ? atoi(getenv("GNX_XO_BPC")) : 0;
-  static const int unroll_env = getenv("GNX_XO_UNROLL") ? atoi(getenv("GNX_XO_UNROLL")) : 0;
-  static const int nt = getenv("GNX_XO_NT") ? atoi(getenv("GNX_XO_NT")) : 1;
-  // beside the whole next step: 2 workgroups per CU while a job was a whole homologue; with
-  // half-homologue blocks 4 .. 16 measure alike (1.23-1.25 ms/step) and 2 loses 15 %
-  static const int tail_bpc_env = getenv("GNX_XO_TAIL_BPC") ? atoi(getenv("GNX_XO_TAIL_BPC")) : 0;
-  const int tail_bpc = tail_bpc_env ? tail_bpc_env : (h->NB > 1 ? 8 : 2);
-  static const int tail_unroll = getenv("GNX_XO_TAIL_UNROLL") ? atoi(getenv("GNX_XO_TAIL_UNROLL")) : 6;
-  const int bpc = narrow ? tail_bpc : (bpc_env ? bpc_env : 32);
+  // blocks per CU and in the unroll from 4 to 8)
+  constexpr int GNX_XO_BPC = 32;
+  // beside the whole next step (gnx_set_crossover_overlap(1)): 2 workgroups per CU and 6 chunks in
+  // flight while a job is a whole homologue; with shorter blocks 4 .. 16 measure alike (1.23-1.25
+  // ms/step) and 2 loses 15 %
+  constexpr int GNX_XO_TAIL_UNROLL = 6;
+  const int tail_bpc = h->NB > 1 ? 8 : 2;
+  const int bpc = narrow ? tail_bpc : GNX_XO_BPC;
   // the narrow share of a split launch is accounted for on its own
   unsigned long long* acc = h->xo_jobs_acc ? h->xo_jobs_acc + ((narrow && lo > 0) ? 1 : 0) : nullptr;
   const int W16 = (h->BW > 0 ? h->BW : h->W64 / h->NB) / 2;       // chunks per block
   const int grid = gnx_grid(max_jobs * h->NB, 4, 256 * bpc);
   if (h->sparse_paths) {
     // (blocks shorter than a homologue: as many loads in flight as the block has chunks)
-    const int U = (narrow && h->NB == 1) ? tail_unroll
-                                          : (unroll_env ? unroll_env : gnx_xo_pick_unroll(W16));
+    const int U = (narrow && h->NB == 1) ? GNX_XO_TAIL_UNROLL : gnx_xo_pick_unroll(W16);
     switch (U) {
-      case 1: xo_launch_sparse<1>(h, st, grid, buf, nt, lo, hi, acc); break;
-      case 2: xo_launch_sparse<2>(h, st, grid, buf, nt, lo, hi, acc); break;
-      case 3: xo_launch_sparse<3>(h, st, grid, buf, nt, lo, hi, acc); break;
-      case 4: xo_launch_sparse<4>(h, st, grid, buf, nt, lo, hi, acc); break;
-      case 5: xo_launch_sparse<5>(h, st, grid, buf, nt, lo, hi, acc); break;
-      case 6: xo_launch_sparse<6>(h, st, grid, buf, nt, lo, hi, acc); break;
-      case 7: xo_launch_sparse<7>(h, st, grid, buf, nt, lo, hi, acc); break;
-      default: xo_launch_sparse<8>(h, st, grid, buf, nt, lo, hi, acc); break;
+      case 1: xo_launch_sparse<1>(h, st, grid, buf, lo, hi, acc); break;
+      case 2: xo_launch_sparse<2>(h, st, grid, buf, lo, hi, acc); break;
+      case 3: xo_launch_sparse<3>(h, st, grid, buf, lo, hi, acc); break;
+      case 4: xo_launch_sparse<4>(h, st, grid, buf, lo, hi, acc); break;
+      case 5: xo_launch_sparse<5>(h, st, grid, buf, lo, hi, acc); break;
+      case 6: xo_launch_sparse<6>(h, st, grid, buf, lo, hi, acc); break;
+      case 7: xo_launch_sparse<7>(h, st, grid, buf, lo, hi, acc); break;
+      default: xo_launch_sparse<8>(h, st, grid, buf, lo, hi, acc); break;
     }
   } else {
     // dense masks: genome chunks stream past once (non-temporal), the path table is
     // re-read by every gamete that drew the key and stays in L2 / the Infinity Cache
-    if (nt)
-      hipLaunchKernelGGL((k_xo_dense<4, true>), dim3(grid), dim3(256), 0, st, h->n_jobs_dev[buf],
-                         W16, (const u64x2*)h->G, (u64x2*)h->G, (const GnxXoJob*)h->jobs[buf],
-                         (const u64x2*)h->paths, h->W64 / 2, lo, hi, acc);
-    else
-      hipLaunchKernelGGL((k_xo_dense<4, false>), dim3(grid), dim3(256), 0, st, h->n_jobs_dev[buf],
-                         W16, (const u64x2*)h->G, (u64x2*)h->G, (const GnxXoJob*)h->jobs[buf],
-                         (const u64x2*)h->paths, h->W64 / 2, lo, hi, acc);
+    hipLaunchKernelGGL((k_xo_dense<4, true>), dim3(grid), dim3(256), 0, st, h->n_jobs_dev[buf],
+                       W16, (const u64x2*)h->G, (u64x2*)h->G, (const GnxXoJob*)h->jobs[buf],
+                       (const u64x2*)h->paths, h->W64 / 2, lo, hi, acc);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -365,8 +341,8 @@ int gnx_xo_launch_pending(gnx_state* h, int site) {
   if (buf < 0) return 0;
   h->xo_ready_buf = -1;
   if (site == GNX_PC_XO_P2 || site == GNX_PC_XO_FLUSH) ++h->pc[site];     // (gnx_path_counts)
-  // behind everything `stream` has been given so far (the jobs, and with launch policy
-  // 1 / 2 the sort that is meant to run alone)
+  // behind everything `stream` has been given so far (the jobs, and with the late launch
+  // the sort that is meant to run alone)
   HIPCHK(hipEventRecord(h->ev_jobs, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_jobs, 0));
   hipStream_t main = h->stream;
@@ -439,7 +415,7 @@ int gnx_l_crossover_survivors(gnx_state* h, int64_t first_slot, int64_t B, const
   h->jobs_cur ^= 1;
   // (tiles: the next step's routing reads the migrants' genome rows first thing - gnx_xo_join - so a
   // crossover held back would only be waited for there: at once)
-  if (h->xo_launch_policy == 0 || h->tiled || h->tile2_mode) GNXCHK(gnx_xo_launch_pending(h, -1));
+  if (!h->xo_launch_late || h->tiled || h->tile2_mode) GNXCHK(gnx_xo_launch_pending(h, -1));
   return 0;
 }
 

@@ -128,8 +128,7 @@ struct MoveP {
   uint32_t* cell32;
   int tile_floats;
   const GnxDD* dd;           // device-driven step: N and the step index live on the device
-  // the NEXT step's movement, run right after this step's death draws on the uncompacted
-  // population (gnx_l_move_ahead): the dead are skipped
+  // an uncompacted population (gnx_internal.h: holes): the death draws' flags, the dead are skipped
   const int32_t* alive;
   // the cell sort's global digit counts (gnx_prim.hip), counted here when the movement writes
   // the sort's keys anyway: hist[place * 2^hist_rb + digit of cell32 at that place]
@@ -458,11 +457,10 @@ int gnx_os_hist_discard(gnx_state* h, hipStream_t st) {
 }
 
 // k_move counts the sort's digits when the keys fit its LDS table (2 places of <= 9 bits: up to
-// 2^18 hash cells - GNX_OS_MOVE_HIST=0: never)
+// 2^18 hash cells)
 static bool gnx_move_hist(const gnx_state* h, int* places, int* rb) {
-  static const bool on = !(getenv("GNX_OS_MOVE_HIST") && atoi(getenv("GNX_OS_MOVE_HIST")) == 0);
   gnx_os_digits(h->key_bits, places, rb);
-  return on && h->os_scratch != nullptr && (*places << *rb) <= GNX_MOVE_HIST_WORDS;
+  return h->os_scratch != nullptr && (*places << *rb) <= GNX_MOVE_HIST_WORDS;
 }
 
 int gnx_l_move(gnx_state* h, bool inc_age, const float* inj_theta, const float* inj_dist,
@@ -537,96 +535,21 @@ int gnx_l_move(gnx_state* h, bool inc_age, const float* inj_theta, const float* 
   }
   h->keys_fresh = with_keys;
   if (with_keys) h->keys_ordmode = ordm;
-  // LDS window of the conductance raster per workgroup (GNX_MOVE_TILE floats): smaller
-  // windows let more workgroups share a CU while the kernel crawls beside the crossover
-  // (2048 floats by default: 0.795 against 0.805-0.84 ms/step with 8192, no further gain below)
-  static const int tile_env = getenv("GNX_MOVE_TILE") ? atoi(getenv("GNX_MOVE_TILE")) : 2048;
-  // (per 256 individuals of the workgroup: two per thread cover twice the stretch of cells)
-  static const int ipt_env = getenv("GNX_MOVE_IPT") ? atoi(getenv("GNX_MOVE_IPT")) : 2;
-  P.tile_floats = sp.move_surf != GNX_SURF_NONE
-                      ? std::max(256, std::min(tile_env * (ipt_env == 2 ? 2 : 1), 12288)) : 0;
+  // LDS window of the conductance raster per workgroup: smaller windows let more workgroups
+  // share a CU while the kernel crawls beside the crossover (0.795 against 0.805-0.84 ms/step with
+  // four times as much, no further gain below); two individuals per thread cover twice the
+  // stretch of cells of one (one per thread: measured and removed, profiles/r04_ab_runs.txt)
+  constexpr int GNX_MOVE_TILE_FLOATS = 2 * 2048;
+  P.tile_floats = sp.move_surf != GNX_SURF_NONE ? GNX_MOVE_TILE_FLOATS : 0;
   gnx_time_begin(h);
-  // individuals per thread (GNX_MOVE_IPT; 2 by default: profiles/r04_ab_runs.txt)
-  static const int ipt = getenv("GNX_MOVE_IPT") ? atoi(getenv("GNX_MOVE_IPT")) : 2;
   const int64_t n_grid = ddm ? (int64_t)c.cap_inds : (holes ? h->holes_N : h->N);
-  if (ipt == 2)
-    hipLaunchKernelGGL(k_move<2>, dim3(gnx_grid(n_grid, 512)), dim3(256),
-                       (size_t)P.tile_floats * sizeof(float), h->stream, P,
-                       h->soa[h->cur], h->rast, inj_theta, inj_dist, out_theta, out_dist);
-  else
-    hipLaunchKernelGGL(k_move<1>, dim3(gnx_grid(n_grid, 256)), dim3(256),
-                       (size_t)P.tile_floats * sizeof(float), h->stream, P,
-                       h->soa[h->cur], h->rast, inj_theta, inj_dist, out_theta, out_dist);
+  hipLaunchKernelGGL(k_move<2>, dim3(gnx_grid(n_grid, 512)), dim3(256),
+                     (size_t)P.tile_floats * sizeof(float), h->stream, P,
+                     h->soa[h->cur], h->rast, inj_theta, inj_dist, out_theta, out_dist);
   // per individual: x,y rw 16 + id 8 + age rw 8 + e store 4*n_lyr + raster gathers 4*n_lyr
   // (+36 for the 3x3 conductance neighbourhood)
   gnx_time_end(h, GNX_K_MOVE,
                (double)h->N * (32.0 + 8.0 * c.n_layers + (sp.move_surf ? 36.0 : 0.0)));
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// The NEXT step's age + movement, launched by THIS step's mortality right after the death draws,
-// on stream `st`, over the still uncompacted population (everybody incl. this step's offspring;
-// the dead are skipped) - gnx_walk only, where nobody looks at the population between two
-// steps.  Where it runs today - beside the crossover, which it slows and which slows it: 0.10-0.13
-// ms against 0.05 alone, the last kernel of that phase to finish - it is latency-bound on HBM
-// that the crossover saturates; here it runs beside the crossover's job builder, a chain of
-// dependent table look-ups, and over slots that are still in this step's (hash cell, id) order,
-// offspring in their parents' order: every workgroup's conductance window fits its LDS tile
-// (after the in-place compaction a sixth of every workgroup's slots hold newborns from anywhere).
-// Same draws (keyed by id and step), same positions: the compaction then moves the moved
-// records - and their sort keys (cell32).  Reference: Species._set_age_stage + _do_movement of
-// step t + 1 (structs/species.py:567-585) after _do_pop_dynamics of step t - nothing in between.
-int gnx_l_move_ahead(gnx_state* h, int64_t N_all, const int32_t* d_alive, hipStream_t st) {
-  const gnx_config& c = h->cfg;
-  const gnx_species_params& sp = h->sp;
-  MoveP P;
-  P.dd = nullptr;
-  P.alive = d_alive;
-  P.N = N_all;
-  P.cap = c.cap_inds;
-  P.W = c.W;
-  P.H = c.H;
-  P.n_layers = c.n_layers;
-  P.xmax = (float)(c.W - 0.001);
-  P.ymax = (float)(c.H - 0.001);
-  P.rrx = (float)sp.res_ratio[0];
-  P.rry = (float)sp.res_ratio[1];
-  P.distr = sp.move_distr;
-  P.p1 = (float)sp.move_p1;
-  P.p2 = (float)sp.move_p2;
-  P.mu = (float)sp.dir_mu;
-  P.kappa = (float)sp.dir_kappa;
-  P.surf = sp.move_surf;
-  P.surf_layer = sp.move_surf_layer;
-  P.surf_kappa = (float)sp.move_surf_kappa;
-  P.inc_age = 1;
-  P.apply = 1;
-  P.step = h->step + 1;
-  P.seed = c.seed;
-  P.key = nullptr;
-  P.cell32 = h->cell32;          // (the cell sort runs over the id-ordered index: gnx_l_mortality checks)
-  P.idx = h->perm[0];
-  P.inv_cs = h->inv_cs;
-  P.ncx = h->ncx;
-  P.ncy = h->ncy;
-  P.idbits = 0;
-  // (the digit counts of the coming step's cell sort: the dead are skipped, so the counts are
-  // those of the population that sort will see; os_scratch was wiped by this step's k_permute)
-  GNXCHK(gnx_os_hist_discard(h, st));
-  P.hist = nullptr;
-  P.hist_rb = P.hist_places = 0;
-  if (gnx_move_hist(h, &P.hist_places, &P.hist_rb)) {
-    P.hist = (uint32_t*)h->os_scratch;
-    h->hist_fresh = true;
-  }
-  P.rg = nullptr;
-  P.rcnt = nullptr;
-  static const int tile_env = getenv("GNX_MOVE_TILE") ? atoi(getenv("GNX_MOVE_TILE")) : 2048;
-  P.tile_floats = sp.move_surf != GNX_SURF_NONE ? std::max(256, std::min(tile_env * 2, 12288)) : 0;
-  hipLaunchKernelGGL(k_move<2>, dim3(gnx_grid(N_all, 512)), dim3(256),
-                     (size_t)P.tile_floats * sizeof(float), st, P, h->soa[h->cur], h->rast,
-                     (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -823,15 +746,12 @@ int gnx_permute_rest_launch(gnx_state* h) {
 }
 
 // the side stream's share of the last cell sort's permutation has arrived
-int gnx_wait_permute_rest(gnx_state* h, bool late_ok) {
+int gnx_wait_permute_rest(gnx_state* h) {
   GNXCHK(gnx_permute_rest_launch(h));
-  // (late mode: the step's own hand-over point lets it run on - gnx_l_death_probs waits)
-  if (late_ok && h->perm_rest_late) return 0;
   if (h->perm_rest_inflight) {
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_perm_rest, 0));
     h->perm_rest_inflight = false;
   }
-  h->perm_rest_late = false;
   return 0;
 }
 
@@ -936,10 +856,7 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
       HIPCHK(hipStreamWaitEvent(h->stream, h->ev_ord, 0));
       h->ord_inflight = false;
     }
-    static const int os_variant = getenv("GNX_OS_SORT") ? atoi(getenv("GNX_OS_SORT")) : 2;
-    static const bool os_fused = !getenv("GNX_OS_FUSED") || atoi(getenv("GNX_OS_FUSED")) != 0;
-    static const bool os_gather = !(getenv("GNX_OS_GATHER") && atoi(getenv("GNX_OS_GATHER")) == 0);
-    if (h->keys_fresh && h->hist_fresh && os_gather && os_variant == 2 && os_fused) {
+    if (h->keys_fresh && h->hist_fresh) {
       // k_move wrote the cells AND counted their digits: the passes alone, the first one
       // gathering its keys through the id-ordered index
       h->hist_fresh = false;
@@ -948,7 +865,7 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
                                   (size_t)N, h->key_bits, h->ord[h->ord_cur], h->ord_n, h->cell32,
                                   h->stream));
       wipe_words = (int64_t)gnx_os_words_used((size_t)N, h->key_bits);
-    } else if (os_variant == 2 && os_fused && h->key_bits <= 24) {
+    } else if (h->key_bits <= 24) {
       GNXCHK(gnx_os_hist_discard(h));
       // keys, histograms and their scans in one launch, then the two or three passes; the
       // scratch is zero on entry (allocation, k_permute below)
@@ -958,17 +875,12 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
                                   h->valk[0], h->valk[1], (size_t)N, h->key_bits, h->stream));
       wipe_words = (int64_t)gnx_os_words_used((size_t)N, h->key_bits);
     } else {
-    GNXCHK(gnx_os_hist_discard(h));
-    hipLaunchKernelGGL(k_keys_ord, dim3(gnx_grid(N, 256)), dim3(256), 0, h->stream, N, h->ord_n,
-                       h->ord[h->ord_cur], h->cell32, h->keyk[0], h->valk[0]);
-    if (os_variant >= 0 && h->key_bits <= 24) {
-      wipe_words = (int64_t)(gnx_os_scratch_bytes((size_t)N, h->key_bits) / 4);
-      GNXCHK(gnx_os_sort32(h->os_scratch, h->os_ktmp, h->os_vtmp, h->keyk[0], h->keyk[1],
-                           h->valk[0], h->valk[1], (size_t)N, h->key_bits, h->stream, os_variant));
-    } else {
+      // (more than 2^24 hash cells: rocPRIM's radix sort)
+      GNXCHK(gnx_os_hist_discard(h));
+      hipLaunchKernelGGL(k_keys_ord, dim3(gnx_grid(N, 256)), dim3(256), 0, h->stream, N, h->ord_n,
+                         h->ord[h->ord_cur], h->cell32, h->keyk[0], h->valk[0]);
       GNXCHK(gnx_prim_sort32_bits(h->sort64_tmp, h->sort64_tmp_bytes, h->keyk[0], h->keyk[1],
                                   h->valk[0], h->valk[1], (size_t)N, h->key_bits, h->stream, alone));
-    }
     }
   } else {
     GNXCHK(gnx_os_hist_discard(h));
@@ -990,9 +902,8 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
       hipLaunchKernelGGL(k_keys, dim3(gnx_grid(N, 256)), dim3(256), 0, h->stream, N, a.x, a.y, a.id,
                          h->inv_cs, h->ncx, h->ncy, idbits, h->key64[0], h->perm[0]);
     }
-    // GNX_TILE_OS64=0: rocPRIM's own driver (a fill before the histograms, two before every pass)
-    static const bool os64 = !(getenv("GNX_TILE_OS64") && atoi(getenv("GNX_TILE_OS64")) == 0);
-    if (os64 && h->sort64_tmp_bytes >= (size_t)n_sort * 12 && h->os_scratch) {
+    // (scratch too small: rocPRIM's own driver - a fill before the histograms, two before every pass)
+    if (h->sort64_tmp_bytes >= (size_t)n_sort * 12 && h->os_scratch) {
       GNXCHK(gnx_os_sort64_clean(h->os_scratch, h->sort64_tmp, h->key64[0], h->key64[1], h->perm[0],
                                  h->perm[1], (size_t)n_sort, idbits + cell_bits, h->stream));
       wipe_words = (int64_t)gnx_os_words_used64((size_t)n_sort, idbits + cell_bits);
@@ -1009,7 +920,7 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
   // from - all k_permute_rest needs; the evicted tail's genome rows, a cold column, are then
   // freed on the side stream behind it.  Measured with two tiles on one GPU: 1.72-1.94 ms/step
   // against 1.58-1.69 with one kernel for every column - parity-green, GNX_TILE_SPLIT=1 turns it on)
-  static const bool tile_split = getenv("GNX_TILE_SPLIT") && atoi(getenv("GNX_TILE_SPLIT")) != 0;
+  static const bool tile_split = gnx_env_int("GNX_TILE_SPLIT", 0) != 0;
   const bool split = split_rest && h->permute_split && (ordm ? !h->tiled : (tile_split && h->tile2_mode)) &&
                      h->stream3 != nullptr;
   hipLaunchKernelGGL(k_permute, dim3(gnx_grid(N, 256)), dim3(256), 0, h->stream, N, c.cap_inds,
@@ -1022,22 +933,13 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
                      h->id_order == 1 ? h->vt_count : (int32_t*)nullptr);
   if (split) {
     // the columns nobody reads before the births follow on stream3, beside the mate search and
-    // the pair list; whoever asked for the split waits (gnx_wait_permute_rest).
-    // (GNX_PERMUTE_REST_AT=1: only behind the mate search, whose random 16-byte loads they
-    // slow - 0.596 against 0.592 ms/step: they are then late for the births)
+    // the pair list; whoever asked for the split waits (gnx_wait_permute_rest).  (Behind the mate
+    // search, or beside the births: measured and removed, profiles/r03_ab_runs.txt and r05_ab_runs.txt)
     h->perm_rest_a = a;
     h->perm_rest_b = b;
     h->perm_rest_N = N;
     h->perm_rest_pending = true;
-    // GNX_PERMUTE_REST_AT=2 (round 5): not beside the mate search and the pair list either - random
-    // 16-byte record loads and chains of dependent filters that take 43 + 34 us beside it against
-    // 25 + 26 alone - but beside the births and the densities (gnx_l_find_pairs_enqueue launches
-    // it behind the pair list): k_offspring takes the parents' alleles from the buffer the column
-    // is permuted FROM, and only the death probabilities wait for the permutation.  Only where
-    // nothing else reads those columns in between: gnx_step (h->perm_rest_late_ok).
-    static const int rest_at = getenv("GNX_PERMUTE_REST_AT") ? atoi(getenv("GNX_PERMUTE_REST_AT")) : 0;
-    h->perm_rest_late = rest_at == 2 && h->perm_rest_late_ok && h->defer_xo && !h->tile2_mode;
-    if (rest_at == 0 || (rest_at == 2 && !h->perm_rest_late)) GNXCHK(gnx_permute_rest_launch(h));
+    GNXCHK(gnx_permute_rest_launch(h));
   }
   gnx_time_end(h, GNX_K_PERMUTE,
                (double)N * 2.0 * (33.0 + 4.0 * c.n_layers + 4.0 * c.n_traits + 16.0 * h->TW));
@@ -1086,7 +988,6 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
     h->ord_valid = false;
     h->fb_adults = false;
   }
-  if (h->xo_launch_policy == 1) GNXCHK(gnx_xo_launch_pending(h, -1));
   return 0;
 }
 
@@ -2086,6 +1987,9 @@ int gnx_l_find_pairs(gnx_state* h, const uint8_t* d_keep, int64_t* n_pairs_out, 
   return gnx_l_find_pairs_finish(h, n_pairs_out);
 }
 
+// rounds of the mate search's first, block-wide stage (k_find_mates: easy_rounds)
+constexpr int GNX_FM_EASY_ROUNDS = 2;
+
 int gnx_l_find_pairs_enqueue(gnx_state* h, const uint8_t* d_keep, bool with_density) {
   int64_t N = h->N;
   h->n_pairs = 0;
@@ -2106,20 +2010,18 @@ int gnx_l_find_pairs_enqueue(gnx_state* h, const uint8_t* d_keep, bool with_dens
     FocalP fp{N, d_keep, (float)sp.b, sexed, sp.repro_age[0], h->step, h->cfg.seed};
     dim3 grid(gnx_grid(N, FM_PER_BLOCK)), blk(256);
     const uint4* cd = (const uint4*)h->cand;
-    static const int easy = getenv("GNX_FM_EASY") ? std::max(1, atoi(getenv("GNX_FM_EASY"))) : 2;
     if (sp.mate_mode == GNX_MATE_NEAREST)
       hipLaunchKernelGGL(k_find_mates<GNX_MATE_NEAREST>, grid, blk, 0, h->stream, fp, s, cd,
-                         h->inv_cs, h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, easy, h->mate);
+                         h->inv_cs, h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, GNX_FM_EASY_ROUNDS, h->mate);
     else if (sp.mate_mode == GNX_MATE_INVERSE)
       hipLaunchKernelGGL(k_find_mates<GNX_MATE_INVERSE>, grid, blk, 0, h->stream, fp, s, cd,
-                         h->inv_cs, h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, easy, h->mate);
+                         h->inv_cs, h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, GNX_FM_EASY_ROUNDS, h->mate);
     else
       hipLaunchKernelGGL(k_find_mates<GNX_MATE_UNIFORM>, grid, blk, 0, h->stream, fp, s, cd,
-                         h->inv_cs, h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, easy, h->mate);
+                         h->inv_cs, h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, GNX_FM_EASY_ROUNDS, h->mate);
   }
   gnx_time_end(h, GNX_K_FIND_MATES, (double)N * 16.0);
-  if (!h->perm_rest_late)
-    GNXCHK(gnx_permute_rest_launch(h));     // (GNX_PERMUTE_REST_AT=1: not before the mate search)
+  GNXCHK(gnx_permute_rest_launch(h));
   gnx_time_begin(h);
   const int nb = (int)((N + GNX_CB - 1) / GNX_CB);
   PairP pp{N, focal, h->mate, d_keep, (float)sp.b, sexed, sp.repro_age[0], sp.repro_age[1],
@@ -2131,26 +2033,17 @@ int gnx_l_find_pairs_enqueue(gnx_state* h, const uint8_t* d_keep, bool with_dens
   const int64_t seq = ++h->pin_seq;
   // (the height of the free-block stack rides along: the host's count of it is exact again)
   const bool with_top = h->half_top && h->genomes_assigned;
-  static const bool self_scan = !(getenv("GNX_PAIR_SELFSCAN") && atoi(getenv("GNX_PAIR_SELFSCAN")) == 0);
-  if (!self_scan)
-    GNXCHK(gnx_block_scan(h, 1, N, h->blk_cnt, h->blk_off, h->cnt_dev, h->h_pin_dev + 4, seq, nullptr,
-                          with_top ? h->half_top : nullptr));
+  // (k_pair_compact adds up the block counts itself: no scan launch in between)
   // (the population was sorted by gnx_l_sort_by_cell with this idbits: max_id has not moved)
   hipLaunchKernelGGL(k_pair_compact, dim3(nb), dim3(256), 0, h->stream, N, focal, h->mate,
                      h->flag2, h->blk_off, s.x, s.y, h->key64[1], gnx_id_bits(h), h->pairs,
                      h->mid_x, h->mid_y, h->key64[0],
-                     self_scan ? (const int32_t*)h->blk_cnt : (const int32_t*)nullptr, h->cnt_dev,
+                     (const int32_t*)h->blk_cnt, h->cnt_dev,
                      h->h_pin_dev + 4, (long long)seq,
                      with_top ? (const int32_t*)h->half_top : (const int32_t*)nullptr,
                      (GnxDD*)nullptr, 0, (int64_t)0, GnxBinP{nullptr, 0.0, 0, 0}, vto);
   gnx_time_end(h, GNX_K_PAIRS, (double)N * 40.0);
   HIPCHK(hipGetLastError());
-  if (h->perm_rest_late_ok && !h->tiled) {     // (gnx_step: the births right behind the pair list)
-    const int rc_ahead = gnx_l_offspring_ahead(h, h->step_burn, true);
-    h->pairs_wait = false;
-    GNXCHK(rc_ahead);
-  }
-  if (h->perm_rest_late) GNXCHK(gnx_permute_rest_launch(h));
   // the pair midpoints' density (ops/demography.py:60-91): on one GPU bins + lattice run on
   // stream3 beside k_offspring and the death probabilities wait for them
   if (with_density && gnx_fused_bins(h)) {
@@ -2183,7 +2076,7 @@ int gnx_l_find_pairs_finish(gnx_state* h, int64_t* n_pairs_out) {
   *n_pairs_out = h->n_pairs;
   if (!h->pairs_with_density) h->spl_P.valid = false;
   else if (h->n_pairs == 0) h->spl_P.valid = false;
-  if (h->xo_launch_policy == 2) GNXCHK(gnx_xo_launch_pending(h, GNX_PC_XO_P2));
+  if (h->xo_launch_late) GNXCHK(gnx_xo_launch_pending(h, GNX_PC_XO_P2));
   return 0;
 }
 
@@ -2236,13 +2129,12 @@ struct OffP {
   const uint8_t* dom;
   GnxBinP bins;          // the individuals' density bins (the newborns join the adults)
   const GnxDD* dd;       // device-driven step: N, B, first id and step index from the device
-  // the parents' alleles at the selected loci: s.tb, or - the cell sort's permutation of that
-  // column is still on its way (GNX_PERMUTE_REST_AT=2) - the buffer it is permuted FROM, through
-  // the sort's permutation (pmap[sorted slot] = the slot before the sort)
+  // the parents' alleles at the selected loci (s.tb), read through pmap when that is not null
+  // (never: the launchers that permuted the column late were measured and removed)
   const uint64_t* ptb;
   const int32_t* pmap;
-  // the births launched AHEAD of the host's read-back of the pair count (gnx_l_offspring_ahead):
-  // the grid covers what the population could bear, the pair count comes from the device
+  // not null: the pair count comes from this device word (never: the births launched ahead of
+  // the host's read-back were measured and removed, profiles/r06_ab_runs.txt)
   const int32_t* P_dev;
 };
 
@@ -2518,8 +2410,7 @@ static OffP gnx_make_offp(gnx_state* h, bool genomes, bool tiled, int64_t id_bas
   // (tiles too since round 4: an offspring whose mate is a ghost gets its tables and phenotype
   // from the mate's resident slot - garbage - and again, from its finished row, once the remote
   // gamete is in: gnx_tile_finish_births)
-  static const bool tile_fuse = !(getenv("GNX_TILE_FUSE_TB") && atoi(getenv("GNX_TILE_FUSE_TB")) == 0);
-  Q.fuse_tb = (genomes && (!tiled || tile_fuse)) ? 1 : 0;
+  Q.fuse_tb = genomes ? 1 : 0;
   Q.TW = h->TW;
   Q.path_sel = h->path_sel;
   Q.dom = h->dom;
@@ -2527,63 +2418,7 @@ static OffP gnx_make_offp(gnx_state* h, bool genomes, bool tiled, int64_t id_bas
   Q.P_dev = nullptr;
   Q.ptb = h->soa[h->cur].tb;
   Q.pmap = nullptr;
-  if (h->perm_rest_late && (h->perm_rest_inflight || h->perm_rest_pending)) {
-    Q.ptb = h->perm_rest_a.tb;
-    Q.pmap = h->perm[1];
-  }
   return Q;
-}
-
-// gnx_step, one device, a fixed number of births per pair: the births kernel goes on the stream
-// BEFORE the host has read the pair count back (gnx_l_find_pairs_finish).  The host's wait for
-// the count and its enqueueing of everything behind the births then run while k_offspring
-// does, instead of leaving the chip idle between the pair list and the births (~15 us of a
-// 0.55-ms step, profiles/r06_timeline.txt) and again behind them.  The kernel takes the pair
-// count from the device word k_pair_compact leaves (cnt_dev[0]); its grid covers the births the
-// population could have at most (every individual the focal one of a pair); the host's checks
-// (capacity, free genome rows) follow in gnx_l_mate once it has the count - a step that does not
-// fit has written nothing by then (the kernel checks the same bounds itself).
-// Same kernel, same arguments as gnx_l_mate's own launch: the reference's order of events
-// (structs/species.py:595-805: pairs, then births) is the stream's.
-int gnx_l_offspring_ahead(gnx_state* h, bool burn, bool inside_enqueue) {
-  // (measured, profiles/r06_ab_runs.txt: 0.544 against 0.542 ms/step - the gap in front of the
-  // births is not the host's wait but the event hand-over to the side stream that precedes them;
-  // parity-green, kept behind GNX_BIRTHS_AHEAD=1.  =2: right behind the pair list, in front of
-  // that hand-over - gnx_l_find_pairs_enqueue)
-  static const int mode = getenv("GNX_BIRTHS_AHEAD") ? atoi(getenv("GNX_BIRTHS_AHEAD")) : 0;
-  if (h->births_ahead) return 0;               // (already on the stream)
-  const bool on = inside_enqueue ? mode == 2 : mode == 1;
-  if (inside_enqueue) h->pairs_wait = true;    // (the enqueue sets it at its end: the test below)
-  h->births_ahead = false;
-  const gnx_config& c = h->cfg;
-  const gnx_species_params& sp = h->sp;
-  if (!on || !h->pairs_wait || h->tiled || h->tile2_mode || !sp.n_births_fixed ||
-      sp.n_births_lambda < 1 || sp.mating_radius < 0 || h->N == 0 || h->dd_active ||
-      (h->profiling && h->profile_only < 0))        // (every family timed: the births by themselves)
-    return 0;
-  const int64_t lam = (int64_t)sp.n_births_lambda;
-  const int64_t room = c.cap_inds - h->N;
-  if (room <= 0) return 0;
-  GNXCHK(gnx_xo_flush_deferred(h));
-  const bool genomes = !burn && c.L > 0 && h->genomes_assigned;
-  GnxSoA s = h->soa[h->cur];
-  // (tile-major offspring ids: k_pair_compact's classification, flags only - gnx_l_mate repeats it)
-  if (h->id_order == 1) GNXCHK(gnx_l_pair_cls(h, -1, true));
-  OffP Q = gnx_make_offp(h, genomes, false, -1, 0);
-  Q.P_dev = h->cnt_dev;
-  if (gnx_fused_bins(h) && h->fb_adults && h->fb_count == h->N) Q.bins.bins = h->fb[h->fb_cur];
-  int32_t* ord_tail = nullptr;
-  if (h->pair_goff_ready && h->pair_goff_local_base && h->ord_mode && h->ord_valid && h->ord_n == h->N)
-    ord_tail = h->ord[h->ord_cur] + h->ord_n;
-  GnxGoff gf{};
-  if (h->pair_goff_ready) gf = gnx_goff_vt(h);
-  const int64_t bound = std::min(h->N * lam, room);
-  hipLaunchKernelGGL(k_offspring, dim3(gnx_grid(bound, 256)), dim3(256), 0, h->stream, Q, s, h->rast,
-                     h->pairs, h->off_pair, h->boff, gf, h->off_parent, h->off_keys, h->off_start,
-                     GnxReq{}, gnx_trait_tab(h), ord_tail);
-  HIPCHK(hipGetLastError());
-  h->births_ahead = true;
-  return 0;
 }
 
 // Appends the offspring of the current pair list (or, inject: of the uploaded
@@ -2597,12 +2432,6 @@ int gnx_l_mate(gnx_state* h, bool burn, bool inject, int64_t B_inject, int64_t* 
   *births_out = 0;
   int64_t B = 0;
   bool ord_tail_used = false;
-  const bool ahead = h->births_ahead;       // k_offspring is already on the stream (gnx_l_offspring_ahead)
-  h->births_ahead = false;
-  if (ahead && (tiled || inject)) {
-    gnx_set_error("births launched ahead of a tiled / injected mating");
-    return 1;
-  }
   GNXCHK(gnx_xo_flush_deferred(h));
   bool genomes = !burn && c.L > 0 && h->genomes_assigned;
   if (inject) {
@@ -2664,17 +2493,12 @@ int gnx_l_mate(gnx_state* h, bool burn, bool inject, int64_t B_inject, int64_t* 
     GnxGoff gf{};
     if (h->pair_goff_ready) gf = gnx_goff_vt(h);
     else if (tiled && !h->pair_goff_local) gf.goff = h->pair_goff;
-    if (!ahead) {
-      gnx_time_begin(h);
-      hipLaunchKernelGGL(k_offspring, dim3(gnx_grid(B, 256)), dim3(256), 0, h->stream, Q, s, h->rast,
-                         h->pairs, h->off_pair, h->boff, gf,
-                         h->off_parent, h->off_keys, h->off_start, rq, gnx_trait_tab(h), ord_tail);
-      gnx_time_end(h, GNX_K_OFFSPRING, (double)B * (60.0 + 8.0 * c.n_layers + 48.0 * h->TW +
-                                                    4.0 * c.n_traits));
-    } else if (h->profiling && h->profile_only < 0) {
-      h->timers[GNX_K_OFFSPRING].bytes += (double)B * (60.0 + 8.0 * c.n_layers + 48.0 * h->TW +
-                                                       4.0 * c.n_traits);
-    }
+    gnx_time_begin(h);
+    hipLaunchKernelGGL(k_offspring, dim3(gnx_grid(B, 256)), dim3(256), 0, h->stream, Q, s, h->rast,
+                       h->pairs, h->off_pair, h->boff, gf,
+                       h->off_parent, h->off_keys, h->off_start, rq, gnx_trait_tab(h), ord_tail);
+    gnx_time_end(h, GNX_K_OFFSPRING, (double)B * (60.0 + 8.0 * c.n_layers + 48.0 * h->TW +
+                                                  4.0 * c.n_traits));
     if (tiled && genomes) {
       // the number of gamete requests is known before the crossover is launched: the host
       // layer serves the neighbour tiles while the crossover runs.  (tile2: it was counted
@@ -2694,8 +2518,7 @@ int gnx_l_mate(gnx_state* h, bool burn, bool inject, int64_t B_inject, int64_t* 
     // tables; the 25-KB rows are only needed by the NEXT generation's crossover, so on one
     // GPU they are cut after this step's death draws, for the survivors only
     // (gnx_l_mortality), unless somebody asks for them earlier (gnx_xo_join)
-    static const bool tile_fuse = !(getenv("GNX_TILE_FUSE_TB") && atoi(getenv("GNX_TILE_FUSE_TB")) == 0);
-    const bool fused = !inject && (!tiled || tile_fuse);        // k_offspring did both already
+    const bool fused = !inject;        // k_offspring did both already
     if (!fused) GNXCHK(gnx_l_newborn_tb(h, h->N, B));
     const bool defer = h->defer_xo && !inject && h->stream2 != nullptr;
     if (defer) {
@@ -2735,18 +2558,15 @@ int gnx_dd_l_sort(gnx_state* h, int32_t* d_bins, hipStream_t st) {
   GnxSoA a = h->soa[h->cur], b = h->soa[h->cur ^ 1];
   // stable sort of the id-ordered index by cell alone, over the capacity: entries behind the
   // population carry the largest key (k_keys_hist)
-  // GNX_DD_SORT_GEO: 1 (default) the front (keys + histograms) in workgroups of 2 048 keys - three
-  // times the workgroups, 15.8 -> 9.0 us at 10^5 individuals - and the passes in rocPRIM's own
-  // 1024 x 6 tiles (512 x 4 tiles take 16.9 us a pass against 13.7: `2`); 0: both 1024 x 6
-  static const int geo = getenv("GNX_DD_SORT_GEO") ? atoi(getenv("GNX_DD_SORT_GEO")) : 1;
-  const bool small = n_fixed <= (1 << 21);
-  const int geometry = (geo == 2 && small) ? 1 : 0;
+  // the front (keys + histograms) in workgroups of 2 048 keys up to 2^21 slots - three times the
+  // workgroups, 15.8 -> 9.0 us at 10^5 individuals - and the passes in rocPRIM's own 1024 x 6 tiles
+  // (smaller tiles: 16.9 us a pass against 13.7, measured and removed - profiles/HISTORY.md)
+  const int front_geometry = n_fixed <= (1 << 21) ? 1 : 0;
   GNXCHK(gnx_os_keys_hist(h->os_scratch, h->tickets + 3, n_fixed, 0, h->ord[h->ord_cur], h->cell32,
-                          h->keyk[0], h->valk[0], h->key_bits, st, h->dd,
-                          (geo != 0 && small) ? 1 : 0));
+                          h->keyk[0], h->valk[0], h->key_bits, st, h->dd, front_geometry));
   GNXCHK(gnx_os_sort32_ranked(h->os_scratch, h->os_ktmp, h->os_vtmp, h->keyk[0], h->keyk[1],
-                              h->valk[0], h->valk[1], (size_t)n_fixed, h->key_bits, st, geometry));
-  const int64_t wipe_words = (int64_t)gnx_os_words_used((size_t)n_fixed, h->key_bits, geometry);
+                              h->valk[0], h->valk[1], (size_t)n_fixed, h->key_bits, st));
+  const int64_t wipe_words = (int64_t)gnx_os_words_used((size_t)n_fixed, h->key_bits);
   hipLaunchKernelGGL(k_permute, dim3(gnx_grid(n_fixed, 256)), dim3(256), 0, st, n_fixed, c.cap_inds,
                      h->valk[1], a, b, c.n_layers, c.n_traits, a.tb ? 2 * h->TW : 0,
                      (unsigned long long)c.seed, h->tag, (uint4*)h->cand, h->key64[1], 40,
@@ -2769,16 +2589,15 @@ int gnx_dd_l_pairs(gnx_state* h, int32_t* d_bins, hipStream_t st) {
   FocalP fp{cap, nullptr, (float)sp.b, sp.sexed, sp.repro_age[0], 0, h->cfg.seed, h->dd};
   dim3 grid(gnx_grid(cap, FM_PER_BLOCK)), blk(256);
   const uint4* cd = (const uint4*)h->cand;
-  static const int easy = getenv("GNX_FM_EASY") ? std::max(1, atoi(getenv("GNX_FM_EASY"))) : 2;
   if (sp.mate_mode == GNX_MATE_NEAREST)
     hipLaunchKernelGGL(k_find_mates<GNX_MATE_NEAREST>, grid, blk, 0, st, fp, s, cd, h->inv_cs,
-                       h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, easy, h->mate);
+                       h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, GNX_FM_EASY_ROUNDS, h->mate);
   else if (sp.mate_mode == GNX_MATE_INVERSE)
     hipLaunchKernelGGL(k_find_mates<GNX_MATE_INVERSE>, grid, blk, 0, st, fp, s, cd, h->inv_cs,
-                       h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, easy, h->mate);
+                       h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, GNX_FM_EASY_ROUNDS, h->mate);
   else
     hipLaunchKernelGGL(k_find_mates<GNX_MATE_UNIFORM>, grid, blk, 0, st, fp, s, cd, h->inv_cs,
-                       h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, easy, h->mate);
+                       h->cell_start, h->ncx, h->ncy, h->cell_ref, r, r2, GNX_FM_EASY_ROUNDS, h->mate);
   const int nb = (int)((cap + GNX_CB - 1) / GNX_CB);
   PairP pp{cap, nullptr, h->mate, nullptr, (float)sp.b, sp.sexed, sp.repro_age[0], sp.repro_age[1],
            sp.sexed ? 0 : 1, 0, h->cfg.seed, h->dd};

@@ -86,10 +86,7 @@ int gnx_prim_sort64_bits(void* tmp, size_t bytes, const uint64_t* kin, uint64_t*
   // workload (8-bit default config 0.187; 2 / 3 / 4 / 8 / 12 keys per thread 0.191 / 0.166 /
   // 0.154 / 0.151 / 0.167).  Beside a crossover (whole-step overlap) its 1024-thread blocks
   // wait longer for a CU than the default's and the step loses 5-9 %: default digits there.
-  // GNX_SORT_BITS=8 / 10 forces one or the other.
-  static const int forced = getenv("GNX_SORT_BITS") ? atoi(getenv("GNX_SORT_BITS")) : 0;
-  const int digit = forced ? forced : (alone ? 10 : 8);
-  if (digit == 10)
+  if (alone)
     HIPCHK(rocprim::radix_sort_pairs<gnx_sort_config10>(tmp, bytes, kin, kout, vin, vout, n, 0,
                                                         end_bit, s));
   else
@@ -102,9 +99,7 @@ int gnx_prim_sort64_bits(void* tmp, size_t bytes, const uint64_t* kin, uint64_t*
 int gnx_prim_sort32_bits(void* tmp, size_t bytes, const uint32_t* kin, uint32_t* kout,
                          const int32_t* vin, int32_t* vout, size_t n, int end_bit,
                          hipStream_t s, bool alone) {
-  static const int forced = getenv("GNX_SORT_BITS") ? atoi(getenv("GNX_SORT_BITS")) : 0;
-  const int digit = forced ? forced : (alone ? 10 : 8);
-  if (digit == 10)
+  if (alone)
     HIPCHK(rocprim::radix_sort_pairs<gnx_sort_config10>(tmp, bytes, kin, kout, vin, vout, n, 0,
                                                         end_bit, s));
   else
@@ -534,20 +529,17 @@ k_keys_hist(long long N, long long ord_n, const int32_t* __restrict__ ord,
 }
 }  // namespace gnx_os
 
-// tile geometries: 0 = 512 threads x 8 keys (4 096 keys a tile), 1 = 256 x 4 (1 024 keys a tile:
-// four times the workgroups for a sort that is all latency at 10^5 keys); 64-bit keys: 512 x 8
+// the passes' tile: 512 threads x 8 keys (4 096 keys a tile), for 32- and 64-bit keys alike (the
+// only other geometry left is the front's: gnx_os_keys_hist, workgroups of 2 048 keys)
 #define GNX_OS_BIG_BS 512
 #define GNX_OS_BIG_IPT 8
-#define GNX_OS_SMALL_BS 256
-#define GNX_OS_SMALL_IPT 4
 #define GNX_OS_64_BS 512
 #define GNX_OS_64_IPT 8
 
 void gnx_os_digits(int end_bit, int* places, int* rb) { gnx_os::digits(end_bit, places, rb); }
 
-size_t gnx_os_words_used(size_t n, int end_bit, int geometry) {
-  return gnx_os::layout(n, end_bit, geometry == 1 ? GNX_OS_SMALL_BS * GNX_OS_SMALL_IPT
-                                                   : GNX_OS_BIG_BS * GNX_OS_BIG_IPT).words;
+size_t gnx_os_words_used(size_t n, int end_bit) {
+  return gnx_os::layout(n, end_bit, GNX_OS_BIG_BS * GNX_OS_BIG_IPT).words;
 }
 int gnx_os_keys_hist(void* scratch, unsigned int* ticket, int64_t N, int64_t ord_n,
                      const int32_t* ord, const uint32_t* cell32, uint32_t* key, int32_t* val,
@@ -575,10 +567,9 @@ int gnx_os_keys_hist(void* scratch, unsigned int* ticket, int64_t N, int64_t ord
 }
 int gnx_os_sort32_ranked(void* scratch, uint32_t* ktmp, int32_t* vtmp, const uint32_t* kin,
                          uint32_t* kout, const int32_t* vin, int32_t* vout, size_t n, int end_bit,
-                         hipStream_t s, int geometry) {
-  if (geometry == 1)
-    return gnx_os::passes<uint32_t, GNX_OS_SMALL_BS, GNX_OS_SMALL_IPT>(
-        scratch, ktmp, vtmp, kin, kout, vin, vout, n, end_bit, s, false, nullptr, 0, nullptr);
+                         hipStream_t s) {
+  // (passes in smaller tiles for small populations: 16.9 us a pass against 13.7, measured
+  // and removed - profiles/HISTORY.md)
   return gnx_os::passes<uint32_t, GNX_OS_BIG_BS, GNX_OS_BIG_IPT>(
       scratch, ktmp, vtmp, kin, kout, vin, vout, n, end_bit, s, false, nullptr, 0, nullptr);
 }
@@ -613,26 +604,7 @@ int gnx_os_sort64_clean(void* scratch, void* tmp, const uint64_t* kin, uint64_t*
 }
 
 size_t gnx_os_scratch_bytes(size_t n, int end_bit) {
-  size_t w = std::max({gnx_os_words_used(n, end_bit, 0),
-                       // (the small geometry: only ever used below GNX_DD_MAX_CAP slots)
-                       gnx_os_words_used(std::min<size_t>(n, 1u << 21), end_bit, 1)});
-  return w * sizeof(unsigned int);
-}
-
-// generic entry (keys given, nothing counted yet): counts, then the passes; the caller has the
-// scratch zero and wipes gnx_os_scratch_bytes of it afterwards
-int gnx_os_sort32(void* scratch, uint32_t* ktmp, int32_t* vtmp, const uint32_t* kin,
-                  uint32_t* kout, const int32_t* vin, int32_t* vout, size_t n, int end_bit,
-                  hipStream_t s, int variant) {
-  (void)variant;
-  int places, rb;
-  gnx_os::digits(end_bit, &places, &rb);
-  const unsigned int blocks = (unsigned int)std::min<size_t>((n + 4095) / 4096, 1024);
-  hipLaunchKernelGGL((gnx_os::k_hist<uint32_t>), dim3(blocks ? blocks : 1), dim3(512),
-                     (size_t)places * (1u << rb) * 4, s, kin, (unsigned int)n, (uint32_t*)scratch,
-                     places, rb);
-  return gnx_os::passes<uint32_t, GNX_OS_BIG_BS, GNX_OS_BIG_IPT>(
-      scratch, ktmp, vtmp, kin, kout, vin, vout, n, end_bit, s, false, nullptr, 0, nullptr);
+  return gnx_os_words_used(n, end_bit) * sizeof(unsigned int);
 }
 
 // ---------------------------------------------------------------- block-count scan

@@ -422,7 +422,7 @@ extern "C" int gnx_tile_offspring(gnx_state* h, int32_t burn, int64_t id_base,
 
 // The gamete service reads parents' genome blocks.  Last step's deferred crossover, which
 // writes the blocks of last step's surviving newborns (parents already), may still be running
-// on stream2 (gnx_set_crossover_overlap(1), GNX_XO_SORT_WAIT=0, a split launch): the serving
+// on stream2 (gnx_set_crossover_overlap(1), a split launch): the serving
 // stream waits for it unless it IS stream2 (SideStream: in order behind the crossover anyway).
 static int serve_wait_crossover(gnx_state* h, hipStream_t main_stream) {
   if (h->stream == h->stream2 && h->stream2 != nullptr) {
@@ -621,11 +621,7 @@ static int tile_settle_births(gnx_state* h, int32_t burn) {
     // waited for; no join, the other offspring's crossover stays deferred)
     GNXCHK(gnx_l_tb_from_rows(h, h->birth_first_slot, h->n_req, h->req_k, nullptr, false));
     // (everybody else's phenotype came with k_offspring)
-    static const bool tile_fuse = !(getenv("GNX_TILE_FUSE_TB") && atoi(getenv("GNX_TILE_FUSE_TB")) == 0);
-    if (tile_fuse)
-      GNXCHK(gnx_l_phenotype(h, h->birth_first_slot, h->n_req, h->req_k));
-    else
-      GNXCHK(gnx_l_phenotype(h, h->birth_first_slot, B));
+    GNXCHK(gnx_l_phenotype(h, h->birth_first_slot, h->n_req, h->req_k));
   }
   return 0;
 }
@@ -1403,9 +1399,8 @@ extern "C" int gnx_tile2_route_begin(gnx_state* h, int32_t move, void** counts_d
     // the sort's keys as in gnx_step)
     h->move_writes_keys = T == 1 && h->sp.mating_radius >= 0;
     // several tiles: the routing's counting pass rides in the movement kernel (it has the new
-    // positions in registers; k_route<false> read them back: 34 us of a tile-step) - GNX_ROUTE_IN_MOVE=0: off
-    static const bool in_move = !(getenv("GNX_ROUTE_IN_MOVE") && atoi(getenv("GNX_ROUTE_IN_MOVE")) == 0);
-    if (in_move && T > 1 && h->N > 0) {
+    // positions in registers; k_route<false> read them back: 34 us of a tile-step)
+    if (T > 1 && h->N > 0) {
       if (!h->route_geo_dev) HIPCHK(hipMalloc((void**)&h->route_geo_dev, sizeof(RouteGeo)));
       if (h->route_geo_epoch != h->cfg_epoch) {
         RouteGeo g;

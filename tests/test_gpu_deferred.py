@@ -316,8 +316,8 @@ def test_small_path_equals_default_path(variant, monkeypatch):
         monkeypatch.setenv('GNX_DD_GRAPH', '0')
     if variant == 'host_driven_walk':
         # gnx_walk as it takes the metric workload (too large for the device-driven step): gnx_step
-        # per step, every step but the last moving the population for the next one right after
-        # its own death draws, on the uncompacted slots (gnx_l_move_ahead) - same population
+        # per step, every step but the last leaving its dead in place for the next step's cell
+        # sort (gnx_l_mortality_enqueue: lazy) - same population
         monkeypatch.setenv('GNX_DD', '0')
     dense = variant == 'dense'
     a, nat = _model(True, dense=dense, seed=31)

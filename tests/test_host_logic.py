@@ -547,3 +547,25 @@ def test_reference_parameter_files_load_unchanged(rel, tmp_path):
         assert dc._when[-1] == p.model.T - 1
     if 'stats' in p.model:
         assert _StatsCollector('m', p).stats
+
+
+def test_library_env_switches_are_listed_in_design():
+    """Every GNX_* environment variable the native library reads is in DESIGN.md's table of
+    switches (5.3): a variant kept behind a new switch has to be written down there - or, once its
+    measurement is, deleted."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, 'geonomics_amd', 'csrc')
+    read = set()
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith(('.hip', '.h')):
+            with open(os.path.join(csrc, name)) as f:
+                read |= set(re.findall(r'\b(?:getenv|gnx_env_int)\s*\(\s*"(GNX_[A-Z0-9_]+)"', f.read()))
+    assert len(read) >= 10, read              # (the pattern still finds the call sites)
+    with open(os.path.join(root, 'DESIGN.md')) as f:
+        design = f.read()
+    table = design[design.index('### 5.3 Environment switches the library reads'):]
+    table = table[:table.index('\n## ')]
+    listed = set(re.findall(r'^\| `(GNX_[A-Z0-9_]+)` \|', table, re.M))
+    assert read <= listed, 'read under csrc/ but missing from DESIGN.md 5.3: %s' % sorted(read - listed)
+    assert listed <= read, 'listed in DESIGN.md 5.3 but read nowhere under csrc/: %s' % sorted(listed - read)

@@ -3,7 +3,7 @@
 # counters in a run of its own, --kernel-trace only): tools/pmc_kernel.sh <tag> <kernel substring>
 #   -> gpurun_out/<tag>/summary.txt: per launch means of the last 10 launches
 TAG=${1:-pmck}
-KERN=${2:-k_xo_jobs_fused}
+KERN=${2:-k_xo_jobs_lanes}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 export TMPDIR=/tmp
 O=$ROOT/gpurun_out/$TAG
