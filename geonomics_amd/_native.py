@@ -62,7 +62,7 @@ EXPORTS = [
     'gnx_tile_step_begin', 'gnx_tile_step_births', 'gnx_tile_step_end', 'gnx_comm_probe',
     'gnx_tile2_pairs_mode', 'gnx_tile2_pairs_settle', 'gnx_tile2_settle_births',
     'gnx_tile2_vt_counts', 'gnx_tile2_vt_bases', 'gnx_tile_step_abort', 'gnx_comm_info', 'gnx_tile_walk',
-    'gnx_geno_gram', 'gnx_geno_matmul', 'gnx_geno_rmatmul',
+    'gnx_geno_gram', 'gnx_geno_matmul', 'gnx_geno_rmatmul', 'gnx_transplant',
 ]
 
 
@@ -135,7 +135,9 @@ def _arr(a, dtype):
 
 
 class GnxError(RuntimeError):
-    pass
+    """a call into libgnxhip.so failed; `code` is its return code where the caller of the
+    binding kept it (2: slots, genome rows or blocks did not fit)"""
+    code = None
 
 
 class Device:
@@ -1024,6 +1026,30 @@ class Device:
                                             C.c_void_p(Z.data_ptr() or None), C.c_int64(n),
                                             _ptr(s, C.c_int64)))
         return Z
+
+    # -- introductions (csrc/gnx_transplant.hip) ----------------------------------------
+    def transplant(self, src, slots, x, y, first_id):
+        """append the individuals in `slots` of Device `src` (same GPU) to this one at
+        (x[i], y[i]) with ids first_id + i, genomes block for block on the device
+        (gnx_transplant).  -> dict(first_slot, blocks_copied, blocks_linked, collections).
+        Raises GnxError with code 2, and changes nothing, when they do not fit."""
+        if not isinstance(src, Device):
+            raise TypeError('src: a Device')
+        slots = _arr(slots, np.int64).ravel()
+        x = _arr(x, np.float32).ravel()
+        y = _arr(y, np.float32).ravel()
+        if not (x.size == slots.size and y.size == slots.size):
+            raise ValueError('slots, x and y: one entry per newcomer')
+        out = np.zeros(4, np.int64)
+        rc = self.lib.gnx_transplant(self.h, src.h, C.c_int64(slots.size), _ptr(slots, C.c_int64),
+                                     _ptr(x, C.c_float), _ptr(y, C.c_float),
+                                     C.c_int64(int(first_id)), _ptr(out, C.c_int64))
+        if rc:
+            e = GnxError(self.lib.gnx_last_error().decode())
+            e.code = int(rc)
+            raise e
+        return dict(zip(('first_slot', 'blocks_copied', 'blocks_linked', 'collections'),
+                        (int(v) for v in out)))
 
     # -- measurement ---------------------------------------------------------
     def profiling(self, on):

@@ -237,6 +237,36 @@ class Model:
         spp._remove_individuals(individs=individs, n=n, n_left=n_left,
                                 verbose=self._rank == 0)
 
+    def add_individuals(self, n, coords, recip_spp=0, source_spp=None,
+                        source_msprime_params=None, individs=None):
+        """add Individuals of another Species - of this Model (int or str) or of another
+        Model in this process (its Species object) - to `recip_spp` at `coords`: n of them
+        (those with the smallest ids) or the listed `individs` (reference
+        sim/model.py:3228-3335; structs/species.py:1631-2077).  `coords`: one x,y pair for
+        everybody, or n x 2.  An msprime source (`source_msprime_params`) is not part of
+        this build."""
+        import warnings
+        from ..structs.species import Species
+        warnings.warn("add_individuals is new: checked, not yet widely used. Please report "
+                      "anything that looks wrong.")
+        if isinstance(recip_spp, (int, str)):
+            recip_spp = self.comm[self._get_spp_num(recip_spp)]
+        assert recip_spp.burned, ("Individuals cannot be added to a Species that has not "
+                                  "been burned in yet.")
+        assert (source_spp is None) != (source_msprime_params is None), (
+            "the source population is either a Species ('source_spp') or a set of msprime "
+            "arguments ('source_msprime_params'): exactly one of them must be given.")
+        if source_spp is not None:
+            assert isinstance(source_spp, (Species, int, str)) and \
+                not isinstance(source_spp, bool), (
+                    "'source_spp' must be a Species object, or the int or str that names a "
+                    "Species of this Model.")
+            if isinstance(source_spp, (int, str)):
+                source_spp = self.comm[self._get_spp_num(source_spp)]
+        recip_spp._add_individuals(n=n, coords=coords, land=self.land, source_spp=source_spp,
+                                   source_msprime_params=source_msprime_params,
+                                   individs=individs, verbose=self._rank == 0)
+
     def write_tskit_table_collection(self, file_basename, spp=0, sep=','):
         """the spatial pedigree as <basename>_{NODES,EDGES,SITES,MUTATIONS,INDIVIDUALS}.csv
         (reference sim/model.py:3449-3486) and, beside them, tskit's text format

@@ -60,6 +60,96 @@ def _sum_K(land, K_layer_idx, K_factor):
     return float(np.sum(land[K_layer_idx].rast) * K_factor)
 
 
+def _introduction_plan(n, coords, individs, source_ids, land_dim):
+    """Which individuals of a source population an introduction takes and where they go
+    (the argument rules of reference structs/species.py:1650-1680, 1707-1727, 1829-1840).
+    Exactly one of `n` (the n smallest ids: the reference keeps the first n of its id-ordered
+    dict) and `individs` (taken in ascending id order) is given; `coords` is one x,y pair for
+    everybody or one pair each, the i-th chosen individual gets the i-th pair; every
+    coordinate lies within [0, dim - 0.001].  Needs no device.
+    -> (chosen source ids int64 [n] ascending, coords float32 [n][2])"""
+    source_ids = np.sort(np.asarray(source_ids, dtype=np.int64).ravel())
+    assert (n is None) != (individs is None), (
+        "With a Species as the source population exactly one of 'n' and 'individs' must be "
+        "given.")
+    if individs is None:
+        assert isinstance(n, (int, np.integer)) and not isinstance(n, bool) and n >= 0, (
+            "'n' must be a non-negative int.")
+        n = int(n)
+        assert n <= source_ids.size, (
+            "'n' must not exceed the size of the source population (%i)." % source_ids.size)
+        chosen = source_ids[:n].copy()
+    else:
+        chosen = np.asarray(individs, dtype=np.int64).ravel()
+        assert np.unique(chosen).size == chosen.size, (
+            "'individs' lists an Individual more than once.")
+        assert np.isin(chosen, source_ids).all(), (
+            "'individs' holds indices of Individuals that do not exist in the source "
+            "population.")
+        chosen = np.sort(chosen)
+        n = int(chosen.size)
+    xy = np.atleast_2d(np.asarray(coords, dtype=np.float64))
+    assert xy.shape in [(1, 2), (n, 2)], (
+        "'coords' must be a single x,y pair (everybody is introduced there) or an n x 2 "
+        "array of x,y pairs, one per introduced Individual.")
+    if xy.shape != (n, 2):
+        xy = np.repeat(xy, n, axis=0)
+    # (the starting coordinates stay 0.001 below the dimensions too; dims are [x, y])
+    assert ((xy >= 0).all() and (xy[:, 0] <= land_dim[0] - 0.001).all() and
+            (xy[:, 1] <= land_dim[1] - 0.001).all()), (
+        "'coords' must lie on the recipient Species' Landscape: x within "
+        "[0, %g] and y within [0, %g]." % (land_dim[0] - 0.001, land_dim[1] - 0.001))
+    return chosen, xy.astype(np.float32)
+
+
+_INTRO_SPP_ATTRS = ('K_layer', 'selection', 'sex_ratio', 'move')
+_INTRO_GEN_ARCH_ATTRS = ('sex', 'use_tskit', 'x')
+_INTRO_RECOMB_ATTRS = ('_rates', '_r_distr_alpha', '_r_distr_beta', '_jitter_breakpoints')
+_INTRO_TRAIT_ATTRS = ('name', 'phi', 'lyr_num', 'max_alpha_mag', 'gamma', 'univ_adv')
+
+
+def _same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and bool(np.all(a == b))
+
+
+def _check_introduction_compat(recip, source):
+    """The attributes that must agree between the recipient and the source of an
+    introduction (reference structs/species.py:1729-1821; the Traits' loop there names a
+    list that does not exist - this is what it means to do).  Mutation rates, dominance,
+    carrying capacities and the neutral / deleterious loci may differ, as there."""
+    for attr in _INTRO_SPP_ATTRS:
+        assert _same(getattr(source, attr, None), getattr(recip, attr, None)), (
+            "the source and the recipient Species must have the same '%s'" % attr)
+    rga, sga = recip.gen_arch, source.gen_arch
+    assert (rga is None) == (sga is None), (
+        "the source and the recipient Species must both have a genome, or neither.")
+    if rga is None:
+        return
+    assert sga.L == rga.L, ("the source Species' genome must be as long as the recipient's.")
+    for attr in _INTRO_GEN_ARCH_ATTRS:
+        assert _same(getattr(sga, attr, None), getattr(rga, attr, None)), (
+            "the GenomicArchitectures of the source and the recipient Species must have "
+            "the same '%s'" % attr)
+    for attr in _INTRO_RECOMB_ATTRS:
+        assert _same(getattr(sga.recombinations, attr, None),
+                     getattr(rga.recombinations, attr, None)), (
+            "the Recombinations of the source and the recipient Species must have the "
+            "same '%s'" % attr)
+    if rga.traits is None:
+        assert sga.traits is None, ("Individuals of a Species with Traits cannot be added "
+                                    "to a Species without them.")
+        return
+    assert sga.traits is not None and len(sga.traits) == len(rga.traits), (
+        "the source Species must have as many Traits as the recipient.")
+    for t, trt in rga.traits.items():
+        assert t in sga.traits, "the source Species has no Trait %s" % (t,)
+        for attr in _INTRO_TRAIT_ATTRS:
+            assert _same(getattr(trt, attr), getattr(sga.traits[t], attr)), (
+                "'%s' of Trait %s must be the same in the source and the recipient Species."
+                % (attr, t))
+
+
 class Species:
     def __init__(self, name, idx, land, spp_params, genomic_architecture=None,
                  seed=0, device=0, rng=None):
@@ -628,6 +718,55 @@ class Species:
             print('\n%i Individuals successfully removed.\n' % individs.size)
         if check_extinct and self._check_extinct():
             self.extinct = True
+
+    def _add_individuals(self, n, coords, land=None, source_spp=None,
+                         source_msprime_params=None, individs=None, verbose=True):
+        """individuals of another Species introduced into this one (reference
+        structs/species.py:1631-2077): the chosen source individuals, in ascending id order,
+        get coords[i] and the ids max_ind_idx + 1 + i; age, sex and genome travel (on the
+        device, block for block: gnx_transplant), e, phenotype and fitness are recomputed
+        here.  Nt, n_births and n_deaths are not touched, as there."""
+        if source_spp is None and source_msprime_params is not None:
+            raise NotImplementedError(
+                'add_individuals from an msprime simulation (source_msprime_params): msprime '
+                'is outside this build (DESIGN section 7); simulate the source population '
+                'with a second Model and pass its Species as source_spp')
+        assert isinstance(source_spp, Species), (
+            "'source_spp' must be another Species object.")
+        warnings.warn(
+            "Individuals of one Species are being introduced into another. Attributes of the "
+            "Species, GenomicArchitectures and Traits that cannot differ are checked, but "
+            "those whose agreement depends on the scenario (mutational parameters, carrying "
+            "capacities, ...) may differ between source and recipient, and an unintended "
+            "difference there goes unnoticed and can give misleading results. Check your "
+            "set-up with care.")
+        if getattr(self, '_comm', None) is not None or getattr(source_spp, '_comm', None) is not None:
+            raise NotImplementedError('add_individuals with a Species tiled over several GPUs '
+                                      'is not implemented; run the model on one GPU')
+        if self._tt is not None or source_spp._tt is not None:
+            raise NotImplementedError(
+                "add_individuals with a Species that records a pedigree ('use_tskit': True): "
+                "the tree-sequence tables take one founder cohort and are not merged")
+        _check_introduction_compat(self, source_spp)
+        src_ids = source_spp._dev.download(nat.F_ID)
+        chosen, xy = _introduction_plan(n, coords, individs, src_ids, self._land_dim)
+        order = np.argsort(src_ids, kind='stable')
+        slots = order[np.searchsorted(src_ids[order], chosen)].astype(np.int64)
+        for attempt in range(8):
+            try:
+                self._dev.transplant(source_spp._dev, slots, xy[:, 0], xy[:, 1],
+                                     self.max_ind_idx + 1)
+                break
+            except nat.GnxError as e:
+                # slots, genome rows or blocks did not fit and nothing changed: a larger
+                # device state and the same call again, as for births (_do_pop_dynamics)
+                if e.code != 2 or attempt == 7:
+                    raise
+                self._grow_device()
+        self.max_ind_idx += int(chosen.size)
+        if verbose:
+            print("\n%i Individuals successfully added to Species %i ('%s').\n"
+                  % (chosen.size, self.idx, self.name))
 
     # -- burn-in spatial test (reference sim/burnin.py:21-91) -------------------------
     def _spatial_update(self):

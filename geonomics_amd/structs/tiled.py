@@ -50,6 +50,11 @@ class TiledSpecies(Species):
         raise NotImplementedError('genetic distances of a Species tiled over several GPUs are '
                                   'not implemented; run the model on one GPU')
 
+    # -- introductions: not over tiles (the newcomers would have to be routed to their tiles)
+    def _add_individuals(self, *args, **kw):
+        raise NotImplementedError('add_individuals with a Species tiled over several GPUs is '
+                                  'not implemented; run the model on one GPU')
+
     # -- construction -----------------------------------------------------------------
     def _capacities(self, cap, N0):
         """Every rank draws the whole initial population before keeping its tile, so the

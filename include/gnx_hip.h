@@ -635,6 +635,20 @@ int gnx_geno_matmul(gnx_state* h, int32_t k, const float* M, float* Y, int64_t n
 int gnx_geno_rmatmul(gnx_state* h, int32_t k, const float* Y, float* Z, int64_t n,
                      const int64_t* slots);
 
+/* ---- introductions (csrc/gnx_transplant.hip) ------------------------------------------ */
+/* Species._add_individuals with a Species as the source (structs/species.py:1631-2077):
+ * n individuals of src, in the order of src_slots, appended to dst at (x[i], y[i]) with ids
+ * first_id + i; age and sex travel, genomes travel bit for bit, e / selected-locus tables /
+ * phenotype / fitness are recomputed from dst's rasters and traits.
+ * out[4] = first new slot, distinct physical blocks copied, logical blocks linked,
+ * collections run in dst.  Returns 2 (dst unchanged) when slots, rows or blocks do not fit.
+ * Both handles live on one device, hold no ghosts, have the same L and block geometry and
+ * (L > 0) assigned genomes; first_id > dst's largest id; slots are distinct living slots of
+ * src; coordinates lie on dst's landscape.  A block that several newcomers share in src is
+ * copied once and shared in dst; src is only read.                                        */
+int gnx_transplant(gnx_state* dst, gnx_state* src, int64_t n, const int64_t* src_slots,
+                   const float* x, const float* y, int64_t first_id, int64_t* out);
+
 /* ---- measurement ------------------------------------------------------------ */
 int gnx_profiling(gnx_state* h, int32_t on);
 /* accumulated HIP-event time (ms) and launch count of one kernel family,
