@@ -63,6 +63,7 @@ EXPORTS = [
     'gnx_tile2_pairs_mode', 'gnx_tile2_pairs_settle', 'gnx_tile2_settle_births',
     'gnx_tile2_vt_counts', 'gnx_tile2_vt_bases', 'gnx_tile_step_abort', 'gnx_comm_info', 'gnx_tile_walk',
     'gnx_geno_gram', 'gnx_geno_matmul', 'gnx_geno_rmatmul', 'gnx_transplant',
+    'gnx_geno_locus_gram', 'gnx_geno_locus_cross',
 ]
 
 
@@ -1026,6 +1027,36 @@ class Device:
                                             C.c_void_p(Z.data_ptr() or None), C.c_int64(n),
                                             _ptr(s, C.c_int64)))
         return Z
+
+    # -- genotype-environment association (csrc/gnx_gea.hip) ----------------------------
+    def geno_locus_gram(self, loci, slots=None):
+        """C = D^T D (int64 [n_loci][n_loci]) and s = D^T 1 (int64 [n_loci]) of the dosages
+        of `slots` (all living slots by default) at `loci` (ascending, distinct, up to
+        8192), exact"""
+        loci = _arr(loci, np.int32).ravel()
+        s, n = self._geno_slots(slots)
+        m = int(loci.size) if 1 <= loci.size <= 8192 else 0    # the library refuses the rest
+        Cm = np.zeros((m, m), np.int64)
+        cs = np.zeros(m, np.int64)
+        self._chk(self.lib.gnx_geno_locus_gram(self.h, int(loci.size), _ptr(loci, C.c_int32),
+                                               C.c_int64(n), _ptr(s, C.c_int64),
+                                               _ptr(Cm, C.c_int64), _ptr(cs, C.c_int64)))
+        return Cm, cs
+
+    def geno_locus_cross(self, loci, lyr, slots=None):
+        """D^T Z [n_loci][3], Z^T Z [3][3], Z^T 1 [3] in fp64, Z = [e[:, lyr], x, y] of
+        `slots` as the device holds them (nothing is uploaded)"""
+        loci = _arr(loci, np.int32).ravel()
+        s, n = self._geno_slots(slots)
+        m = int(loci.size) if 1 <= loci.size <= 8192 else 0
+        DtZ = np.zeros((m, 3), np.float64)
+        ZtZ = np.zeros((3, 3), np.float64)
+        Zt1 = np.zeros(3, np.float64)
+        self._chk(self.lib.gnx_geno_locus_cross(self.h, int(loci.size), _ptr(loci, C.c_int32),
+                                                int(lyr), C.c_int64(n), _ptr(s, C.c_int64),
+                                                _ptr(DtZ, C.c_double), _ptr(ZtZ, C.c_double),
+                                                _ptr(Zt1, C.c_double)))
+        return DtZ, ZtZ, Zt1
 
     # -- introductions (csrc/gnx_transplant.hip) ----------------------------------------
     def transplant(self, src, slots, x, y, first_id):

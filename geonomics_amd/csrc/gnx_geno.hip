@@ -10,82 +10,13 @@
 // The products use plain fp32 FMAs: d * m is exact, so each output is an fp32 sum of exact
 // products and meets the any-order bound of DESIGN.md (and is exact for integer inputs whose
 // absolute sums stay below 2^24).  Rows follow the order of the slots given.
-#include <algorithm>
-#include "gnx_internal.h"
-
-typedef unsigned long long u64;
-
-namespace {
-
-// device scratch of one call, freed on every exit
-struct Scratch {
-  std::vector<void*> p;
-  ~Scratch() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <class T>
-  int get(T** out, size_t count) {
-    *out = nullptr;
-    if (hipMalloc((void**)out, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-      gnx_set_error("gnx_geno: out of device memory (%zu bytes)", count * sizeof(T));
-      return 1;
-    }
-    p.push_back(*out);
-    return 0;
-  }
-};
-
-// what every entry point checks first: genomes, no ghosts (tiles), the deferred crossover
-// joined (the newest offspring's genomes are written) and the living in slots [0, N)
-int geno_ready(gnx_state* h, const char* who) {
-  if (h->cfg.L == 0 || !h->genomes_assigned) {
-    gnx_set_error("%s: genomes not assigned", who);
-    return 1;
-  }
-  if (h->n_ghost > 0) {
-    gnx_set_error("%s: the handle holds ghost records (a tile): not supported", who);
-    return 1;
-  }
-  GNXCHK(gnx_xo_join(h));
-  GNXCHK(gnx_l_make_dense(h));
-  return 0;
-}
-
-}  // namespace
+#include "gnx_geno.h"
 
 __global__ void k_geno_rows(int64_t n, const int64_t* __restrict__ slots,
                             const int32_t* __restrict__ grow, int32_t* __restrict__ rows) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) rows[i] = grow[slots ? slots[i] : i];
 }
-
-namespace {
-// the slots' physical genome rows on the device; slots == null: all living slots (n == N)
-int geno_rows(gnx_state* h, const char* who, int64_t n, const int64_t* slots, Scratch& s,
-              int32_t** d_rows) {
-  if (!slots && n != h->N) {
-    gnx_set_error("%s: n = %lld but %lld individuals are alive (slots == null)", who,
-                  (long long)n, (long long)h->N);
-    return 1;
-  }
-  for (int64_t i = 0; slots && i < n; ++i)
-    if (slots[i] < 0 || slots[i] >= h->N) {
-      gnx_set_error("%s: slot out of range", who);
-      return 1;
-    }
-  int64_t* d_slots = nullptr;
-  GNXCHK(s.get(d_rows, (size_t)n));
-  if (slots && n > 0) {
-    GNXCHK(s.get(&d_slots, (size_t)n));
-    GNXCHK(gnx_h2d(h, d_slots, slots, (size_t)n * sizeof(int64_t)));
-  }
-  if (n > 0)
-    hipLaunchKernelGGL(k_geno_rows, dim3(gnx_grid(n, 256)), dim3(256), 0, h->stream, n, d_slots,
-                       h->soa[h->cur].grow, *d_rows);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-}  // namespace
 
 // ---------------------------------------------------------------- Gram
 // X[i][hom][q] = word widx[q] of row i's homologue, masked (q >= nw and i >= n: 0)
@@ -109,7 +40,6 @@ __global__ void k_geno_gather(int64_t n, int64_t n_pad, int nw, int Wm,
 // one 64 x 64 tile of G per block (upper triangle of tiles only, mirrored on the write);
 // thread (tx, ty) owns rows ty + 16 r and columns tx + 16 c.  LDS: [word][hom][row], 16 words
 // per stage, so consecutive threads read consecutive u64.
-#define GRAM_GK 16
 __global__ void __launch_bounds__(256)
 k_geno_gram(int64_t n, int Wm, const u64* __restrict__ X, int64_t* __restrict__ out) {
   const int ti = blockIdx.y, tj = blockIdx.x;

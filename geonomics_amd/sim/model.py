@@ -20,6 +20,7 @@ import os
 import random
 import sys
 import traceback
+import warnings
 
 import numpy as np
 
@@ -815,3 +816,33 @@ class Model:
         dist_type='gen', biallelic=False) computed on the device: -> (ids, dist [n][n])"""
         spp = self.comm[self._get_spp_num(spp)]
         return spp._calc_genetic_distances(individs=individs, loci=loci)
+
+    def run_gea(self, method='cca', spp=0, trt=0, plot=True, plot_sd=True, scale=3, sd=3,
+                individs=None, loci=None, gea_df=False):
+        """genotype-environment association (reference sim/model.py:2717-2780): for
+        method 'cca', the only one, the canonical correlation analysis genotype ~ env + lat +
+        long of Species._run_cca, computed from cross-products taken on the device.
+        -> dict(ind_df [n][3], loci_df [n_loci][3], var_df [3][3], trait_loci, ids), numpy
+        arrays where the reference has DataFrames; rows of ind_df in ascending-id order (ids).
+        individs and loci (extensions) restrict the analysis; more than 8192 loci need loci.
+        gea_df=True adds the reference's 'gea_df' table ([n][n_loci + 3]: mean genotypes, env,
+        lat, long) - the one thing here that downloads N x L genotypes to the host.
+        This build does not plot: a truthy plot warns and the results are returned all the
+        same; plot_sd, scale and sd only ever shaped the reference's plot.  Initialise torch's
+        device (torch.cuda.init()) before the model is made, as for calc_genetic_PCA."""
+        if not isinstance(method, str) or method.lower() != 'cca':
+            raise ValueError('Invalid GEA method. Valid methods include: cca')
+        spp = self.comm[self._get_spp_num(spp)]
+        trt_num = self._get_trt_num(spp, trt)
+        results = spp._run_cca(trt_num=trt_num, individs=individs, loci=loci)
+        if gea_df:
+            gts = spp._get_genotypes(loci=None if loci is None else np.unique(loci),
+                                     individs=individs, biallelic=False)
+            ids = None if individs is None else np.sort(individs)
+            lyr = spp.gen_arch.traits[trt_num].lyr_num
+            results['gea_df'] = np.column_stack([gts, spp._get_e(lyr_num=lyr, individs=ids),
+                                                 spp._get_coords(individs=ids)])
+        if plot:
+            warnings.warn('run_gea: this build does not plot (plotting is outside the GPU hot '
+                          'path); pass plot=False.  The results are returned.', stacklevel=2)
+        return results

@@ -952,6 +952,57 @@ class Species:
         g = np.diag(G)
         return ids, 0.5 * np.sqrt((g[:, None] + g[None, :] - 2 * G).astype(np.float64))
 
+    # -- genotype-environment association (sim/gea.py; csrc/gnx_gea.hip) -----------------
+    def _gea_products(self, slots, loci, lyr_num):
+        """what sim/gea.cca_from_cross_products takes, from the device: C, s (gnx_geno_locus_gram),
+        DtZ, ZtZ, Zt1 (gnx_geno_locus_cross; Z = [e[:, lyr_num], x, y]) of the individuals in
+        `slots` at `loci`, and matmul(M [n_loci][3]) -> D M [n][3] (gnx_geno_matmul, fp32)"""
+        import torch
+        dev = self._dev
+        Cm, cs = dev.geno_locus_gram(loci, slots)
+        DtZ, ZtZ, Zt1 = dev.geno_locus_cross(loci, lyr_num, slots)
+        tdev = torch.device('cuda', int(dev.cfg.device))
+        loci_t = torch.as_tensor(loci, device=tdev)
+
+        def matmul(M):
+            full = torch.zeros((dev.L, M.shape[1]), dtype=torch.float32, device=tdev)
+            full[loci_t] = torch.as_tensor(M, dtype=torch.float32, device=tdev)
+            return dev.geno_matmul(full, slots).cpu().numpy().astype(np.float64)
+
+        return Cm, cs, DtZ, ZtZ, Zt1, matmul
+
+    def _run_cca(self, trt_num=0, individs=None, loci=None):
+        """Canonical correlation analysis genotype ~ env + lat + long for one Trait (reference
+        structs/species.py:2269-2355: sklearn's CCA(n_components=3) on the table of
+        _make_gea_df, :2218-2266; env = e of the Trait's Layer, lat = x, long = y), from
+        cross-products taken on the device (sim/gea.py): no N x L table leaves the GPU.
+        individs and loci (extensions) restrict the rows and the columns; at most 8192 loci.
+        -> dict(ind_df [n][3] (rows in ascending-id order), loci_df [n_loci][3], var_df [3][3],
+        trait_loci, ids)"""
+        from ..sim import gea as _gea
+        if self.gen_arch is None or self._dev.L == 0:
+            raise ValueError('run_gea: the Species has no genomes (no gen_arch)')
+        traits = self.gen_arch.traits
+        if not traits:
+            raise ValueError('run_gea: the Species has no Traits')
+        if isinstance(trt_num, bool) or trt_num not in traits:
+            raise ValueError('run_gea: no Trait %r (Traits: %s)' % (trt_num, sorted(traits)))
+        if not self.__dict__.get('_genomes_assigned', False):
+            raise ValueError('run_gea: genomes are assigned at the end of the burn-in; '
+                             'burn the model in first')
+        trt = traits[trt_num]
+        loci_u, _ = self._geno_loci(loci)
+        if loci_u is None:
+            loci_u = np.arange(self._dev.L, dtype=np.int64)
+        if loci_u.size > 8192:
+            raise ValueError('run_gea: at most 8192 loci per analysis (the cross-product matrix '
+                             'is n_loci x n_loci), got %d: choose them with loci=...' % loci_u.size)
+        ids, slots = self._geno_sample(individs)
+        prods = self._gea_products(slots, loci_u, int(trt.lyr_num))
+        res = _gea.cca_from_cross_products(*prods[:5], ids.size, prods[5])
+        return dict(ind_df=res['ind_df'], loci_df=res['loci_df'], var_df=res['var_df'],
+                    trait_loci=np.asarray(trt.loci), ids=ids)
+
     def _calc_fitness(self, trait_num=None, set_fit=True):
         """reference ops/selection.py:51-112.  Overall fitness (trait_num None) is what
         the death-probability kernel of the last _do_pop_dynamics stored; the fitness of

@@ -50,6 +50,12 @@ class TiledSpecies(Species):
         raise NotImplementedError('genetic distances of a Species tiled over several GPUs are '
                                   'not implemented; run the model on one GPU')
 
+    # -- GEA: not over tiles (the cross-products add over tiles: one all-reduce of
+    # n_loci x n_loci, then the scores tile by tile)
+    def _run_cca(self, *args, **kw):
+        raise NotImplementedError('run_gea with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
     # -- introductions: not over tiles (the newcomers would have to be routed to their tiles)
     def _add_individuals(self, *args, **kw):
         raise NotImplementedError('add_individuals with a Species tiled over several GPUs is '

@@ -635,6 +635,24 @@ int gnx_geno_matmul(gnx_state* h, int32_t k, const float* M, float* Y, int64_t n
 int gnx_geno_rmatmul(gnx_state* h, int32_t k, const float* Y, float* Z, int64_t n,
                      const int64_t* slots);
 
+/* ---- genotype-environment association (reference sim/model.py:2717-2780 Model.run_gea ->
+ *      structs/species.py:2218-2355 _make_gea_df / _run_cca: the N x L table of mean
+ *      genotypes with env, lat, long on the host, then sklearn's CCA) ------------------------
+ * The cross-products over the individuals that the fit needs (geonomics_amd/sim/gea.py), of
+ * the dosages D at the listed loci (1..8192 of them, ascending and distinct) of the
+ * individuals in `slots` (NULL: all living slots, and n must equal N).  Preconditions as the
+ * calls above.  Outputs are HOST buffers.                                                  */
+/* C = D^T D, int64 [n_loci][n_loci], and s = D^T 1, int64 [n_loci], exact; n <= 2^29
+ * (replaces the genotype columns of _make_gea_df, structs/species.py:2252-2255)           */
+int gnx_geno_locus_gram(gnx_state* h, int32_t n_loci, const int32_t* loci, int64_t n,
+                        const int64_t* slots, int64_t* C, int64_t* s);
+/* D^T Z double [n_loci][3], Z^T Z double [3][3], Z^T 1 double [3] with Z = [e of layer lyr,
+ * x, y] read from the device's own columns (_make_gea_df's env, lat, long,
+ * structs/species.py:2258-2264) and summed in fp64 in a fixed order                        */
+int gnx_geno_locus_cross(gnx_state* h, int32_t n_loci, const int32_t* loci, int32_t lyr,
+                         int64_t n, const int64_t* slots, double* DtZ, double* ZtZ,
+                         double* Zt1);
+
 /* ---- introductions (csrc/gnx_transplant.hip) ------------------------------------------ */
 /* Species._add_individuals with a Species as the source (structs/species.py:1631-2077):
  * n individuals of src, in the order of src_slots, appended to dst at (x[i], y[i]) with ids
