@@ -64,6 +64,7 @@ EXPORTS = [
     'gnx_tile2_vt_counts', 'gnx_tile2_vt_bases', 'gnx_tile_step_abort', 'gnx_comm_info', 'gnx_tile_walk',
     'gnx_geno_gram', 'gnx_geno_matmul', 'gnx_geno_rmatmul', 'gnx_transplant',
     'gnx_geno_locus_gram', 'gnx_geno_locus_cross',
+    'gnx_lineage_trace', 'gnx_lineage_chains', 'gnx_lineage_budget', 'gnx_lineage_info',
 ]
 
 
@@ -1057,6 +1058,86 @@ class Device:
                                                 _ptr(DtZ, C.c_double), _ptr(ZtZ, C.c_double),
                                                 _ptr(Zt1, C.c_double)))
         return DtZ, ZtZ, Zt1
+
+    # -- lineages through the recorded pedigree (csrc/gnx_lineage.hip) -------------------
+    @staticmethod
+    def _ago(v, default, up):
+        """a time-window bound as the int32 the library compares integers with"""
+        if v is None:
+            return default
+        v = float(v)
+        if v != v:
+            raise ValueError('a time-window bound is NaN')
+        v = np.ceil(v) if up else np.floor(v)
+        return int(min(max(v, -2 ** 31), 2 ** 31 - 1))
+
+    def _lineage_args(self, node_tab, birth_t, nodes, loci, t_curr, drop_before_sim,
+                      min_time_ago, max_time_ago):
+        tab = _arr(node_tab, np.int32)
+        bt = _arr(birth_t, np.int32).ravel()
+        if tab.ndim != 2 or tab.shape != (2 * bt.size, 2):
+            raise ValueError('node_tab: int32 [2 n_rows][2] with birth_t [n_rows]')
+        nodes = _arr(nodes, np.int32).ravel()
+        loci = _arr(loci, np.int32).ravel()
+        keep = (tab, bt, nodes, loci)
+        args = (self.h, C.c_int64(bt.size), _ptr(tab, C.c_int32), _ptr(bt, C.c_int32),
+                C.c_int64(nodes.size), _ptr(nodes, C.c_int32), int(loci.size),
+                _ptr(loci, C.c_int32), int(t_curr), int(bool(drop_before_sim)),
+                self._ago(min_time_ago, -2 ** 31, True), self._ago(max_time_ago, 2 ** 31 - 1, False))
+        return keep, args, (int(loci.size), int(nodes.size))
+
+    def lineage_trace(self, node_tab, birth_t, nodes, loci, t_curr, drop_before_sim=True,
+                      min_time_ago=None, max_time_ago=None,
+                      want=('root', 'first', 'last', 'n_kept'), locus_range=True):
+        """gnx_lineage_trace: the lineages of the sample `nodes` at `loci` through the pedigree
+        (TreeTables.node_table()).  -> dict of the int32 [n_loci][n_nodes] arrays named in
+        `want`, plus 'locus_lo' / 'locus_hi' int32 [n_loci] (min / max of `last` over the
+        sample) if locus_range"""
+        bad = set(want) - {'root', 'first', 'last', 'n_kept'}
+        if bad:
+            raise ValueError('want: unknown output %s' % sorted(bad))
+        keep, args, shape = self._lineage_args(node_tab, birth_t, nodes, loci, t_curr,
+                                               drop_before_sim, min_time_ago, max_time_ago)
+        out = {k: np.full(shape, -1, np.int32) for k in ('root', 'first', 'last', 'n_kept')
+               if k in want}
+        if locus_range:
+            out['locus_lo'] = np.zeros(shape[0], np.int32)
+            out['locus_hi'] = np.zeros(shape[0], np.int32)
+        self._chk(self.lib.gnx_lineage_trace(
+            *args, *[_ptr(out.get(k), C.c_int32)
+                     for k in ('root', 'first', 'last', 'n_kept', 'locus_lo', 'locus_hi')]))
+        return out
+
+    def lineage_chains(self, node_tab, birth_t, nodes, loci, t_curr, drop_before_sim=True,
+                       min_time_ago=None, max_time_ago=None, n_kept=None):
+        """gnx_lineage_chains: every kept node of every lineage, youngest first, in CSR form
+        (offsets int64 [n_loci * n_nodes + 1], nodes int32); n_kept: that of a lineage_trace
+        of the same request (taken here if not given)"""
+        if n_kept is None:
+            n_kept = self.lineage_trace(node_tab, birth_t, nodes, loci, t_curr, drop_before_sim,
+                                        min_time_ago, max_time_ago, want=('n_kept',),
+                                        locus_range=False)['n_kept']
+        keep, args, shape = self._lineage_args(node_tab, birth_t, nodes, loci, t_curr,
+                                               drop_before_sim, min_time_ago, max_time_ago)
+        n_kept = np.asarray(n_kept)
+        if n_kept.shape != shape:
+            raise ValueError('n_kept: shape %s, not %s' % (n_kept.shape, shape))
+        offsets = np.zeros(n_kept.size + 1, np.int64)
+        np.cumsum(n_kept.ravel(), dtype=np.int64, out=offsets[1:])
+        chain = np.zeros(int(offsets[-1]), np.int32)
+        self._chk(self.lib.gnx_lineage_chains(*args, _ptr(offsets, C.c_int64),
+                                              _ptr(chain, C.c_int32)))
+        return offsets, chain
+
+    def lineage_budget(self, n_bytes):
+        """bytes of output per launch of the lineage calls (0: the default, 256 MiB)"""
+        self._chk(self.lib.gnx_lineage_budget(self.h, C.c_int64(int(n_bytes))))
+
+    def lineage_info(self):
+        """of the last lineage call: dict(kernel_ms, launches, uploaded)"""
+        ms, n, up = C.c_double(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.gnx_lineage_info(self.h, C.byref(ms), C.byref(n), C.byref(up)))
+        return dict(kernel_ms=ms.value, launches=int(n.value), uploaded=bool(up.value))
 
     # -- introductions (csrc/gnx_transplant.hip) ----------------------------------------
     def transplant(self, src, slots, x, y, first_id):

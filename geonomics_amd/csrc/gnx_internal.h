@@ -344,6 +344,16 @@ struct gnx_state {
   int32_t* bp_loci = nullptr;
   bool sparse_paths = false;
 
+  // lineage requests (gnx_lineage.hip): the device copy of the host's pedigree node table,
+  // kept between calls while nothing is appended to it (rows, checksum of its last rows)
+  int32_t* lin_tab = nullptr;    // [2 * lin_rows][2] {parent row, key * 2 + start}
+  int32_t* lin_bt = nullptr;     // [lin_rows] birth times
+  int64_t lin_rows = 0;
+  uint64_t lin_sum = 0;
+  int64_t lin_budget = 0;        // output bytes per launch (0: the default)
+  double lin_ms = 0.0;           // kernel time, launches and upload of the last call
+  int64_t lin_launches = 0, lin_uploaded = 0;
+
   // traits etc
   GnxTrait traits[GNX_MAX_TRAITS];
   // selected loci: all trait loci concatenated trait-major (n_tl of them), then the

@@ -21,8 +21,82 @@ tskit's own text format, `tskit.load_text` reads it; `write_csv` the per-table C
 Model.write_tskit_table_collection, sim/model.py:3449-3486).  Not kept: the coalescent
 history msprime simulates for the founders (:956-1094) - founders are roots here -
 and periodic simplification (the tables keep every individual that ever lived).
+
+Beside the float edge rows the tables keep the integers they are made from (`node_table`:
+parent row, path key and start homologue per node, birth time per row).  A lineage at a locus
+is a chain of look-ups in them (reference structs/genome.py:1638-1782, there through tskit's
+trees): `trace` / `lineages` walk it in numpy, csrc/gnx_lineage.hip on the device, and
+`lineage_stat_values` holds the reference's four gene-flow statistics (:1803-1871).  Because
+nothing is simplified, a lineage lists EVERY ancestor, not only those tskit's simplification
+would keep for the current sample.
 """
 import numpy as np
+
+
+LINEAGE_STATS = ('dir', 'dist', 'time', 'speed')
+
+
+def lineage_stat_values(stats, t_young, xy_young, t_old, xy_old, n_kept):
+    """the reference's lineage statistics (structs/genome.py:1803-1871) from the youngest and
+    the oldest kept node of each lineage: times [...], locations [..., 2], fp64.  'dir': compass
+    degrees of the displacement FROM the oldest TO the youngest node; 'dist' and 'time':
+    oldest minus youngest; 'speed' = dist / time.  NaN where n_kept < 2 (the reference's None)"""
+    t_young, t_old = np.asarray(t_young, np.float64), np.asarray(t_old, np.float64)
+    xy_young, xy_old = np.asarray(xy_young, np.float64), np.asarray(xy_old, np.float64)
+    ok = np.asarray(n_kept) >= 2
+    out = {}
+    with np.errstate(invalid='ignore', divide='ignore'):
+        x_diff = xy_old[..., 0] - xy_young[..., 0]
+        y_diff = xy_old[..., 1] - xy_young[..., 1]
+        dist = np.sqrt(x_diff ** 2 + y_diff ** 2)
+        time = t_old - t_young
+        for st in stats:
+            if st == 'dir':
+                ang = np.rad2deg(np.arctan2(xy_young[..., 1] - xy_old[..., 1],
+                                            xy_young[..., 0] - xy_old[..., 0]))
+                ang = np.where(ang < 0, ang + 360, ang)
+                v = (-ang + 90) % 360
+            elif st == 'dist':
+                v = dist
+            elif st == 'time':
+                v = time
+            elif st == 'speed':
+                v = dist / time
+            else:
+                raise ValueError('unknown lineage statistic %r' % (st,))
+            out[st] = np.where(ok, v, np.nan)
+    return out
+
+
+def lineage_stats(tt, nodes, first, last, n_kept, t_curr, stats=LINEAGE_STATS, curr_xy=None):
+    """lineage_stat_values of a trace ([n_loci][n_nodes] first / last / n_kept of the sample
+    `nodes`) with the birth times and locations of the tables `tt`; curr_xy [n_nodes][2]: the
+    sample individuals' current locations, used where the sample node itself is the youngest
+    kept node (the reference's use_individs_curr_pos)"""
+    _, bt = tt.node_table()
+    xy = tt._ind_xy[0]
+    nodes = np.asarray(nodes, dtype=np.int64).ravel()
+    first, last, n_kept = np.atleast_2d(first), np.atleast_2d(last), np.atleast_2d(n_kept)
+    if curr_xy is not None:
+        curr_xy = np.asarray(curr_xy, np.float64)
+        used = (first == nodes[None, :]).any(axis=0)
+        if np.isnan(curr_xy[used]).any():
+            raise ValueError('use_individs_curr_pos: a sample node belongs to an individual that '
+                             'is not alive')
+    out = {st: np.empty(first.shape, np.float64) for st in stats}
+    block = max(1, (1 << 22) // max(nodes.size, 1))       # loci per pass: bounded temporaries
+    for i in range(0, first.shape[0], block):
+        sl = slice(i, i + block)
+        f, l = np.maximum(first[sl], 0) >> 1, np.maximum(last[sl], 0) >> 1
+        xy_young = xy[f]
+        if curr_xy is not None:
+            own = first[sl] == nodes[None, :]
+            xy_young = np.where(own[..., None], curr_xy[None, :, :], xy_young)
+        vals = lineage_stat_values(stats, bt[f].astype(np.float64) + t_curr, xy_young,
+                                   bt[l].astype(np.float64) + t_curr, xy[l], n_kept[sl])
+        for st in stats:
+            out[st][sl] = vals[st]
+    return out
 
 
 class TreeTables:
@@ -34,13 +108,17 @@ class TreeTables:
         self._ind_xy = [np.zeros((0, 2), np.float64)]
         self._ind_time = [np.zeros(0, np.float64)]
         self._edges = [np.zeros((0, 4), np.float64)]  # left, right, parent node, child node
+        # the integers the edges are made from (node_table): per node {parent row, key * 2 +
+        # start homologue}, per row the birth time
+        self._nt = [np.zeros((0, 2), np.int32)]
+        self._bt = [np.zeros(0, np.int32)]
         self._founder_g = None                        # int8 [n_founders, L, 2]
         self.n_founders = 0
         self._new_muts = []                           # (locus, individual id, homologue)
 
     # -- building ---------------------------------------------------------------------
     def _flush(self):
-        for name in ('_ind_id', '_ind_xy', '_ind_time', '_edges'):
+        for name in ('_ind_id', '_ind_xy', '_ind_time', '_edges', '_nt', '_bt'):
             chunks = getattr(self, name)
             if len(chunks) > 1:
                 setattr(self, name, [np.concatenate(chunks)])
@@ -57,6 +135,8 @@ class TreeTables:
         self._ind_id.append(ids)
         self._ind_xy.append(np.asarray(xy, dtype=np.float64))
         self._ind_time.append(np.full(ids.size, 1.0))
+        self._nt.append(np.tile(np.array([[-1, 0]], np.int32), (2 * ids.size, 1)))
+        self._bt.append(np.full(ids.size, 1, np.int32))
         self.n_founders = ids.size
         self._founder_g = None if genotypes is None else np.asarray(genotypes, dtype=np.int8)
 
@@ -77,6 +157,9 @@ class TreeTables:
         self._ind_id.append(child)
         self._ind_xy.append(xy.astype(np.float64))
         self._ind_time.append(np.full(child.size, -float(t)))
+        self._nt.append(np.stack([prow.reshape(-1), 2 * keys.reshape(-1).astype(np.int64)
+                                  + starts.reshape(-1).astype(np.int64)], axis=1).astype(np.int32))
+        self._bt.append(np.full(child.size, -int(t), np.int32))
         # one gamete per (offspring, homologue): segments from the path's switch points
         B = child.size
         key = keys.reshape(-1).astype(np.int64)             # [2B], (k, h) -> 2k + h
@@ -101,6 +184,115 @@ class TreeTables:
         """new mutations on this step's offspring (ops/mutation.py:62-131)"""
         for i, l, h in zip(ind_ids, loci, homs):
             self._new_muts.append((int(l), int(i), int(h)))
+
+    # -- lineages ------------------------------------------------------------------------
+    def node_table(self):
+        """(int32 [2 n_rows][2], int32 [n_rows]): for node 2 row + h {row of the parent that
+        gave the gamete (-1: a founder node), path key * 2 + start homologue}, and the rows'
+        birth times as in the nodes table (founders +1, offspring of main step t: -t)"""
+        self._flush()
+        return self._nt[0], self._bt[0]
+
+    def _switches_upto(self, key, locus):
+        """number of switch points <= locus of path `key` (arrays of one shape)"""
+        if self._bp_loci.size == 0:
+            return np.zeros(np.shape(key), np.int64)
+        g = self.__dict__.get('_bp_global')
+        if g is None:                    # switch loci made globally ascending: key * (L + 1) + locus
+            owner = np.repeat(np.arange(self._bp_off.size - 1), np.diff(self._bp_off))
+            g = self._bp_global = owner * (self.L + 1) + self._bp_loci
+        return np.searchsorted(g, key * (self.L + 1) + locus, side='right') - self._bp_off[key]
+
+    @staticmethod
+    def _window(min_time_ago, max_time_ago):
+        lo = -np.inf if min_time_ago is None else min_time_ago
+        hi = np.inf if max_time_ago is None else max_time_ago
+        return lo, hi
+
+    def _walk(self, nodes, loci, t_curr, drop_before_sim, min_time_ago, max_time_ago, visit):
+        """the lineage of every (locus, node), all at once, one generation back per pass:
+        visit(query indices, their current lineage nodes, kept mask) per pass.  -> roots"""
+        nt, bt = self.node_table()
+        nodes = np.asarray(nodes, dtype=np.int64).ravel()
+        loci = np.asarray(loci, dtype=np.int64).ravel()
+        if nodes.size and (nodes.min() < 0 or nodes.max() >= nt.shape[0]):
+            raise ValueError('nodes: node ids in 0..%d' % (nt.shape[0] - 1))
+        if loci.size and (loci.min() < 0 or loci.max() >= self.L):
+            raise ValueError('loci: loci in 0..%d' % (self.L - 1))
+        lo, hi = self._window(min_time_ago, max_time_ago)
+        n = nodes.size
+        cur = np.tile(nodes, loci.size)                     # query q = locus index * n + node index
+        loc = np.repeat(loci, n)
+        root = np.full(cur.size, -1, np.int64)
+        act = np.arange(cur.size)
+        while act.size:
+            c = cur[act]
+            t = bt[c >> 1].astype(np.int64)
+            kept = (t < 0) if drop_before_sim else np.ones(c.size, bool)
+            ago = t + int(t_curr)
+            kept &= (lo <= ago) & (ago <= hi)
+            visit(act, c, kept)
+            prow = nt[c, 0].astype(np.int64)
+            done = prow < 0
+            root[act[done]] = c[done]
+            go = ~done
+            act, c, prow = act[go], c[go], prow[go]
+            ks = nt[c, 1].astype(np.int64)
+            hom = ((ks & 1) + self._switches_upto(ks >> 1, loc[act])) & 1
+            cur[act] = 2 * prow + hom
+        return root
+
+    def trace(self, nodes, loci, t_curr, drop_before_sim=True, min_time_ago=None,
+              max_time_ago=None):
+        """Lineages of the sample `nodes` (2 row + h) at `loci` through the recorded pedigree:
+        the parent homologue at locus l is (start + #{switch points of the path <= l}) mod 2.
+        Kept nodes as the reference keeps them (structs/genome.py:1720-1759): with
+        drop_before_sim only table times < 0 (a node born in step 0 has time 0 and is dropped,
+        as there), then min_time_ago <= time + t_curr <= max_time_ago.
+        -> dict of int32 [n_loci][n_nodes]: root (the founder node reached), first / last (the
+        youngest / oldest kept node, -1 if none), n_kept"""
+        nodes = np.asarray(nodes, dtype=np.int64).ravel()
+        loci = np.asarray(loci, dtype=np.int64).ravel()
+        nq = nodes.size * loci.size
+        first = np.full(nq, -1, np.int64)
+        last = np.full(nq, -1, np.int64)
+        n_kept = np.zeros(nq, np.int64)
+
+        def visit(q, c, kept):
+            q, c = q[kept], c[kept]
+            new = n_kept[q] == 0
+            first[q[new]] = c[new]
+            last[q] = c
+            n_kept[q] += 1
+
+        root = self._walk(nodes, loci, t_curr, drop_before_sim, min_time_ago, max_time_ago,
+                          visit)
+        shape = (loci.size, nodes.size)
+        return dict(root=root.astype(np.int32).reshape(shape),
+                    first=first.astype(np.int32).reshape(shape),
+                    last=last.astype(np.int32).reshape(shape),
+                    n_kept=n_kept.astype(np.int32).reshape(shape))
+
+    def lineages(self, nodes, loci, t_curr, drop_before_sim=True, min_time_ago=None,
+                 max_time_ago=None):
+        """the kept nodes of every lineage, youngest first, in CSR form: (offsets int64
+        [n_loci * n_nodes + 1], nodes int32); query (locus index i, node index j) is
+        i * n_nodes + j"""
+        nodes = np.asarray(nodes, dtype=np.int64).ravel()
+        loci = np.asarray(loci, dtype=np.int64).ravel()
+        qs, cs = [], []
+
+        def visit(q, c, kept):
+            qs.append(q[kept])
+            cs.append(c[kept])
+
+        self._walk(nodes, loci, t_curr, drop_before_sim, min_time_ago, max_time_ago, visit)
+        q = np.concatenate(qs) if qs else np.zeros(0, np.int64)
+        c = np.concatenate(cs) if cs else np.zeros(0, np.int64)
+        order = np.argsort(q, kind='stable')               # passes go back in time: youngest first
+        offsets = np.zeros(nodes.size * loci.size + 1, np.int64)
+        np.cumsum(np.bincount(q, minlength=nodes.size * loci.size), out=offsets[1:])
+        return offsets, c[order].astype(np.int32)
 
     # -- tables ------------------------------------------------------------------------
     def tables(self):

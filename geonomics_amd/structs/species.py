@@ -1003,6 +1003,159 @@ class Species:
         return dict(ind_df=res['ind_df'], loci_df=res['loci_df'], var_df=res['var_df'],
                     trait_loci=np.asarray(trt.loci), ids=ids)
 
+    # -- lineages through the recorded pedigree (structs/pedigree.py; csrc/gnx_lineage.hip) ----
+    # The reference simplifies its tables with tskit's default, which drops unary nodes: its
+    # lineage at a locus lists only the ancestors that survive simplification for the current
+    # sample.  The pedigree here is not simplified (tskit is outside this build), so a lineage
+    # lists EVERY ancestor.  _check_coalescence is the same either way (two lineages share
+    # their oldest in-simulation node exactly when they coalesce inside the simulation); the
+    # statistics are taken to the oldest in-simulation ancestor of the full pedigree, and no
+    # parity with tskit's simplification is claimed.
+    _LINEAGE_DICT_MAX = 2000000          # chain entries _get_lineage_dicts turns into dicts
+
+    def _lineage_request(self, individs, nodes, loci, who):
+        """(the TreeTables, sample node ids int64, loci int64) of a lineage request"""
+        if self._tt is None:
+            raise ValueError("%s: no pedigree was recorded for this Species ('use_tskit' False, "
+                             "or the genomes were not assigned yet)" % who)
+        tt = self._tt
+        if nodes is None:
+            if individs is None:
+                ids, order = self._ids_sorted()
+                ids = ids[order]
+            else:
+                ids = np.asarray(individs, dtype=np.int64).ravel()
+            rows = np.searchsorted(tt.ids, ids)
+            if ids.size and not (tt.ids[np.minimum(rows, tt.ids.size - 1)] == ids).all():
+                raise ValueError('%s: individs holds ids the pedigree does not know' % who)
+            nodes = (2 * rows[:, None] + np.arange(2)[None, :]).ravel()
+        nodes = np.asarray(nodes, dtype=np.int64).ravel()
+        if nodes.size == 0:
+            raise ValueError('%s: no sample nodes' % who)
+        if nodes.min() < 0 or nodes.max() >= 2 * tt.ids.size:
+            raise ValueError('%s: nodes are node ids of the pedigree tables, 0..%d'
+                             % (who, 2 * tt.ids.size - 1))
+        L = self.gen_arch.L
+        loci = np.arange(L, dtype=np.int64) if loci is None else \
+            np.asarray(loci, dtype=np.int64).ravel()
+        if loci.size == 0 or loci.min() < 0 or loci.max() >= L:
+            raise ValueError('%s: loci: a non-empty list of loci in 0..%d' % (who, L - 1))
+        return tt, nodes, loci
+
+    def _lineage_curr_xy(self, tt, nodes):
+        """current x, y [n][2] of the sample nodes' individuals, read from the device columns
+        (as _get_coords); NaN rows for individuals that are not alive"""
+        ids, order = self._ids_sorted()
+        ids = ids[order]
+        xy = np.stack([self._field(nat.F_X)[order].astype(np.float64),
+                       self._field(nat.F_Y)[order].astype(np.float64)], axis=1)
+        want = tt.ids[nodes >> 1]
+        pos = np.minimum(np.searchsorted(ids, want), max(ids.size - 1, 0))
+        out = np.full((nodes.size, 2), np.nan)
+        alive = ids[pos] == want if ids.size else np.zeros(nodes.size, bool)
+        out[alive] = xy[pos[alive]]
+        return out
+
+    def _get_lineage_dicts(self, loci, nodes=None, drop_before_sim=True,
+                           time_before_present=True, use_individs_curr_pos=True,
+                           max_time_ago=None, min_time_ago=None):
+        """{locus: {sample node: {lineage node: (birth time, array([x, y]))}}}, youngest node
+        first (reference structs/species.py:1242-1276, structs/genome.py:1638-1760), the chains
+        walked on the device (gnx_lineage_chains).  Node ids are those of this Species'
+        pedigree tables (2 * row + homologue); `nodes` defaults to both nodes of every living
+        individual in ascending id order.  Times are time + t if time_before_present, and the
+        window min_time_ago..max_time_ago applies to the times as returned, as there.
+        use_individs_curr_pos puts the individual's current x, y (device columns) in the
+        sample node's own entry when that entry is among the kept nodes; the reference raises
+        KeyError when it is not, here the dict is left as it is.  The lineages list every
+        ancestor: the pedigree is not simplified (see the comment above).  Meant for
+        plotting-sized requests: above _LINEAGE_DICT_MAX chain entries it raises ValueError - use
+        _calc_lineage_stats(as_arrays=True) or _check_coalescence."""
+        who = '_get_lineage_dicts'
+        tt, nodes, loci = self._lineage_request(None, nodes, loci, who)
+        lo, hi = min_time_ago, max_time_ago
+        if not time_before_present:           # the window is on the raw table times then
+            lo = None if lo is None else lo + self.t
+            hi = None if hi is None else hi + self.t
+        tab, bt = tt.node_table()
+        kw = dict(drop_before_sim=drop_before_sim, min_time_ago=lo, max_time_ago=hi)
+        n_kept = self._dev.lineage_trace(tab, bt, nodes, loci, self.t, want=('n_kept',),
+                                         locus_range=False, **kw)['n_kept']
+        total = int(n_kept.sum(dtype=np.int64))
+        if total > self._LINEAGE_DICT_MAX:
+            raise ValueError('%s: %d lineage entries (more than %d): nested dicts are for '
+                             'plotting-sized requests; use _calc_lineage_stats(as_arrays=True) '
+                             'or _check_coalescence' % (who, total, self._LINEAGE_DICT_MAX))
+        off, chain = self._dev.lineage_chains(tab, bt, nodes, loci, self.t, n_kept=n_kept, **kw)
+        times = bt[chain >> 1].astype(np.float64) + (self.t if time_before_present else 0)
+        xy = tt._ind_xy[0][chain >> 1]
+        curr = self._lineage_curr_xy(tt, nodes) if use_individs_curr_pos else None
+        out = {}
+        n = nodes.size
+        for i, locus in enumerate(loci.tolist()):
+            d_loc = out[locus] = {}
+            for j, node in enumerate(nodes.tolist()):
+                a, b = off[i * n + j], off[i * n + j + 1]
+                d = {int(c): (float(tm), np.array(p)) for c, tm, p in
+                     zip(chain[a:b].tolist(), times[a:b], xy[a:b])}
+                if curr is not None and node in d:
+                    if np.isnan(curr[j, 0]):
+                        raise ValueError('%s: use_individs_curr_pos: the individual of node %d '
+                                         'is not alive' % (who, node))
+                    d[node] = (d[node][0], curr[j].copy())
+                d_loc[node] = d
+        return out
+
+    def _calc_lineage_stats(self, individs=None, nodes=None, loci=None,
+                            stats=['dir', 'dist', 'time', 'speed'], use_individs_curr_pos=True,
+                            max_time_ago=None, min_time_ago=None, as_arrays=False):
+        """Gene-flow statistics of the lineages of the sample nodes at the loci (reference
+        structs/species.py:1309-1343, structs/genome.py:1786-1871): 'dir' the compass
+        direction in degrees from the oldest kept node's birth location to the youngest's,
+        'dist' and 'time' oldest minus youngest, 'speed' = dist / time.  The youngest and
+        oldest kept node of every (locus, node) come from the device (gnx_lineage_trace); the
+        floats are computed here in fp64 with the reference's formulas.  -> {stat: {locus:
+        [value per node]}} with None where a lineage has fewer than two kept nodes; with
+        as_arrays (an extension) {stat: float64 [n_loci][n_nodes] (NaN there), 'nodes', 'loci'}.
+        individs are Geonomics ids (default: all living, ascending, two nodes each); nodes are
+        node ids of this Species' pedigree tables.  use_individs_curr_pos as in
+        _get_lineage_dicts.  The statistics reach back to the oldest in-simulation ancestor of
+        the FULL pedigree: the reference's simplified tables list fewer ancestors (see the
+        comment above _lineage_request)."""
+        from . import pedigree as _ped
+        who = '_calc_lineage_stats'
+        for st in stats:
+            if st not in _ped.LINEAGE_STATS:
+                raise ValueError("%s: the only valid statistics are 'dir', 'dist', 'time' and "
+                                 "'speed', not %r" % (who, st))
+        tt, nodes, loci = self._lineage_request(individs, nodes, loci, who)
+        tab, bt = tt.node_table()
+        tr = self._dev.lineage_trace(tab, bt, nodes, loci, self.t, drop_before_sim=True,
+                                     min_time_ago=min_time_ago, max_time_ago=max_time_ago,
+                                     want=('first', 'last', 'n_kept'), locus_range=False)
+        curr = self._lineage_curr_xy(tt, nodes) if use_individs_curr_pos else None
+        vals = _ped.lineage_stats(tt, nodes, tr['first'], tr['last'], tr['n_kept'], self.t,
+                                  stats, curr_xy=curr)
+        if as_arrays:
+            return dict(vals, nodes=nodes, loci=loci)
+        return {st: {locus: [None if v != v else v for v in vals[st][i].tolist()]
+                     for i, locus in enumerate(loci.tolist())} for st in stats}
+
+    def _check_coalescence(self, individs=None, loci=None, all_loci=False):
+        """whether the lineages of the individuals' nodes (default: all living) have coalesced
+        inside the simulation at each locus (default: all) -> {locus: bool}, or one bool for
+        all of them if all_loci (reference structs/species.py:1282-1306): the oldest
+        in-simulation node is the same for every sample node.  Reduced on the device to a min
+        and a max per locus (gnx_lineage_trace): nothing n_loci x n_nodes comes back.  A locus
+        at which some sample node has no in-simulation node at all is not coalesced."""
+        tt, nodes, loci = self._lineage_request(individs, None, loci, '_check_coalescence')
+        tab, bt = tt.node_table()
+        tr = self._dev.lineage_trace(tab, bt, nodes, loci, self.t, want=(), locus_range=True)
+        co = (tr['locus_lo'] == tr['locus_hi']) & (tr['locus_lo'] >= 0)
+        if all_loci:
+            return bool(co.all())
+        return {locus: bool(c) for locus, c in zip(loci.tolist(), co)}
+
     def _calc_fitness(self, trait_num=None, set_fit=True):
         """reference ops/selection.py:51-112.  Overall fitness (trait_num None) is what
         the death-probability kernel of the last _do_pop_dynamics stored; the fitness of

@@ -56,6 +56,20 @@ class TiledSpecies(Species):
         raise NotImplementedError('run_gea with a Species tiled over several GPUs is not '
                                   'implemented; run the model on one GPU')
 
+    # -- lineages: not over tiles (each rank records its own births: the pedigree of a tiled
+    # Species is in pieces, and a lineage crosses them)
+    def _get_lineage_dicts(self, *args, **kw):
+        raise NotImplementedError('lineages of a Species tiled over several GPUs are not '
+                                  'implemented; run the model on one GPU')
+
+    def _calc_lineage_stats(self, *args, **kw):
+        raise NotImplementedError('lineage statistics of a Species tiled over several GPUs are '
+                                  'not implemented; run the model on one GPU')
+
+    def _check_coalescence(self, *args, **kw):
+        raise NotImplementedError('the coalescence check of a Species tiled over several GPUs '
+                                  'is not implemented; run the model on one GPU')
+
     # -- introductions: not over tiles (the newcomers would have to be routed to their tiles)
     def _add_individuals(self, *args, **kw):
         raise NotImplementedError('add_individuals with a Species tiled over several GPUs is '

@@ -653,6 +653,46 @@ int gnx_geno_locus_cross(gnx_state* h, int32_t n_loci, const int32_t* loci, int3
                          int64_t n, const int64_t* slots, double* DtZ, double* ZtZ,
                          double* Zt1);
 
+/* ---- lineages through the recorded pedigree (csrc/gnx_lineage.hip; reference
+ *      structs/genome.py:1638-1782 _get_lineage_dicts, structs/species.py:1242-1343) ---------
+ * The pedigree is recorded on the host (geonomics_amd/structs/pedigree.py, TreeTables.
+ * node_table): node_tab int32 [2 n_rows][2], node 2 row + h -> {row of the parent that gave the
+ * gamete (-1: a founder node), path key * 2 + start homologue}; birth_t int32 [n_rows], the
+ * nodes table's times (founders +1, offspring of main step t: -t).  The parent homologue at
+ * locus l is start ^ bit l of the handle's path `key` (gnx_set_recomb_paths).  A node is KEPT
+ * (structs/genome.py:1747, 1720-1729) if (!drop_before_sim or birth_t < 0) and
+ * min_ago <= birth_t + t_curr <= max_ago.  All pointers are HOST buffers; the calls return when
+ * the outputs are complete.  The table is uploaded, or the device copy of the last call is
+ * used again when n_rows and a checksum of the table's last rows are unchanged; it is freed
+ * with the handle.  Refused: a handle without genomes, without paths or with ghost records
+ * (tiles); a table whose parent rows are not earlier rows or whose keys are not cached paths;
+ * sample nodes outside the table; loci outside 0..L-1 - all before anything is launched.   */
+/* per (locus, sample node), int32 [n_loci][n_nodes], each may be NULL: root = the founder node
+ * reached, first / last = the youngest / oldest kept node (-1: none), n_kept.  locus_lo /
+ * locus_hi int32 [n_loci] (both or neither): min and max of `last` over the sample nodes - the
+ * sample has coalesced inside the simulation at a locus iff lo == hi >= 0.  The loci are
+ * worked off in launches whose outputs stay under gnx_lineage_budget.                       */
+int gnx_lineage_trace(gnx_state* h, int64_t n_rows, const int32_t* node_tab,
+                      const int32_t* birth_t, int64_t n_nodes, const int32_t* nodes,
+                      int32_t n_loci, const int32_t* loci, int32_t t_curr,
+                      int32_t drop_before_sim, int32_t min_ago, int32_t max_ago, int32_t* root,
+                      int32_t* first, int32_t* last, int32_t* n_kept, int32_t* locus_lo,
+                      int32_t* locus_hi);
+/* the same walk writing every kept node, youngest first, at chain_nodes[offsets[q] ...], q =
+ * locus index * n_nodes + node index; offsets int64 [n_loci * n_nodes + 1] = the exclusive scan
+ * of a gnx_lineage_trace's n_kept for the same request (anything else is an error, and never
+ * a write outside a chain's own stretch)                                                     */
+int gnx_lineage_chains(gnx_state* h, int64_t n_rows, const int32_t* node_tab,
+                       const int32_t* birth_t, int64_t n_nodes, const int32_t* nodes,
+                       int32_t n_loci, const int32_t* loci, int32_t t_curr,
+                       int32_t drop_before_sim, int32_t min_ago, int32_t max_ago,
+                       const int64_t* offsets, int32_t* chain_nodes);
+/* bytes of output one launch of the two calls above may produce (0: the default, 256 MiB) */
+int gnx_lineage_budget(gnx_state* h, int64_t bytes);
+/* of the last lineage call: its kernels' HIP-event time (ms), their number, and whether the
+ * node table was uploaded (1) or the resident copy used (0); each may be NULL              */
+int gnx_lineage_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* uploaded);
+
 /* ---- introductions (csrc/gnx_transplant.hip) ------------------------------------------ */
 /* Species._add_individuals with a Species as the source (structs/species.py:1631-2077):
  * n individuals of src, in the order of src_slots, appended to dst at (x[i], y[i]) with ids
