@@ -744,6 +744,14 @@ extern "C" int gnx_set_species_params(gnx_state* h, const gnx_species_params* p)
     gnx_set_error("gnx_set_species_params: n_births_fixed needs an integer lambda");
     return 1;
   }
+  // k_births multiplies at most the 64 uniforms of its stream, so the mass of k >= 64 would
+  // collapse onto 64: 2.4e-10 at lambda = 26, 1.0e-9 at 27, 4.4e-3 at 45
+  if (!p->n_births_fixed && !(p->n_births_lambda <= GNX_BIRTHS_LAMBDA_MAX)) {
+    gnx_set_error("gnx_set_species_params: n_births_lambda %g is above %d, the limit of the "
+                  "Poisson births (64 uniforms per pair)", p->n_births_lambda,
+                  GNX_BIRTHS_LAMBDA_MAX);
+    return 1;
+  }
   HIPCHK(hipStreamSynchronize(h->stream));
   h->sp = *p;
   h->have_sp = true;

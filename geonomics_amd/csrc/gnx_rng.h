@@ -73,10 +73,17 @@ __device__ __forceinline__ float gnx_normal(float u0, float u1) {
 // scipy.stats.vonmises.rvs (utils/spatial.py:383,421).  Consumes from `s`:
 // one uniform when kappa < 1e-8, else (U,V) per rejection round, bounded at
 // 14 rounds, plus one for the sign.
+// numpy takes the series s = 1/kappa + kappa below kappa = 1e-5, where rho cancels in doubles.
+// In f32 the cancellation starts four decades higher: r = 1 + sqrtf(1 + 4 kappa^2) is exactly 2
+// up to kappa = 3.2e-4 (rho = 0, s = inf, every proposal NaN) and rho is off by up to 12 % up
+// to kappa = 1e-2.  So the series serves all kappa < 0.01 (it omits O(kappa^3) beside an s of
+// 1 / kappa, less than an f32 ulp, and the acceptance test is exact for any s > 1); the draws
+// for kappa >= 0.01 are unchanged.
+#define GNX_VM_SERIES_KAPPA 0.01f
 __device__ __forceinline__ float gnx_vonmises(GnxStream& s, float mu, float kappa) {
   if (kappa < 1e-8f) return GNX_PI_F * (2.0f * gnx_u01(s.next()) - 1.0f);
   float sv;
-  if (kappa < 1e-5f) {
+  if (kappa < GNX_VM_SERIES_KAPPA) {
     sv = 1.0f / kappa + kappa;
   } else {
     float r = 1.0f + sqrtf(1.0f + 4.0f * kappa * kappa);
@@ -115,9 +122,12 @@ __device__ __forceinline__ float gnx_distance(int distr, float p1, float p2, uin
   if (distr == 0) {                        // lognormal(mean=p1, sigma=p2)
     return expf(p1 + p2 * zn);
   } else if (distr == 1) {                 // wald(mean=p1, scale=p2), numpy legacy_wald
-    float mu_2l = p1 / (2.0f * p2);
+    // numpy's smaller root X = p1 + p1 / (2 p2) (Y - sqrt(4 p2 Y + Y^2)) cancels in f32 once
+    // p1 >> p2 (negative distances from p1 / p2 ~ 1000).  With S = sqrt(4 p2 Y + Y^2),
+    // Y - S = -4 p2 Y / (Y + S), hence X = 2 p1 p2 / (2 p2 + Y + S): positive terms only, and
+    // X = p1 at Y = 0.
     float Y = p1 * zn * zn;
-    float X = p1 + mu_2l * (Y - sqrtf(4.0f * p2 * Y + Y * Y));
+    float X = 2.0f * p1 * p2 / (2.0f * p2 + Y + sqrtf(4.0f * p2 * Y + Y * Y));
     float U = gnx_u01(r.z);
     return (U <= p1 / (p1 + X)) ? X : p1 * p1 / X;
   } else {                                 // levy(loc=p1, scale=p2) = loc + scale / Z^2

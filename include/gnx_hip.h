@@ -72,6 +72,11 @@ typedef struct {
   int32_t reserved;
 } gnx_config;
 
+/* The Poisson births draw a pair's count from 64 uniforms (Knuth's product): above this mean
+ * the mass of counts >= 64 (2.4e-10 at 26, 1.0e-9 at 27) would collapse onto 64, and
+ * gnx_set_species_params refuses it.                                                        */
+#define GNX_BIRTHS_LAMBDA_MAX 26
+
 /* Species life-history parameters: the 'mating', 'mortality' and 'movement'
  * sections of the parameters file (sim/params.py SPP_PARAMS), hoisted to
  * Species attributes at structs/species.py:409-425.                          */
@@ -79,7 +84,8 @@ typedef struct {
   /* mating */
   double  b;                       /* P(pair mates)                          */
   double  R;                       /* intrinsic growth rate                  */
-  double  n_births_lambda;
+  double  n_births_lambda;         /* n_births_fixed: the (integer) number of births;
+                                    * else Poisson mean, <= GNX_BIRTHS_LAMBDA_MAX       */
   int32_t n_births_fixed;
   int32_t sexed;                   /* mating.sex                             */
   double  p_male;                  /* sex_ratio/(sex_ratio+1) (species.py:416) */

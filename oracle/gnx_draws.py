@@ -9,6 +9,11 @@ import philox as P
 
 F = np.float32
 PI = F(3.14159274101257324)
+# below it gnx_vonmises takes the series s = 1/kappa + kappa (GNX_VM_SERIES_KAPPA)
+VM_SERIES_KAPPA = F(0.01)
+# k_births multiplies at most the 64 uniforms of its stream: P(Poisson(26) >= 64) = 2.4e-10,
+# and gnx_set_species_params refuses a larger lambda
+BIRTHS_LAMBDA_MAX = 26
 
 
 def _u(seed, ids, step, op, blk=0):
@@ -27,9 +32,9 @@ def distance(distr, p1, p2, r):
     if distr == 'lognormal':
         return np.exp(p1 + p2 * zn).astype(F)
     if distr == 'wald':
-        mu_2l = p1 / (F(2.0) * p2)
+        # (the cancellation-free form of numpy's smaller root, see gnx_rng.h)
         Y = p1 * zn * zn
-        X = p1 + mu_2l * (Y - np.sqrt(F(4.0) * p2 * Y + Y * Y))
+        X = F(2.0) * p1 * p2 / (F(2.0) * p2 + Y + np.sqrt(F(4.0) * p2 * Y + Y * Y))
         U = P.u01(r[:, 2])
         return np.where(U <= p1 / (p1 + X), X, p1 * p1 / X).astype(F)
     return (p1 + p2 / (zn * zn)).astype(F)
@@ -46,7 +51,7 @@ def vonmises(seed, ids, step, op, mu, kappa, first_word=0):
     mu, kappa = F(mu), F(kappa)
     if kappa < 1e-8:
         return (PI * (F(2.0) * P.u01(words[:, w]) - F(1.0))).astype(F)
-    if kappa < 1e-5:
+    if kappa < VM_SERIES_KAPPA:
         sv = F(1.0) / kappa + kappa
     else:
         r = F(1.0) + np.sqrt(F(1.0) + F(4.0) * kappa * kappa)
@@ -97,6 +102,9 @@ def panmixia_draws(seed, ids, step, N):
 
 def births_draws(seed, focal_ids, step, lam):
     import gnx_oracle as O
+    if lam > BIRTHS_LAMBDA_MAX:
+        raise ValueError('births_draws: lambda %g > %d, the limit of the 64-uniform Poisson'
+                         % (lam, BIRTHS_LAMBDA_MAX))
     u = np.concatenate([P.u01(_u(seed, focal_ids, step, P.OP_BIRTHS, b))
                         for b in range(16)], axis=1)
     return np.maximum(O.poisson_knuth(lam, u), 1)

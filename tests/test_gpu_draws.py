@@ -25,18 +25,19 @@ def _population(rng, n, W, H, id0=1000):
     return x, y, ids
 
 
-@pytest.mark.parametrize('lam', [0.4, 1.7, 4.0])
+@pytest.mark.parametrize('lam', [0.4, 1.7, 4.0, 12.0, 26.0])
 def test_poisson_births_match_oracle(lam):
     """k_births: max(Poisson(lambda), 1) per pair from the focal parent's stream equals
     O.poisson_knuth on the same uniforms, pair by pair; offspring ids ascend in
     (pair, birth) order (structs/species.py:614-648), pairs in the canonical
-    (hash cell, id) order of their focal individual"""
+    (hash cell, id) order of their focal individual.  Up to lambda = 26, the largest the library
+    accepts: the law of these counts is checked on the oracle's (test_distributions_host.py)"""
     rng = np.random.RandomState(int(lam * 10))
     W = H = 48
     seed, step = 77, 9
     n = 4000
     x, y, ids = _population(rng, n, W, H)
-    dev = make_dev(W, H, cap=4 * n, seed=seed, mating_radius=3.0, n_births_fixed=0,
+    dev = make_dev(W, H, cap=8 * n, seed=seed, mating_radius=3.0, n_births_fixed=0,
                    n_births_lambda=lam, K_factor=2.0)
     upload_simple(dev, x, y, ids=ids)
     dev.step_index = step
@@ -56,6 +57,25 @@ def test_poisson_births_match_oracle(lam):
     # every child of a pair has the same mate
     for f in uf[:50]:
         assert np.unique(par[focal == f, 1]).size == 1
+    dev.close()
+
+
+def test_births_lambda_refusals():
+    """gnx_set_species_params: a fixed number of births is a non-negative integer; a Poisson
+    mean is at most 26 (k_births has the 64 uniforms of its stream, and the mass of k >= 64 -
+    1.0e-9 at 27 - would collapse onto 64), and the message names that limit"""
+    nat = native()
+    dev = make_dev(16, 16, cap=64, n_births_fixed=0, n_births_lambda=D.BIRTHS_LAMBDA_MAX)
+    for kw in (dict(n_births_fixed=1, n_births_lambda=1.5),
+               dict(n_births_fixed=1, n_births_lambda=-1)):
+        with pytest.raises(nat.GnxError, match='n_births_fixed needs an integer lambda'):
+            dev.set_species_params(nat.default_species_params(**kw))
+    for lam in (26.5, 45.0, float('nan')):
+        with pytest.raises(nat.GnxError, match='above 26'):
+            dev.set_species_params(nat.default_species_params(n_births_fixed=0,
+                                                              n_births_lambda=lam))
+    # a fixed number of births is not a Poisson mean
+    dev.set_species_params(nat.default_species_params(n_births_fixed=1, n_births_lambda=40))
     dev.close()
 
 
