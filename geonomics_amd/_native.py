@@ -65,6 +65,7 @@ EXPORTS = [
     'gnx_geno_gram', 'gnx_geno_matmul', 'gnx_geno_rmatmul', 'gnx_transplant',
     'gnx_geno_locus_gram', 'gnx_geno_locus_cross',
     'gnx_lineage_trace', 'gnx_lineage_chains', 'gnx_lineage_budget', 'gnx_lineage_info',
+    'gnx_pedigree_reach', 'gnx_lineage_forget',
 ]
 
 
@@ -1138,6 +1139,34 @@ class Device:
         ms, n, up = C.c_double(), C.c_int64(), C.c_int64()
         self._chk(self.lib.gnx_lineage_info(self.h, C.byref(ms), C.byref(n), C.byref(up)))
         return dict(kernel_ms=ms.value, launches=int(n.value), uploaded=bool(up.value))
+
+    # -- simplification of the recorded pedigree (csrc/gnx_simplify.hip) ------------------
+    def pedigree_reach(self, node_tab, birth_t, sample_rows, masks_of=None):
+        """gnx_pedigree_reach: node_loci int32 [2 n_rows], the number of loci at which each node
+        of the pedigree (TreeTables.node_table()) is an ancestor of the sample - both nodes of
+        every row in `sample_rows`; 0: at none.  With masks_of (node ids) -> (node_loci, uint64
+        [n][W64]): those nodes' ancestral loci as bit masks in the paths' layout"""
+        tab = _arr(node_tab, np.int32)
+        bt = _arr(birth_t, np.int32).ravel()
+        if tab.ndim != 2 or tab.shape != (2 * bt.size, 2):
+            raise ValueError('node_tab: int32 [2 n_rows][2] with birth_t [n_rows]')
+        rows = _arr(sample_rows, np.int32).ravel()
+        node_loci = np.zeros(2 * bt.size, np.int32)
+        req = masks = None
+        if masks_of is not None:
+            req = _arr(masks_of, np.int32).ravel()
+            masks = np.zeros((req.size, self.W64), np.uint64)
+        n_req = 0 if req is None else int(req.size)
+        self._chk(self.lib.gnx_pedigree_reach(
+            self.h, C.c_int64(bt.size), _ptr(tab, C.c_int32), _ptr(bt, C.c_int32),
+            C.c_int64(rows.size), _ptr(rows, C.c_int32), _ptr(node_loci, C.c_int32),
+            C.c_int64(n_req), _ptr(req if n_req else None, C.c_int32),
+            _ptr(masks if n_req else None, C.c_uint64)))
+        return node_loci if masks_of is None else (node_loci, masks)
+
+    def lineage_forget(self):
+        """drop the device's copy of the node table: the next lineage call uploads its own"""
+        self._chk(self.lib.gnx_lineage_forget(self.h))
 
     # -- introductions (csrc/gnx_transplant.hip) ----------------------------------------
     def transplant(self, src, slots, x, y, first_id):

@@ -916,3 +916,54 @@ static inline int gnx_grid(int64_t n, int block, int max_blocks = 1 << 20) {
   if (g > max_blocks) g = max_blocks;
   return (int)g;
 }
+
+// ---- lineage calls (gnx_lineage.hip, gnx_simplify.hip) -----------------------------------
+#define LIN_BUDGET (256ll << 20)  // bytes of output per launch unless gnx_lineage_budget says so
+
+// the handle takes lineage requests; the node table is on the device (uploaded, or the copy of
+// an earlier call when nothing was appended since) and every index in it is in range
+int lin_table(gnx_state* h, const char* who, int64_t n_rows, const int32_t* tab,
+              const int32_t* bt, int32_t t_curr);
+
+// device buffers of one call, freed on every exit
+struct LinScratch {
+  std::vector<void*> p;
+  ~LinScratch() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  template <class T>
+  int get(T** out, size_t count) {
+    *out = nullptr;
+    if (hipMalloc((void**)out, (count > 0 ? count : 1) * sizeof(T)) != hipSuccess) {
+      gnx_set_error("gnx_lineage: out of device memory (%zu bytes)", count * sizeof(T));
+      return 1;
+    }
+    p.push_back(*out);
+    return 0;
+  }
+};
+
+// HIP events around the launches of one call: gnx_lineage_info's kernel time and launches
+struct LinTimer {
+  gnx_state* h;
+  hipEvent_t a = nullptr, b = nullptr;
+  explicit LinTimer(gnx_state* h_) : h(h_) {
+    (void)hipEventCreate(&a);
+    (void)hipEventCreate(&b);
+    h->lin_ms = 0.0;
+    h->lin_launches = 0;
+  }
+  ~LinTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  void start() { (void)hipEventRecord(a, h->stream); }
+  int stop(int64_t launches = 1) {
+    (void)hipEventRecord(b, h->stream);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) h->lin_ms += ms;
+    h->lin_launches += launches;
+    return 0;
+  }
+};

@@ -27,7 +27,6 @@ typedef unsigned long long u64;
 
 #define LIN_NPT 8                 // sample nodes per thread of the trace kernel
 #define LIN_CHECK_ROWS 1024       // rows at the table's end that the reuse checksum covers
-#define LIN_BUDGET (256ll << 20)  // bytes of output per launch unless gnx_lineage_budget says so
 
 namespace {
 
@@ -164,24 +163,6 @@ k_lin_chains(int64_t n_nodes, const int32_t* __restrict__ nodes, int n_q,
 
 namespace {
 
-// device buffers of one call, freed on every exit
-struct LinScratch {
-  std::vector<void*> p;
-  ~LinScratch() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <class T>
-  int get(T** out, size_t count) {
-    *out = nullptr;
-    if (hipMalloc((void**)out, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-      gnx_set_error("gnx_lineage: out of device memory (%zu bytes)", count * sizeof(T));
-      return 1;
-    }
-    p.push_back(*out);
-    return 0;
-  }
-};
-
 uint64_t lin_checksum(int64_t n_rows, const int32_t* tab, const int32_t* bt, int n_paths) {
   const int64_t r0 = std::max<int64_t>(0, n_rows - LIN_CHECK_ROWS);
   uint64_t s = 1469598103934665603ull ^ (uint64_t)n_rows;
@@ -193,6 +174,8 @@ uint64_t lin_checksum(int64_t n_rows, const int32_t* tab, const int32_t* bt, int
   }
   return s;
 }
+
+}  // namespace
 
 // the handle takes lineage requests; the node table is on the device (uploaded, or the copy of
 // an earlier call when nothing was appended since) and every index in it is in range
@@ -261,6 +244,8 @@ int lin_table(gnx_state* h, const char* who, int64_t n_rows, const int32_t* tab,
   return 0;
 }
 
+namespace {
+
 // the sample nodes and the loci, checked and uploaded
 int lin_request(gnx_state* h, const char* who, int64_t n_rows, int64_t n_nodes,
                 const int32_t* nodes, int32_t n_loci, const int32_t* loci, LinScratch& s,
@@ -307,30 +292,6 @@ int lin_grid(const char* who, int n_q, int64_t n_groups, LinGrid* g) {
   g->blocks = (unsigned)blocks;
   return 0;
 }
-
-struct LinTimer {
-  gnx_state* h;
-  hipEvent_t a = nullptr, b = nullptr;
-  explicit LinTimer(gnx_state* h_) : h(h_) {
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-    h->lin_ms = 0.0;
-    h->lin_launches = 0;
-  }
-  ~LinTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  void start() { (void)hipEventRecord(a, h->stream); }
-  int stop() {
-    (void)hipEventRecord(b, h->stream);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) h->lin_ms += ms;
-    h->lin_launches += 1;
-    return 0;
-  }
-};
 
 }  // namespace
 

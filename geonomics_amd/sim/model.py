@@ -464,6 +464,8 @@ class Model:
                 break
         if self._verbose:
             self._print_timestep_info(mode)
+        if mode == 'main':
+            self._simplify_pedigrees()
         if mode == 'burn' and np.all([spp.burned for spp in self.comm.values()]):
             if self.reassign_genomes:
                 for spp in self.comm.values():
@@ -482,6 +484,28 @@ class Model:
                 ' & '.join('"' + spp.name + '"' for spp in self.comm.values()
                            if spp.extinct), self.it), flush=True)
         return extinct
+
+    def _simplify_pedigrees(self):
+        """at the end of every tskit_simp_interval-th main step, simplify the recorded pedigree
+        of each Species that keeps one (reference sim/model.py:756-768); an interval of None:
+        never.  A Species tiled over several GPUs is skipped (structs/tiled.py)."""
+        for spp in self.comm.values():
+            if spp._tt is None or spp.extinct or getattr(spp, '_comm', None) is not None:
+                continue
+            interval = getattr(spp.gen_arch, 'tskit_simp_interval', None)
+            if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) \
+                    or interval < 1 or self.t == -1 or (self.t + 1) % interval != 0:
+                continue
+            if self._verbose:
+                print("\n\nnow sorting and simplifying tskit tables for Species: '%s'"
+                      % spp.name)
+                print('\tNUMBER EDGES BEFORE SIMPLIFICATION:', spp._tt._edges_count())
+                print('\tNUMBER INDIVIDS BEFORE SIMPLIFICATION:', spp._tt.ids.size)
+            spp._sort_and_simplify_table_collection()
+            if self._verbose:
+                print('\n\tNUMBER EDGES AFTER SIMPLIFICATION: ', spp._tt._edges_count())
+                print('\tNUMBER INDIVIDS AFTER SIMPLIFICATION: ', spp._tt.ids.size, '\n',
+                      flush=True)
 
     def _iter_seed(self, it):
         """the host-side random stream of iteration it >= 1 (community / genomic

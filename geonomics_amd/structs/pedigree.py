@@ -19,16 +19,21 @@ module turns them into the rows the reference adds to its tables:
 tskit itself is not needed to build or to write the tables (`write_text` emits
 tskit's own text format, `tskit.load_text` reads it; `write_csv` the per-table CSVs of
 Model.write_tskit_table_collection, sim/model.py:3449-3486).  Not kept: the coalescent
-history msprime simulates for the founders (:956-1094) - founders are roots here -
-and periodic simplification (the tables keep every individual that ever lived).
+history msprime simulates for the founders (:956-1094) - founders are roots here.
+
+Periodic simplification (reference structs/species.py:1107-1142, every tskit_simp_interval
+main steps) is `simplify`: the rows no lineage of the living passes through are dropped and the
+rest renumbered in their old order.  tskit's simplify also removes unary nodes and trims edges
+to their ancestral intervals; one parent row and one path per node cannot express that, so
+both stay.
 
 Beside the float edge rows the tables keep the integers they are made from (`node_table`:
 parent row, path key and start homologue per node, birth time per row).  A lineage at a locus
 is a chain of look-ups in them (reference structs/genome.py:1638-1782, there through tskit's
 trees): `trace` / `lineages` walk it in numpy, csrc/gnx_lineage.hip on the device, and
 `lineage_stat_values` holds the reference's four gene-flow statistics (:1803-1871).  Because
-nothing is simplified, a lineage lists EVERY ancestor, not only those tskit's simplification
-would keep for the current sample.
+unary nodes are never removed, a lineage lists EVERY ancestor, not only those tskit's
+simplification would keep for the current sample.
 """
 import numpy as np
 
@@ -127,6 +132,9 @@ class TreeTables:
     def ids(self):
         self._flush()
         return self._ind_id[0]
+
+    def _edges_count(self):
+        return int(sum(c.shape[0] for c in self._edges))
 
     def add_founders(self, ids, xy, genotypes=None):
         ids = np.asarray(ids, dtype=np.int64)
@@ -293,6 +301,117 @@ class TreeTables:
         offsets = np.zeros(nodes.size * loci.size + 1, np.int64)
         np.cumsum(np.bincount(q, minlength=nodes.size * loci.size), out=offsets[1:])
         return offsets, c[order].astype(np.int32)
+
+    # -- simplification ------------------------------------------------------------------
+    def _sample_rows(self, sample_rows):
+        rows = np.unique(np.asarray(sample_rows, dtype=np.int64).ravel())
+        n = self.ids.size
+        if rows.size == 0 or rows[0] < 0 or rows[-1] >= n:
+            raise ValueError('sample_rows: a non-empty list of rows in 0..%d' % (n - 1))
+        return rows
+
+    def _path_bits(self, keys):
+        """bool [n][L]: bit l of the paths `keys` (the parity of their switch points <= l)"""
+        keys = np.asarray(keys, dtype=np.int64)
+        flips = np.zeros((keys.size, self.L + 1), np.int8)
+        n = self._bp_off[keys + 1] - self._bp_off[keys]
+        who = np.repeat(np.arange(keys.size), n)
+        idx = np.arange(n.sum()) - np.repeat(np.cumsum(n) - n, n) + np.repeat(self._bp_off[keys], n)
+        if idx.size:
+            np.add.at(flips, (who, self._bp_loci[idx]), 1)
+        return (np.cumsum(flips[:, :self.L], axis=1) & 1).astype(bool)
+
+    def ancestral_masks(self, sample_rows):
+        """bool [2 n_rows][L]: node v is ANCESTRAL at locus l if the lineage at l of some sample
+        node passes through v; the sample is both nodes of every row in `sample_rows` (a sample
+        node is ancestral at every locus).  The masks follow from the children alone,
+
+            mask[2 prow + 1] |= mask[c] &  (path bits of c ^ start of c)
+            mask[2 prow + 0] |= mask[c] & ~(path bits of c ^ start of c)
+
+        for every node c with parent row prow, and a parent is born in an earlier main step than
+        its child: one pass over the birth cohorts, youngest first, is exact.  The numpy form of
+        csrc/gnx_simplify.hip."""
+        nt, bt = self.node_table()
+        rows = self._sample_rows(sample_rows)
+        mask = np.zeros((nt.shape[0], self.L), bool)
+        mask[2 * rows] = True
+        mask[2 * rows + 1] = True
+        prow_all = nt[:, 0].astype(np.int64)
+        has = prow_all >= 0
+        assert (bt[prow_all[has]] > bt[np.nonzero(has)[0] >> 1]).all(), (
+            'a parent must be born in an earlier step than its child')
+        for t in np.unique(bt):                              # ascending: the youngest cohort first
+            r = np.nonzero(bt == t)[0]
+            c = np.stack([2 * r, 2 * r + 1], 1).ravel()
+            c = c[has[c] & mask[c].any(axis=1)]
+            if c.size == 0:
+                continue
+            ks = nt[c, 1].astype(np.int64)
+            keys, inv = np.unique(ks >> 1, return_inverse=True)
+            x = self._path_bits(keys)[inv] ^ (ks & 1).astype(bool)[:, None]
+            m = mask[c]
+            np.logical_or.at(mask, 2 * prow_all[c] + 1, m & x)
+            np.logical_or.at(mask, 2 * prow_all[c], m & ~x)
+        return mask
+
+    def simplify(self, sample_rows, node_loci=None):
+        """Drop the rows without an ancestral node (ancestral_masks) for the sample - both nodes
+        of every row in `sample_rows`, in the model the living - and renumber the rest in their
+        old order.  node_loci int [2 n_rows]: per node the number of loci at which it is
+        ancestral, from the device (gnx_pedigree_reach); None: counted here.
+        -> int64 [old n_rows]: the new row, or -1.
+
+        Every lineage of every sample node, at every locus, runs through kept rows only, so
+        trace / lineages of the sample are what they were up to the renumbering, and
+        genotypes_of is exact for the sample.  A node of a kept row that is itself not ancestral
+        may lose its parent row: it becomes a root, its edge rows go, and genotypes_of of a kept
+        ANCESTOR is exact only on its ancestral loci.  The sites table can lose sites that only
+        dropped founders carried; new mutations of dropped individuals go with them.  Unlike
+        tskit's simplify, unary nodes stay and edges are not trimmed to ancestral intervals."""
+        nt, bt = self.node_table()
+        n = bt.size
+        rows = self._sample_rows(sample_rows)
+        if node_loci is None:
+            node_loci = self.ancestral_masks(rows).sum(axis=1)
+        anc = np.asarray(node_loci).ravel() > 0
+        if anc.size != 2 * n:
+            raise ValueError('node_loci: one entry per node (%d), not %d' % (2 * n, anc.size))
+        assert anc[2 * rows].all() and anc[2 * rows + 1].all(), 'a sample node is ancestral'
+        keep = anc[0::2] | anc[1::2]
+        new_row = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int64)
+        if keep.all():
+            return new_row
+        # the node table: parent rows renumbered; a node whose parent row went is a root
+        knode = np.repeat(keep, 2)
+        nt2 = nt[knode].copy()
+        has = nt2[:, 0] >= 0
+        newp = np.where(has, new_row[np.maximum(nt2[:, 0], 0)], -1)
+        lost = has & (newp < 0)
+        assert not (lost & anc[knode]).any(), 'an ancestral node keeps its parent row'
+        nt2[:, 0] = newp
+        nt2[lost, 1] = 0
+        # the edge rows of the kept children whose parent row stays
+        e = self._edges[0]
+        par, chi = e[:, 2].astype(np.int64), e[:, 3].astype(np.int64)
+        ek = (new_row[chi >> 1] >= 0) & (new_row[par >> 1] >= 0)
+        e2 = e[ek].copy()
+        e2[:, 2] = 2 * new_row[par[ek] >> 1] + (par[ek] & 1)
+        e2[:, 3] = 2 * new_row[chi[ek] >> 1] + (chi[ek] & 1)
+        old_ids = self._ind_id[0]
+        if self._new_muts:
+            r = np.searchsorted(old_ids, np.array([m[1] for m in self._new_muts], np.int64))
+            self._new_muts = [m for m, k in zip(self._new_muts, keep[r]) if k]
+        kf = keep[:self.n_founders]
+        if self._founder_g is not None:
+            self._founder_g = self._founder_g[kf]
+        self.n_founders = int(kf.sum())                   # (kept founders stay the first rows)
+        self._nt, self._edges = [nt2], [e2]
+        self._bt = [bt[keep]]
+        self._ind_id = [old_ids[keep]]
+        self._ind_xy = [self._ind_xy[0][keep]]
+        self._ind_time = [self._ind_time[0][keep]]
+        return new_row
 
     # -- tables ------------------------------------------------------------------------
     def tables(self):

@@ -1006,8 +1006,9 @@ class Species:
     # -- lineages through the recorded pedigree (structs/pedigree.py; csrc/gnx_lineage.hip) ----
     # The reference simplifies its tables with tskit's default, which drops unary nodes: its
     # lineage at a locus lists only the ancestors that survive simplification for the current
-    # sample.  The pedigree here is not simplified (tskit is outside this build), so a lineage
-    # lists EVERY ancestor.  _check_coalescence is the same either way (two lineages share
+    # sample.  The simplification here (_sort_and_simplify_table_collection) drops only the rows
+    # no lineage of the living passes through and keeps unary nodes, so a lineage lists EVERY
+    # ancestor.  _check_coalescence is the same either way (two lineages share
     # their oldest in-simulation node exactly when they coalesce inside the simulation); the
     # statistics are taken to the oldest in-simulation ancestor of the full pedigree, and no
     # parity with tskit's simplification is claimed.
@@ -1068,7 +1069,7 @@ class Species:
         use_individs_curr_pos puts the individual's current x, y (device columns) in the
         sample node's own entry when that entry is among the kept nodes; the reference raises
         KeyError when it is not, here the dict is left as it is.  The lineages list every
-        ancestor: the pedigree is not simplified (see the comment above).  Meant for
+        ancestor: a simplification keeps unary nodes (see the comment above).  Meant for
         plotting-sized requests: above _LINEAGE_DICT_MAX chain entries it raises ValueError - use
         _calc_lineage_stats(as_arrays=True) or _check_coalescence."""
         who = '_get_lineage_dicts'
@@ -1155,6 +1156,37 @@ class Species:
         if all_loci:
             return bool(co.all())
         return {locus: bool(c) for locus, c in zip(loci.tolist(), co)}
+
+    def _sort_and_simplify_table_collection(self, verbose=False):
+        """Drop from the recorded pedigree every row that no lineage of a living individual
+        passes through at any locus (reference structs/species.py:1107-1142, there tskit's
+        sort and simplify with the living individuals' nodes as the sample).  Which nodes are
+        ancestral is worked out on the device (gnx_pedigree_reach), the tables are compacted on
+        the host (TreeTables.simplify).  Lineages, lineage statistics, the coalescence check and
+        genotypes_of of the living are unchanged by it; node ids are renumbered.  Unary nodes
+        stay and edges are not trimmed, unlike tskit's simplify.
+        -> (rows before, rows after)"""
+        if self._tt is None:
+            raise ValueError("no pedigree was recorded for this Species ('use_tskit' False, "
+                             "or the genomes were not assigned yet)")
+        tt = self._tt
+        ids, order = self._ids_sorted()
+        ids = ids[order]
+        before = int(tt.ids.size)
+        if ids.size == 0:
+            return before, before
+        rows = np.searchsorted(tt.ids, ids)
+        assert (tt.ids[np.minimum(rows, before - 1)] == ids).all(), (
+            'a living individual is missing from the pedigree')
+        tab, bt = tt.node_table()
+        node_loci = self._dev.pedigree_reach(tab, bt, rows)
+        tt.simplify(rows, node_loci)
+        self._dev.lineage_forget()
+        after = int(tt.ids.size)
+        if verbose:
+            print('pedigree of "%s" simplified: %d -> %d individuals' % (self.name, before, after),
+                  flush=True)
+        return before, after
 
     def _calc_fitness(self, trait_num=None, set_fit=True):
         """reference ops/selection.py:51-112.  Overall fitness (trait_num None) is what

@@ -19,7 +19,9 @@ What changes with respect to the single-GPU Species:
     gathered); files are written by rank 0.
 Mutations: every rank draws the same list from the host generator and applies those
 whose offspring it owns (_mutate_tiled); the pedigree tables are kept whole on every
-rank (birth records gathered each step); linkage r^2 from counts summed over the tiles
+rank (birth records gathered each step) and never simplified (Model._do_timestep skips a
+tiled Species at its tskit_simp_interval: the reachability pass runs on one handle without
+ghost records); linkage r^2 from counts summed over the tiles
 (sim/stats.py).  Panmixia (mating_radius None): every tile holds everybody's record, the
 Python-driven protocol (parallel.py) - correct, not fast.
 """
@@ -69,6 +71,10 @@ class TiledSpecies(Species):
     def _check_coalescence(self, *args, **kw):
         raise NotImplementedError('the coalescence check of a Species tiled over several GPUs '
                                   'is not implemented; run the model on one GPU')
+
+    def _sort_and_simplify_table_collection(self, *args, **kw):
+        raise NotImplementedError('simplifying the pedigree of a Species tiled over several '
+                                  'GPUs is not implemented; run the model on one GPU')
 
     # -- introductions: not over tiles (the newcomers would have to be routed to their tiles)
     def _add_individuals(self, *args, **kw):

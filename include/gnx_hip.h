@@ -699,6 +699,29 @@ int gnx_lineage_budget(gnx_state* h, int64_t bytes);
  * node table was uploaded (1) or the resident copy used (0); each may be NULL              */
 int gnx_lineage_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* uploaded);
 
+/* ---- simplification of the recorded pedigree (csrc/gnx_simplify.hip; reference
+ *      structs/species.py:1107-1142 _sort_and_simplify_table_collection, run every
+ *      tskit_simp_interval main steps: sim/model.py:756-768) ------------------------------
+ * A node is ANCESTRAL at locus l if the lineage at l of some sample node passes through it; the
+ * sample is both nodes of every row in sample_rows (the living).  node_loci int32 [2 n_rows]:
+ * the number of loci at which the node is ancestral (0: at none; a row both of whose nodes have
+ * 0 carries no lineage of the sample and can be dropped).  req_masks uint64 [n_req][W64] (NULL
+ * with n_req = 0): the ancestral loci of the nodes in req_nodes as bit masks in the layout of
+ * the recombination paths, bits at or above L zero.  node_tab / birth_t as for
+ * gnx_lineage_trace, taken through the same resident copy; one launch per birth cohort
+ * (youngest first) and, when the masks of all nodes exceed gnx_lineage_budget, per block of
+ * mask words.  gnx_lineage_info reports the call.  Refused before anything is launched, beside
+ * what gnx_lineage_trace refuses: birth_t ascending somewhere along the rows, a parent row that
+ * is not of an earlier birth cohort than its child, sample rows out of range or repeated,
+ * requested nodes out of range.                                                            */
+int gnx_pedigree_reach(gnx_state* h, int64_t n_rows, const int32_t* node_tab,
+                       const int32_t* birth_t, int64_t n_samples, const int32_t* sample_rows,
+                       int32_t* node_loci, int64_t n_req, const int32_t* req_nodes,
+                       uint64_t* req_masks);
+/* drop the resident copy of the node table: the next lineage call uploads its table (after the
+ * host has renumbered the rows, the reuse check's row count and checksum mean nothing)      */
+int gnx_lineage_forget(gnx_state* h);
+
 /* ---- introductions (csrc/gnx_transplant.hip) ------------------------------------------ */
 /* Species._add_individuals with a Species as the source (structs/species.py:1631-2077):
  * n individuals of src, in the order of src_slots, appended to dst at (x[i], y[i]) with ids

@@ -18,6 +18,19 @@ and all loci:
              formulas on the host
   host       TreeTables.trace (the vectorised numpy walk) on a subsample of `--host-nodes`
              sample nodes x `--host-loci` loci, its time scaled by queries to the full request
+
+The model never simplifies its pedigree while it runs ('tskit_simp_interval': None): the
+measurements above are of the table that holds every individual that ever lived.
+
+    python tools/lineage_bench.py --simplify        # the same run, simplified once at its end
+
+  trace      before: gnx_lineage_trace for the full request on the unsimplified table
+  reach      gnx_pedigree_reach for the living (csrc/gnx_simplify.hip): kernel time, launches,
+             the bytes the pass must move (every mask written once, the children's non-empty
+             masks and their paths' words read once) and their rate beside gnx_measure_copy;
+             then once more with the byte budget raised so that all words go in one block
+  simplify   TreeTables.simplify on the host: seconds, rows and edges before / after
+  trace      after: the same request on the simplified table, equal to the one before
 """
 import argparse
 import json
@@ -45,21 +58,24 @@ def params(side, N, L, T, r, seed):
     s = d['comm']['species']['spp_0']
     s['init'].update({'N': N, 'K_factor': 0.5})
     s['mating'].update({'mating_radius': 4})
-    s['gen_arch'].update({'L': L, 'n_recomb_sims': 2000, 'use_tskit': True, 'r_distr_alpha': r})
+    s['gen_arch'].update({'L': L, 'n_recomb_sims': 2000, 'use_tskit': True, 'r_distr_alpha': r,
+                          'tskit_simp_interval': None})
     d['model'].update({'T': T, 'burn_T': 30, 'seed': {'num': seed}})
     return gnx.make_params_dict(d, 'lineage_bench')
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--side', type=int, default=460, help='landscape side (K = 0.5 per cell)')
-    ap.add_argument('--N', type=int, default=90000)
+    ap.add_argument('--side', type=int, default=420, help='landscape side (K = 0.5 per cell)')
+    ap.add_argument('--N', type=int, default=85000)
     ap.add_argument('--L', type=int, default=1000)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--r', type=float, default=2e-3,
                     help='recombination rate between neighbouring loci (the default of 0.5 makes '
                          '~L / 2 edge rows per gamete: the HOST tables of 10^5 individuals over '
                          'hundreds of steps would not fit)')
+    ap.add_argument('--simplify', action='store_true',
+                    help='simplify the pedigree once at the end and measure that instead')
     ap.add_argument('--host-nodes', type=int, default=2000)
     ap.add_argument('--host-loci', type=int, default=50)
     a = ap.parse_args()
@@ -90,6 +106,8 @@ def main():
     emit(what='model', burn_s=round(t1 - t0, 2), main_s=round(t2 - t1, 2),
          node_table_bytes=int(tab.nbytes + bt.nbytes), **size)
     dev = spp._dev
+    if a.simplify:
+        return simplify(a, spp, tt, ids, size)
     for rep in range(2):        # the first call uploads the node table, the second finds it
         t0 = time.perf_counter()
         tr = dev.lineage_trace(tab, bt, nodes, loci, spp.t, want=('first', 'last', 'n_kept'),
@@ -129,6 +147,70 @@ def main():
     emit(what='host', subsample_nodes=int(hn.size), subsample_loci=int(hl.size), queries=q,
          s=round(t, 3), scaled_to_full_request_s=round(t * size['queries'] / q, 1),
          equals_device=bool(same))
+
+
+def simplify(a, spp, tt, ids, size):
+    """--simplify: the full trace, one simplification for the living, the full trace again"""
+    from geonomics_amd import _native as nat
+    dev = spp._dev
+    loci = np.arange(a.L)
+    want = ('first', 'last', 'n_kept')
+
+    def trace(when):
+        tab, bt = tt.node_table()
+        rows = np.searchsorted(tt.ids, ids)
+        nodes = np.stack([2 * rows, 2 * rows + 1], 1).ravel()
+        t0 = time.perf_counter()
+        tr = dev.lineage_trace(tab, bt, nodes, loci, spp.t, want=want, locus_range=False)
+        t = time.perf_counter() - t0
+        info = dev.lineage_info()
+        emit(what='trace', when=when, rows=int(bt.size), call_s=round(t, 3),
+             kernel_ms=round(info['kernel_ms'], 3), launches=info['launches'],
+             table_uploaded=info['uploaded'])
+        # node ids are renumbered by the simplification: compare the individuals behind them
+        # (every 8th locus: the ids are int64)
+        sub = {k: tr[k][::8] for k in want}
+        return {k: np.where(v >= 0, tt.ids[np.maximum(v, 0) >> 1] * 2 + (v & 1), -1)
+                if k != 'n_kept' else v.copy() for k, v in sub.items()}
+
+    before = trace('before')
+    tab, bt = tt.node_table()
+    rows = np.searchsorted(tt.ids, ids)
+    n_rows, n_edges = int(bt.size), tt._edges_count()
+    t0 = time.perf_counter()
+    node_loci = dev.pedigree_reach(tab, bt, rows)
+    t = time.perf_counter() - t0
+    info = dev.lineage_info()
+    # every mask written once (16 W64 bytes per row); per child with a non-empty mask its mask
+    # and the words of its path read once
+    anc = node_loci > 0
+    has_parent = tab[:, 0] >= 0
+    moved = 8 * dev.W64 * (2 * n_rows + 2 * int((anc & has_parent).sum()))
+    copy = nat.measure_copy(1 << 30, 3)
+    rate = moved / (info['kernel_ms'] * 1e-3) / 1e9
+    emit(what='reach', call_s=round(t, 3), kernel_ms=round(info['kernel_ms'], 3),
+         launches=info['launches'], cohorts=int(np.unique(bt).size),
+         nodes_ancestral=int(anc.sum()), nodes=int(anc.size),
+         rows_with_an_ancestral_node=int((anc[0::2] | anc[1::2]).sum()),
+         bytes_moved=int(moved), gb_per_s=round(rate, 1), measure_copy_gb_per_s=round(copy, 1),
+         fraction_of_copy=round(rate / copy, 4))
+    # the same pass with all words in one column block: a launch per cohort and no more
+    dev.lineage_budget(2 * n_rows * dev.W64 * 8)
+    same = np.array_equal(dev.pedigree_reach(tab, bt, rows), node_loci)
+    info = dev.lineage_info()
+    dev.lineage_budget(0)
+    emit(what='reach_one_block', kernel_ms=round(info['kernel_ms'], 3), launches=info['launches'],
+         mask_bytes=int(2 * n_rows * dev.W64 * 8), equals_default_budget=bool(same),
+         fraction_of_copy=round(moved / (info['kernel_ms'] * 1e-3) / 1e9 / copy, 4))
+    t0 = time.perf_counter()
+    tt.simplify(rows, node_loci)
+    t = time.perf_counter() - t0
+    dev.lineage_forget()
+    emit(what='simplify', host_s=round(t, 3), rows_before=n_rows, rows_after=int(tt.ids.size),
+         edges_before=n_edges, edges_after=tt._edges_count(),
+         kept_fraction=round(tt.ids.size / n_rows, 4), living=int(ids.size))
+    after = trace('after')
+    emit(what='equal', loci_compared=int(before['n_kept'].shape[0]), **{k: bool(np.array_equal(before[k], after[k])) for k in want})
 
 
 if __name__ == '__main__':
