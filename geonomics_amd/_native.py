@@ -65,7 +65,7 @@ EXPORTS = [
     'gnx_geno_gram', 'gnx_geno_matmul', 'gnx_geno_rmatmul', 'gnx_transplant',
     'gnx_geno_locus_gram', 'gnx_geno_locus_cross',
     'gnx_lineage_trace', 'gnx_lineage_chains', 'gnx_lineage_budget', 'gnx_lineage_info',
-    'gnx_pedigree_reach', 'gnx_lineage_forget',
+    'gnx_pedigree_reach', 'gnx_lineage_forget', 'gnx_dist_perm_sums',
 ]
 
 
@@ -1059,6 +1059,38 @@ class Device:
                                                 _ptr(DtZ, C.c_double), _ptr(ZtZ, C.c_double),
                                                 _ptr(Zt1, C.c_double)))
         return DtZ, ZtZ, Zt1
+
+    # -- Mantel tests and MMRR (csrc/gnx_mantel.hip) --------------------------------------
+    def dist_perm_sums(self, predictors, perm, slots=None, locus_mask=None):
+        """the cross-sums of the genetic distances of `slots` (all living slots by default)
+        with the predictors' distances under the permutations `perm` int32 [n_perm][n]
+        (individual i takes the columns of individual perm[p][i]).  predictors: a list of lists
+        of (field, index) columns, e.g. [[(F_X, 0), (F_Y, 0)], [(F_E, 1)]], read as the device
+        holds them.  -> sums float64 [n_perm][n_pred], dict(m, sy, syy, sx [n_pred],
+        sxy [n_pred], sxx [n_pred][n_pred]) of the unpermuted pairs"""
+        s, n = self._geno_slots(slots)
+        m = None
+        if locus_mask is not None:
+            m = _arr(locus_mask, np.uint64)
+            if m.size != self.W64:
+                raise ValueError('locus_mask: %d words, not %d' % (m.size, self.W64))
+        off = np.cumsum([0] + [len(p) for p in predictors]).astype(np.int32)
+        cols = _arr([c for p in predictors for c in p], np.int32).reshape(-1, 2)
+        k = len(predictors)
+        perm = _arr(perm, np.int32)
+        if perm.ndim != 2 or perm.shape[1] != n:
+            raise ValueError('perm: [n_perm][%d], not %s' % (n, perm.shape))
+        sums = np.zeros((perm.shape[0], k), np.float64)
+        mom = np.zeros(3 + 2 * k + k * (k + 1) // 2, np.float64)
+        self._chk(self.lib.gnx_dist_perm_sums(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), k,
+            _ptr(off, C.c_int32), _ptr(cols, C.c_int32), int(perm.shape[0]),
+            _ptr(perm, C.c_int32), _ptr(sums, C.c_double), _ptr(mom, C.c_double)))
+        sxx = np.zeros((k, k))
+        sxx[np.triu_indices(k)] = mom[3 + 2 * k:]
+        sxx = sxx + np.triu(sxx, 1).T
+        return sums, dict(m=mom[0], sy=mom[1], syy=mom[2], sx=mom[3:3 + k].copy(),
+                          sxy=mom[3 + k:3 + 2 * k].copy(), sxx=sxx)
 
     # -- lineages through the recorded pedigree (csrc/gnx_lineage.hip) -------------------
     @staticmethod

@@ -1,5 +1,6 @@
 // What the entry points that read the dosage matrix share (gnx_geno.hip: products over the
-// individuals; gnx_gea.hip: cross-products over the loci): the call's device scratch, the
+// individuals; gnx_gea.hip: cross-products over the loci;
+// gnx_mantel.hip: distance cross-sums under permutation): the call's device scratch, the
 // preconditions, the slots' genome rows, and the 64 x 64 popcount tile kernel.
 #pragma once
 #include <algorithm>
@@ -14,6 +15,11 @@ typedef unsigned long long u64;
 // gnx_geno.hip
 __global__ void k_geno_rows(int64_t n, const int64_t* __restrict__ slots,
                             const int32_t* __restrict__ grow, int32_t* __restrict__ rows);
+// X[i][hom][q] = word widx[q] of row i's homologue, masked (q >= nw and i >= n: 0)
+__global__ void k_geno_gather(int64_t n, int64_t n_pad, int nw, int Wm,
+                              const int32_t* __restrict__ rows, const int32_t* __restrict__ widx,
+                              const u64* __restrict__ wmask, const u64* __restrict__ G, GnxHalves H,
+                              u64* __restrict__ X);
 // out[i][j] = sum over words and homologue pairs of popcount(X[i][h][w] & X[j][h'][w]) for
 // rows i, j < n of X [n rounded up to 64][2][Wm] (rows past n and words past the data: 0)
 __global__ void k_geno_gram(int64_t n, int Wm, const u64* __restrict__ X,

@@ -870,3 +870,44 @@ class Model:
             warnings.warn('run_gea: this build does not plot (plotting is outside the GPU hot '
                           'path); pass plot=False.  The results are returned.', stacklevel=2)
         return results
+
+    def _test_sample(self, spp, individs, n):
+        """the ids a Mantel / MMRR call analyses: individs, or a random n of the living drawn
+        as write_gendata draws its sample, or everybody"""
+        if n is None:
+            return individs
+        if individs is not None:
+            raise ValueError('give individs or n, not both')
+        if isinstance(n, bool) or int(n) != n or n < 1:
+            raise ValueError('n: a positive number of individuals (got %r)' % (n,))
+        return np.array([*_get_adhoc_sample(spp, int(n), rng=self._rng)], dtype=np.int64)
+
+    def run_mmrr(self, spp=0, predictors=('geo', 'env'), env_lyrs=None, trts=None,
+                 individs=None, n=None, loci=None, nperm=999, seed=None):
+        """multiple matrix regression with randomization (reference
+        data/IBD_IBE_demo/MMRR.py, the last step of demos/_IBD_IBE.py): the genetic distances
+        between the individuals (get_genetic_distances) regressed on the distances of the
+        predictors - 'geo' (x, y), 'env' (the layers env_lyrs; default: the layers the Traits
+        are tied to, or all) and 'phn' (the Traits trts; default: all) - with nperm row-and-column
+        permutations of the genetic matrix, computed on the device.  individs, or a random
+        sample of n, and loci restrict the analysis; at most 8192 individuals.  seed: the
+        permutations of np.random.seed(seed) followed by the reference's shuffles (default: the
+        model's own generator).
+        -> the reference's OrderedDict: 'R^2', 'Intercept', the predictors, '<name>(t)',
+        '<name>(p)', 'F-statistic', 'F p-value'"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._run_mmrr(predictors=predictors, env_lyrs=env_lyrs, trts=trts,
+                             individs=self._test_sample(spp, individs, n), loci=loci,
+                             nperm=nperm, seed=seed)
+
+    def run_mantel(self, x='geo', given=None, spp=0, env_lyrs=None, trts=None, individs=None,
+                   n=None, loci=None, nperm=999, seed=None):
+        """Mantel test of the genetic distances against the distances of predictor x ('geo',
+        'env' or 'phn', as run_mmrr), or the partial test given another predictor (reference
+        data/IBD_IBE_demo/run_mantel.R: vegan's mantel.partial(gen, env, geo), the genetic
+        matrix permuted), computed on the device.
+        -> dict(r, p = (1 + #{r_perm >= r}) / (nperm + 1), nperm, perm_r [nperm])"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._run_mantel(x=x, given=given, env_lyrs=env_lyrs, trts=trts,
+                               individs=self._test_sample(spp, individs, n), loci=loci,
+                               nperm=nperm, seed=seed)

@@ -1003,6 +1003,99 @@ class Species:
         return dict(ind_df=res['ind_df'], loci_df=res['loci_df'], var_df=res['var_df'],
                     trait_loci=np.asarray(trt.loci), ids=ids)
 
+    # -- Mantel tests and MMRR (sim/mmrr.py; csrc/gnx_mantel.hip) --------------------------
+    def _dist_predictors(self, who, predictors, env_lyrs, trts):
+        """the device columns [(field, index), ...] of each named predictor: 'geo' = (x, y),
+        'env' = the layers env_lyrs (default: the layers the Traits are tied to, or every layer
+        of a Species without Traits), 'phn' = the Traits trts (default: all)"""
+        if isinstance(predictors, str):
+            predictors = (predictors,)
+        predictors = list(predictors)
+        if not predictors:
+            raise ValueError('%s: no predictors' % who)
+        traits = self.gen_arch.traits or {}
+        n_layers = int(self._dev.cfg.n_layers)
+        cols = []
+        for name in predictors:
+            if name == 'geo':
+                cols.append([(nat.F_X, 0), (nat.F_Y, 0)])
+            elif name == 'env':
+                lyrs = env_lyrs
+                if lyrs is None:
+                    lyrs = sorted({int(t.lyr_num) for t in traits.values()}) or range(n_layers)
+                lyrs = [int(l) for l in np.atleast_1d(lyrs)]
+                if not lyrs or min(lyrs) < 0 or max(lyrs) >= n_layers:
+                    raise ValueError('%s: env_lyrs: layers in 0..%d' % (who, n_layers - 1))
+                cols.append([(nat.F_E, l) for l in lyrs])
+            elif name == 'phn':
+                nums = sorted(traits) if trts is None else [int(t) for t in np.atleast_1d(trts)]
+                if not nums or any(t not in traits for t in nums):
+                    raise ValueError('%s: trts: Traits among %s' % (who, sorted(traits)))
+                cols.append([(nat.F_Z, t) for t in nums])
+            else:
+                raise ValueError("%s: unknown predictor %r ('geo', 'env' or 'phn')"
+                                 % (who, name))
+        if len(set(predictors)) != len(predictors):
+            raise ValueError('%s: a predictor is listed twice' % who)
+        if len(cols) > 4 or sum(len(c) for c in cols) > 8:
+            raise ValueError('%s: at most 4 predictors and 8 columns (layers, traits, x, y) '
+                             'together' % who)
+        return predictors, cols
+
+    def _dist_perm_sums(self, who, predictors, env_lyrs, trts, individs, loci, nperm, seed,
+                        min_n):
+        """(names, permuted cross-sums [nperm][K], moments) of a Mantel / MMRR request:
+        the reference's row shuffles drawn from `seed` (or the Species' rng), inverted for the
+        library, and gnx_dist_perm_sums on the device columns"""
+        from ..sim import mmrr as _mmrr
+        if self.gen_arch is None or self._dev.L == 0:
+            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
+        if not self.__dict__.get('_genomes_assigned', False):
+            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
+                             'model in first' % who)
+        if isinstance(nperm, bool) or int(nperm) != nperm or nperm < 1:
+            raise ValueError('%s: nperm: at least 1 permutation (got %r)' % (who, nperm))
+        names, cols = self._dist_predictors(who, predictors, env_lyrs, trts)
+        ids, slots = self._geno_sample(individs)
+        if ids.size > 8192:
+            raise ValueError('%s: at most 8192 individuals per test (the distance matrix is '
+                             'n x n), got %d: sample them with n=... or individs=...'
+                             % (who, ids.size))
+        if ids.size < min_n:
+            raise ValueError('%s: %d individuals leave the test no degrees of freedom (at least '
+                             '%d)' % (who, ids.size, min_n))
+        _, mask = self._geno_loci(loci)
+        rows = _mmrr.draw_row_shuffles(ids.size, int(nperm), seed=seed, rng=self._rng)
+        sums, mom = self._dev.dist_perm_sums(cols, _mmrr.invert_rows(rows), slots, mask)
+        return names, sums, mom
+
+    def _run_mmrr(self, predictors=('geo', 'env'), env_lyrs=None, trts=None, individs=None,
+                  loci=None, nperm=999, seed=None):
+        """multiple matrix regression with randomization of the genetic distances on the
+        predictors' distances (reference data/IBD_IBE_demo/MMRR.py, as demos/_IBD_IBE.py calls
+        it), every permutation's fit from cross-sums taken on the device
+        -> the reference's OrderedDict (sim/mmrr.mmrr)"""
+        from ..sim import mmrr as _mmrr
+        K = 1 if isinstance(predictors, str) else len(predictors)
+        # n (n - 1) / 2 pairs must exceed the K + 1 coefficients
+        min_n = 3
+        while min_n * (min_n - 1) // 2 < K + 2:
+            min_n += 1
+        names, sums, mom = self._dist_perm_sums('run_mmrr', predictors, env_lyrs, trts,
+                                                individs, loci, nperm, seed, min_n)
+        return _mmrr.mmrr(sums, mom, names)
+
+    def _run_mantel(self, x='geo', given=None, env_lyrs=None, trts=None, individs=None,
+                    loci=None, nperm=999, seed=None):
+        """Mantel test of the genetic distances against predictor x, partial given another
+        (reference data/IBD_IBE_demo/run_mantel.R: vegan's mantel.partial with the genetic
+        matrix permuted) -> dict(r, p, nperm, perm_r [nperm])"""
+        from ..sim import mmrr as _mmrr
+        preds = (x,) if given is None else (x, given)
+        _, sums, mom = self._dist_perm_sums('run_mantel', preds, env_lyrs, trts, individs,
+                                            loci, nperm, seed, 3 if given is None else 4)
+        return _mmrr.mantel(sums, mom, 0, None if given is None else 1)
+
     # -- lineages through the recorded pedigree (structs/pedigree.py; csrc/gnx_lineage.hip) ----
     # The reference simplifies its tables with tskit's default, which drops unary nodes: its
     # lineage at a locus lists only the ancestors that survive simplification for the current

@@ -58,6 +58,16 @@ class TiledSpecies(Species):
         raise NotImplementedError('run_gea with a Species tiled over several GPUs is not '
                                   'implemented; run the model on one GPU')
 
+    # -- Mantel tests and MMRR: not over tiles (the distance matrix pairs individuals of
+    # different tiles: a gather of the sample)
+    def _run_mmrr(self, *args, **kw):
+        raise NotImplementedError('run_mmrr with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
+    def _run_mantel(self, *args, **kw):
+        raise NotImplementedError('run_mantel with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
     # -- lineages: not over tiles (each rank records its own births: the pedigree of a tiled
     # Species is in pieces, and a lineage crosses them)
     def _get_lineage_dicts(self, *args, **kw):

@@ -659,6 +659,28 @@ int gnx_geno_locus_cross(gnx_state* h, int32_t n_loci, const int32_t* loci, int3
                          int64_t n, const int64_t* slots, double* DtZ, double* ZtZ,
                          double* Zt1);
 
+/* ---- isolation by distance and by environment (csrc/gnx_mantel.hip; reference
+ *      demos/_IBD_IBE.py:195-330 -> data/IBD_IBE_demo/MMRR.py:7-74, which refits an OLS on the
+ *      n (n - 1) / 2 unfolded pairs once per permutation, and data/IBD_IBE_demo/run_mantel.R,
+ *      vegan's mantel.partial) -------------------------------------------------------------
+ * The cross-sums of the genetic distance matrix Y with n_pred predictor distance matrices
+ * under row-and-column permutation of Y, from which every statistic of both tests follows
+ * (geonomics_amd/sim/mmrr.py).  n, slots, locus_mask and the preconditions as gnx_geno_gram
+ * (1..8192 individuals); Y[a][b] = 0.5 sqrt(G_aa + G_bb - 2 G_ab) of that call's exact G, which
+ * stays on the device.  Predictor k is the Euclidean distance over columns pred_off[k] ..
+ * pred_off[k + 1] - 1 (pred_off int32 [n_pred + 1], from 0; 1..4 predictors, at most 8 columns
+ * together) of pred_cols int32 [columns][2] = {field, index}: {GNX_F_X, 0}, {GNX_F_Y, 0},
+ * {GNX_F_E, layer} or {GNX_F_Z, trait}, read as the device holds them.  perm int32
+ * [n_perm][n] (1..2^20 permutations): individual i of the sample takes the columns of individual
+ * perm[p][i]; an entry outside 0..n-1 is an error before anything is launched.  HOST outputs,
+ * fp64 throughout, summed in a fixed order (a call repeated is bit-equal):
+ * sums [n_perm][n_pred]: S_k(p) = sum over pairs a > b of Y[a][b] x_k[perm[p][a]][perm[p][b]];
+ * moments [3 + 2 n_pred + n_pred (n_pred + 1) / 2] of the unpermuted sample over the pairs:
+ * their number, sum y, sum y^2, sum x_k, sum y x_k, sum x_k x_l (k <= l, row-major).        */
+int gnx_dist_perm_sums(gnx_state* h, int64_t n, const int64_t* slots, const uint64_t* locus_mask,
+                       int32_t n_pred, const int32_t* pred_off, const int32_t* pred_cols,
+                       int32_t n_perm, const int32_t* perm, double* sums, double* moments);
+
 /* ---- lineages through the recorded pedigree (csrc/gnx_lineage.hip; reference
  *      structs/genome.py:1638-1782 _get_lineage_dicts, structs/species.py:1242-1343) ---------
  * The pedigree is recorded on the host (geonomics_amd/structs/pedigree.py, TreeTables.
