@@ -66,6 +66,7 @@ EXPORTS = [
     'gnx_geno_locus_gram', 'gnx_geno_locus_cross',
     'gnx_lineage_trace', 'gnx_lineage_chains', 'gnx_lineage_budget', 'gnx_lineage_info',
     'gnx_pedigree_reach', 'gnx_lineage_forget', 'gnx_dist_perm_sums',
+    'gnx_stats_group_counts',
 ]
 
 
@@ -950,6 +951,25 @@ class Device:
         ch = np.zeros(self.L, np.int32)
         self._chk(self.lib.gnx_stats_locus_counts(self.h, _ptr(c1, C.c_int32),
                                                   _ptr(ch, C.c_int32)))
+        return c1, ch
+
+    def stats_group_counts(self, slots, group_start):
+        """per-group, per-locus counts: slots[group_start[g]:group_start[g + 1]] are the slots of
+        group g -> (cnt1 [G][L] int32 1-alleles, cnt_het [G][L] int32 heterozygotes)"""
+        s = _arr(slots, np.int64).ravel()
+        if s.size and (s.min() < -2 ** 31 or s.max() >= 2 ** 31):
+            raise GnxError('gnx_stats_group_counts: slot out of range')
+        s = s.astype(np.int32)
+        gs = _arr(group_start, np.int64).ravel()
+        G = int(gs.size) - 1
+        # (the library refuses G outside 1..1024 before it writes: no G x L buffer for that)
+        shape = (G, self.L) if 1 <= G <= 1024 and G * self.L <= 2 ** 26 else (0, 0)
+        c1 = np.zeros(shape, np.int32)
+        ch = np.zeros(shape, np.int32)
+        self._chk(self.lib.gnx_stats_group_counts(
+            self.h, C.c_int64(int(s.size)), _ptr(s, C.c_int32), C.c_int32(max(G, -1)),
+            _ptr(gs if gs.size else np.zeros(1, np.int64), C.c_int64), _ptr(c1, C.c_int32),
+            _ptr(ch, C.c_int32)))
         return c1, ch
 
     def stats_ld(self, loci):

@@ -911,3 +911,36 @@ class Model:
         return spp._run_mantel(x=x, given=given, env_lyrs=env_lyrs, trts=trts,
                                individs=self._test_sample(spp, individs, n), loci=loci,
                                nperm=nperm, seed=seed)
+
+    # -- Fst, diversity and the SFS of groups of individuals (sim/fst.py) ----------------
+    def calc_fst(self, groups, spp=0, loci=None, method='HsHt', mean=True, est_Hs=False,
+                 include_zeros=False):
+        """Fst between groups of individuals (reference tests/validation/island/island_test.py,
+        calc_Fsts_mod), from per-group locus counts taken on the device.  groups: a dict
+        name -> ids, or integer labels aligned with the living in id order (group_by_layer,
+        group_by_grid; negative: left out).  method 'HsHt' (the reference's) or 'hudson'
+        -> {(name_a, name_b): mean over loci, or with mean=False the per-locus array};
+        'var' -> one array over all groups, or its mean"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_fst(groups, loci=loci, method=method, mean=mean, est_Hs=est_Hs,
+                             include_zeros=include_zeros)
+
+    def calc_diversity(self, groups=None, spp=0, loci=None):
+        """per group (default: everybody as one group): n, S, pi, theta_w, tajima_d, Ho, He, Fis"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_diversity(groups=groups, loci=loci)
+
+    def calc_sfs(self, groups=None, spp=0, loci=None, folded=False):
+        """site-frequency spectrum, one row per group -> (names, sfs)"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_sfs(groups=groups, loci=loci, folded=folded)
+
+    def group_by_layer(self, lyr, edges, spp=0):
+        """labels of the living in id order: np.digitize(e on Layer lyr, edges) - 1, -1 outside"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._group_by_layer(self._get_lyr_num(lyr), edges)
+
+    def group_by_grid(self, nx, ny, spp=0):
+        """labels of the living in id order: the landscape cut into nx x ny rectangles"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._group_by_grid(nx, ny)

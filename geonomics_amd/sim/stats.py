@@ -11,6 +11,9 @@ output tree GNX_mod-<name>/it-<i>/spp-<name>/mod-<name>_it-<i>_spp-<name>_
 a 't' column, the LD matrix stack in %0.5f text, and OTHER_STATS written once
 at the last timestep with 5-decimal floats (utils/io.py:126-168).
 Not kept: _plot_stat (plotting is outside the hot path).
+Added: the stat 'fst' (params: calc, freq, method, and either 'grid': (nx, ny) or 'lyr' and
+'edges'): the mean Fst of every pair of groups (sim/fst.py, from gnx_stats_group_counts), one
+row per sampled timestep in ..._FST.csv.
 """
 import csv
 import os
@@ -74,6 +77,37 @@ def _calc_mean_fitness(spp):
     return np.nan
 
 
+def _calc_fst(spp, method='HsHt', grid=None, lyr=None, edges=None):
+    """mean Fst of every pair of groups (sim/fst.py, from per-group counts taken on the
+    device): the groups are the rectangles of grid = (nx, ny), or the classes of the
+    environment on Layer lyr between edges.  The set of groups is fixed by the params, not by
+    who is alive: an empty group's pairs are NaN.  -> (column names, values)"""
+    from . import fst as _fst
+    if grid is not None and lyr is None and edges is None:
+        nx, ny = (int(v) for v in grid)
+        G, labels = nx * ny, spp._group_by_grid(nx, ny)
+    elif grid is None and lyr is not None and edges is not None:
+        land = getattr(spp, '_land_ref', None)
+        if isinstance(lyr, str) and land is not None:
+            lyr = land._get_lyr_num(lyr)
+        G, labels = len(edges) - 1, spp._group_by_layer(lyr, edges)
+    else:
+        raise ValueError("the 'fst' statistic takes either 'grid': (nx, ny) or 'lyr' and "
+                         "'edges'")
+    n, cnt1, cnt_het = (np.zeros(G, np.int64), np.zeros((G, 0), np.int32),
+                        np.zeros((G, 0), np.int32))
+    if (np.asarray(labels) >= 0).any():
+        _, n_, c1, ch = spp._group_counts(labels)
+        n = np.concatenate([n_, np.zeros(G - len(n_), np.int64)])
+        pad = np.zeros((G - len(n_), c1.shape[1]), np.int32)
+        cnt1, cnt_het = np.concatenate([c1, pad]), np.concatenate([ch, pad])
+    names = [*range(G)]
+    if method == 'var':
+        return ['var'], [_fst.calc_fst(names, n, cnt1, cnt_het, method='var', mean=True)]
+    res = _fst.calc_fst(names, n, cnt1, cnt_het, method=method, mean=True)
+    return ['%s-%s' % k for k in res], [*res.values()]
+
+
 _OTHER = 'OTHER_STATS.csv'
 
 
@@ -87,10 +121,10 @@ def _fmt(v):
 
 class _StatsCollector:
     calc_fn_dict = {'Nt': _calc_Nt, 'ld': _calc_ld, 'het': _calc_het, 'maf': _calc_maf,
-                    'mean_fit': _calc_mean_fitness}
+                    'mean_fit': _calc_mean_fitness, 'fst': _calc_fst}
     file_suffix_dict = {'Nt': _OTHER, 'ld': 'LD.txt', 'het': 'HET.csv', 'maf': 'MAF.csv',
-                        'mean_fit': _OTHER}
-    _needs_genome = ('ld', 'het', 'maf', 'mean_fit')
+                        'mean_fit': _OTHER, 'fst': 'FST.csv'}
+    _needs_genome = ('ld', 'het', 'maf', 'mean_fit', 'fst')
 
     def __init__(self, model_name, params):
         self.model_name = model_name
@@ -155,6 +189,18 @@ class _StatsCollector:
             w.writerow([t] + row.tolist())
 
     @staticmethod
+    def _write_fst_row(filepath, val, t):
+        """one row per sampled timestep: t, then the mean Fst of every pair of groups in sorted
+        pair order; the header is written once, from the group names"""
+        cols, row = val
+        new = not os.path.exists(filepath)
+        with open(filepath, 'a', newline='') as f:
+            w = csv.writer(f)
+            if new:
+                w.writerow(['t'] + [*cols])
+            w.writerow([t] + [float(v) for v in row])
+
+    @staticmethod
     def _write_array_to_stack(filepath, arr, t):
         with open(filepath, 'a') as f:
             np.savetxt(f, arr, fmt='%0.5f')
@@ -192,8 +238,8 @@ class _StatsCollector:
                 vals = sd['vals']
                 if t >= len(vals) or vals[t] is None or vals[t] is np.nan:
                     continue
-                writer = (self._write_array_to_stack if stat == 'ld'
-                          else self._write_row_to_csv)
+                writer = {'ld': self._write_array_to_stack,
+                          'fst': self._write_fst_row}.get(stat, self._write_row_to_csv)
                 if self.writer:
                     writer(sd['filepath'], vals[t], t)
                 # keep only the latest sample in memory (sim/stats.py:214-222)

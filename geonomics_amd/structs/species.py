@@ -893,6 +893,81 @@ class Species:
         np.bitwise_or.at(mask, loci >> 6, np.uint64(1) << (loci & 63).astype(np.uint64))
         return loci, mask
 
+    # -- Fst, diversity and the SFS of groups of individuals (sim/fst.py;
+    # csrc/gnx_group_counts.hip) --------------------------------------------------------
+    def _group_counts(self, groups, loci=None):
+        """per-group locus counts taken on the device (gnx_stats_group_counts): groups as
+        sim/fst.make_groups takes them (a dict name -> ids, or integer labels aligned with the
+        living in id order; negative: left out); loci selects columns on the host
+        -> (names, n [G], cnt1 [G][L'], cnt_het [G][L'])"""
+        from ..sim import fst as _fst
+        if self.gen_arch is None or self._dev.L == 0:
+            raise ValueError('the Species has no genomes (no gen_arch)')
+        ids, slots = self._geno_sample(None)
+        names, order, group_start = _fst.make_groups(ids, groups)
+        if len(names) > 1024:
+            raise ValueError('at most 1024 groups per call (got %d)' % len(names))
+        cnt1, cnt_het = self._dev.stats_group_counts(slots[order], group_start)
+        if loci is not None:
+            loci = np.asarray(loci, dtype=np.int64).ravel()
+            if loci.size == 0 or loci.min() < 0 or loci.max() >= self._dev.L:
+                raise ValueError('loci: a non-empty list of loci in 0..%d' % (self._dev.L - 1))
+            cnt1, cnt_het = cnt1[:, loci], cnt_het[:, loci]
+        return names, np.diff(group_start), cnt1, cnt_het
+
+    def _everybody(self, groups):
+        return np.zeros(len(self), np.int64) if groups is None else groups
+
+    def _calc_fst(self, groups, loci=None, method='HsHt', mean=True, est_Hs=False,
+                  include_zeros=False):
+        """Fst between groups of individuals from counts taken on the device.  'HsHt' (the
+        reference's island validation, tests/validation/island/island_test.py:54-115) and
+        'hudson' -> {(name_a, name_b): value}, keyed as calc_Fsts_mod keys its dict; the value
+        is the nanmean over loci as there ('hudson': the ratio of averages), or with mean=False
+        the per-locus array.  'var' -> one array over all groups, or its mean."""
+        from ..sim import fst as _fst
+        if method not in ('HsHt', 'hudson', 'var'):
+            raise ValueError("method: 'HsHt', 'hudson' or 'var', not %r" % (method,))
+        names, n, cnt1, cnt_het = self._group_counts(groups, loci)
+        return _fst.calc_fst(names, n, cnt1, cnt_het, method=method, mean=mean, est_Hs=est_Hs,
+                             include_zeros=include_zeros)
+
+    def _calc_diversity(self, groups=None, loci=None):
+        """per group (None: one group holding everybody): n, S, pi, theta_w, tajima_d, Ho, He,
+        Fis (sim/fst.diversity) -> dict of arrays [G], and 'names'"""
+        from ..sim import fst as _fst
+        names, n, cnt1, cnt_het = self._group_counts(self._everybody(groups), loci)
+        out = _fst.diversity(cnt1, cnt_het, n)
+        out['names'] = names
+        return out
+
+    def _calc_sfs(self, groups=None, loci=None, folded=False):
+        """site-frequency spectrum, one row per group (sim/fst.sfs) -> (names, sfs)"""
+        from ..sim import fst as _fst
+        names, n, cnt1, _ = self._group_counts(self._everybody(groups), loci)
+        return names, _fst.sfs(cnt1, n, folded=folded)
+
+    def _group_by_layer(self, lyr_num, edges):
+        """labels of the living in id order by their environment on a Layer:
+        np.digitize(e, edges) - 1, individuals outside the edges -1"""
+        edges = np.asarray(edges, dtype=np.float64).ravel()
+        if edges.size < 2 or (np.diff(edges) <= 0).any():
+            raise ValueError('edges: at least two ascending values')
+        lab = np.digitize(self._get_e(lyr_num=int(lyr_num)), edges) - 1
+        lab[lab >= edges.size - 1] = -1
+        return lab.astype(np.int64)
+
+    def _group_by_grid(self, nx, ny):
+        """labels of the living in id order by the rectangle of the landscape, cut into
+        nx x ny by coordinate, they stand in: label = iy * nx + ix"""
+        if int(nx) < 1 or int(ny) < 1:
+            raise ValueError('nx, ny: at least 1')
+        dim = self._land_ref.dim
+        xy = self._get_coords()
+        ix = np.clip((xy[:, 0] * (int(nx) / dim[0])).astype(np.int64), 0, int(nx) - 1)
+        iy = np.clip((xy[:, 1] * (int(ny) / dim[1])).astype(np.int64), 0, int(ny) - 1)
+        return iy * int(nx) + ix
+
     def _calc_genetic_PCA(self, n_pcs=3, individs=None, loci=None, method='auto', n_iter=8,
                           oversample=10, seed=0):
         """PCA of the mean genotypes of the living individuals asked for (reference

@@ -86,6 +86,12 @@ class TiledSpecies(Species):
         raise NotImplementedError('simplifying the pedigree of a Species tiled over several '
                                   'GPUs is not implemented; run the model on one GPU')
 
+    # -- Fst, diversity and the SFS of groups: not over tiles (the per-group counts add over
+    # tiles: one all-reduce of G x L, with the groups agreed between the ranks)
+    def _group_counts(self, *args, **kw):
+        raise NotImplementedError('group counts (Fst, diversity, SFS) of a Species tiled over '
+                                  'several GPUs are not implemented; run the model on one GPU')
+
     # -- introductions: not over tiles (the newcomers would have to be routed to their tiles)
     def _add_individuals(self, *args, **kw):
         raise NotImplementedError('add_individuals with a Species tiled over several GPUs is '

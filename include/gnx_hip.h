@@ -615,6 +615,23 @@ int gnx_last_births(gnx_state* h, int64_t* child_id /*[B]*/, int64_t* parent_id 
 /* per-locus count of 1-alleles over the 2N chromosomes and of heterozygous
  * individuals: het = cnt_het / N (_calc_het), f1 = cnt1 / 2N (_calc_maf)     */
 int gnx_stats_locus_counts(gnx_state* h, int32_t* cnt1 /*[L]*/, int32_t* cnt_het /*[L]*/);
+/* the same two counts per group of individuals (csrc/gnx_group_counts.hip): what Fst between
+ * groups, per-group diversity and the site-frequency spectrum are host arithmetic on
+ * (geonomics_amd/sim/fst.py).  It replaces the reference's method, which downloads every
+ * genotype and loops in Python over loci x pairs of islands
+ * (tests/validation/island/island_test.py:70-115).
+ * slots[group_start[g] .. group_start[g + 1]) are the slots of group g's individuals; a group
+ * may be empty, and individuals in no group are absent.  cnt1[g][l] = 1-alleles of group g at
+ * locus l over both homologues, cnt_het[g][l] = its heterozygotes; with G = 1 and all living
+ * slots the outputs equal gnx_stats_locus_counts'.  Refused before anything is launched
+ * (return 1): no genomes; ghost records (a tile); G outside 1..1024; G * L above 2^26 counts per table; group_start
+ * not starting at 0, decreasing, or not ending at n; a slot outside [0, gnx_n_slots); a group
+ * of 2^30 individuals or more.  A pending crossover is cut first, and an uncompacted
+ * population would be gathered (the order of the slots may change then, no result does):
+ * no individual, genome or later draw is changed.                                        */
+int gnx_stats_group_counts(gnx_state* h, int64_t n, const int32_t* slots /*[n], grouped*/,
+                           int32_t G, const int64_t* group_start /*[G + 1]*/,
+                           int32_t* cnt1 /*[G][L]*/, int32_t* cnt_het /*[G][L]*/);
 /* r^2 between the listed loci (_calc_ld); double [n][n], NaN on the diagonal */
 int gnx_stats_ld(gnx_state* h, int32_t n_loci, const int32_t* loci, double* r2);
 /* the counts behind r^2, which add over tiles: c[i] 1-alleles at locus i, cc[i][j]
