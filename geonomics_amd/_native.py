@@ -66,7 +66,7 @@ EXPORTS = [
     'gnx_geno_locus_gram', 'gnx_geno_locus_cross',
     'gnx_lineage_trace', 'gnx_lineage_chains', 'gnx_lineage_budget', 'gnx_lineage_info',
     'gnx_pedigree_reach', 'gnx_lineage_forget', 'gnx_dist_perm_sums',
-    'gnx_stats_group_counts',
+    'gnx_stats_group_counts', 'gnx_sgs_sums',
 ]
 
 
@@ -1111,6 +1111,48 @@ class Device:
         sxx = sxx + np.triu(sxx, 1).T
         return sums, dict(m=mom[0], sy=mom[1], syy=mom[2], sx=mom[3:3 + k].copy(),
                           sxy=mom[3 + k:3 + 2 * k].copy(), sxx=sxx)
+
+    # -- fine-scale spatial genetic structure (csrc/gnx_sgs.hip) ---------------------------
+    def sgs_sums(self, edges, slots=None, locus_mask=None, locus_weight=None, perm=None,
+                 max_work=0):
+        """the per-class sums over the pairs of `slots` (all living slots by default) closer
+        than edges[-1] (include/gnx_hip.h, gnx_sgs_sums).  edges float64 [n_bins + 1];
+        locus_weight float64 [L] or None; perm int32 [n] or None (individual i stands where it
+        is with the genome of individual perm[i]).  max_work <= 0: only the work is computed.
+        -> dict(work, isums int64 [n_bins][3], fsums float64 [n_bins][7], n_zero); isums,
+        fsums and n_zero are None when max_work <= 0"""
+        s, n = self._geno_slots(slots)
+        m = None
+        if locus_mask is not None:
+            m = _arr(locus_mask, np.uint64)
+            if m.size != self.W64:
+                raise ValueError('locus_mask: %d words, not %d' % (m.size, self.W64))
+        e = _arr(edges, np.float64).ravel()
+        nb = int(e.size) - 1
+        wt = None
+        if locus_weight is not None:
+            wt = _arr(locus_weight, np.float64).ravel()
+            if wt.size != self.L:
+                raise ValueError('locus_weight: %d entries, not L = %d' % (wt.size, self.L))
+        p = None
+        if perm is not None:
+            p = _arr(perm, np.int32).ravel()
+            if p.size != n:
+                raise ValueError('perm: [%d], not %s' % (n, p.shape))
+        # (the library refuses n_bins outside 1..32 before it writes)
+        rows = nb if 1 <= nb <= 32 else 0
+        isums = np.zeros((rows, 3), np.int64)
+        fsums = np.zeros((rows, 7), np.float64)
+        work = np.zeros(1, np.int64)
+        nz = np.zeros(1, np.int64)
+        self._chk(self.lib.gnx_sgs_sums(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), C.c_int32(max(nb, -1)),
+            _ptr(e if e.size else np.zeros(1), C.c_double), _ptr(wt, C.c_double),
+            _ptr(p, C.c_int32), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
+            _ptr(isums, C.c_int64), _ptr(fsums, C.c_double), _ptr(nz, C.c_int64)))
+        if max_work <= 0:
+            return dict(work=int(work[0]), isums=None, fsums=None, n_zero=None)
+        return dict(work=int(work[0]), isums=isums, fsums=fsums, n_zero=int(nz[0]))
 
     # -- lineages through the recorded pedigree (csrc/gnx_lineage.hip) -------------------
     @staticmethod

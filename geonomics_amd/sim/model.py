@@ -912,6 +912,28 @@ class Model:
                                individs=self._test_sample(spp, individs, n), loci=loci,
                                nperm=nperm, seed=seed)
 
+    def calc_spatial_structure(self, spp=0, edges=None, n_classes=10, max_dist=None,
+                               individs=None, n=None, loci=None, nperm=0, seed=None,
+                               fit_range=None, max_work=None):
+        """fine-scale spatial genetic structure (an extension: the reference's IBD demo ends at
+        MMRR on a sample): Loiselle's kinship averaged over the pairs of each distance class,
+        its slope on ln(distance), Sp = -slope / (1 - F of the first class) and Wright's
+        neighbourhood size 1 / Sp, computed on the device from the pairs closer than the largest
+        class only, so the whole population can be analysed.  edges: the classes' bounds
+        (default: n_classes classes of equal width in ln r from one landscape cell to max_dist;
+        default a quarter of the shorter side).  individs, or a random sample of n, and loci
+        restrict the analysis.  nperm > 0 adds permutation tests (genomes shuffled over the
+        positions; seed as run_mantel's).  fit_range: (first class, one past the last) the slope
+        is fitted over.  max_work bounds the pair-words (candidate pairs x genome words) of one
+        device call; a request above it raises ValueError.
+        -> dict: edges, pairs, mean_r, mean_lnr, F, dist2 (arrays over the classes), slope, F1,
+        Sp, Nb, n, n_zero, work, ids; with nperm: nperm, perm_slope, p_slope, perm_F, p_F"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_spatial_structure(
+            edges=edges, n_classes=n_classes, max_dist=max_dist,
+            individs=self._test_sample(spp, individs, n), loci=loci, nperm=nperm, seed=seed,
+            fit_range=fit_range, max_work=max_work)
+
     # -- Fst, diversity and the SFS of groups of individuals (sim/fst.py) ----------------
     def calc_fst(self, groups, spp=0, loci=None, method='HsHt', mean=True, est_Hs=False,
                  include_zeros=False):

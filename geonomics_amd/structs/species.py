@@ -1171,6 +1171,84 @@ class Species:
                                             loci, nperm, seed, 3 if given is None else 4)
         return _mmrr.mantel(sums, mom, 0, None if given is None else 1)
 
+    # -- fine-scale spatial genetic structure (sim/sgs.py; csrc/gnx_sgs.hip) ----------------
+    # pair-words (candidate pairs x genome words) one call may take: about ten seconds at the
+    # measured rate of the call with cells that fill their tiles
+    _SGS_MAX_WORK = 1 << 43
+
+    def _calc_spatial_structure(self, edges=None, n_classes=10, max_dist=None, individs=None,
+                                loci=None, nperm=0, seed=None, fit_range=None, max_work=None):
+        """kinship by distance class over the pairs of the living individuals asked for (all by
+        default; no n x n matrix, so the whole population can be analysed): Loiselle's kinship
+        per class, its slope on ln(distance), Sp and Wright's neighbourhood size
+        (sim/sgs.spatial_structure), from per-class sums taken on the device (gnx_sgs_sums).
+        edges: the classes' bounds, ascending (1..32 classes); default n_classes classes of equal
+        width in ln r from the landscape's cell size to max_dist (default: a quarter of the
+        shorter landscape side).  nperm > 0: the genomes are permuted over the positions, drawn
+        as run_mantel draws its permutations, one device call each.  fit_range: (first class,
+        one past the last) of the classes the slope is fitted over.  max_work: the pair-words
+        (candidate pairs x genome words) one call may take
+        -> dict of arrays and scalars: edges, pairs, mean_r, mean_lnr, F, dist2, slope, F1, Sp,
+        Nb, n, n_zero (pairs at distance 0: in no class), work, ids; with nperm: nperm,
+        perm_slope, p_slope, perm_F, p_F"""
+        from ..sim import mmrr as _mmrr
+        from ..sim import sgs as _sgs
+        who = 'calc_spatial_structure'
+        if self.gen_arch is None or self._dev.L == 0:
+            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
+        if not self.__dict__.get('_genomes_assigned', False):
+            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
+                             'model in first' % who)
+        if isinstance(nperm, bool) or int(nperm) != nperm or nperm < 0:
+            raise ValueError('%s: nperm: a number of permutations >= 0 (got %r)' % (who, nperm))
+        if edges is None:
+            dim = self._land_ref.dim
+            hi = min(dim) / 4.0 if max_dist is None else float(max_dist)
+            edges = _sgs.default_edges(1.0, hi, n_classes)
+        elif max_dist is not None:
+            raise ValueError('%s: give edges or max_dist, not both' % who)
+        edges = _sgs.check_edges(edges)
+        _sgs._fit_slice(fit_range, edges.size - 1)
+        if max_work is None:
+            max_work = self._SGS_MAX_WORK
+        if isinstance(max_work, bool) or int(max_work) != max_work or max_work < 1:
+            raise ValueError('%s: max_work: a positive number of pair-words (got %r)'
+                             % (who, max_work))
+        ids, slots = self._geno_sample(individs)
+        n = ids.size
+        if n < 2:
+            raise ValueError('%s: at least 2 individuals (got %d)' % (who, n))
+        if n > 2 ** 24:
+            raise ValueError('%s: at most 2^24 individuals per call (got %d): sample them with '
+                             'n=... or individs=...' % (who, n))
+        loci_u, mask = self._geno_loci(loci)
+        dev = self._dev
+        work = dev.sgs_sums(edges, slots, mask)['work']
+        if work > max_work:
+            raise ValueError('%s: %d pair-words of work (candidate pairs x genome words) exceed '
+                             'max_work = %d: analyse a sample (n=...), fewer loci (loci=...) or a '
+                             'smaller max_dist, or raise max_work' % (who, work, max_work))
+        cnt1, _ = dev.stats_group_counts(slots, np.array([0, n], np.int64))
+        s_l = cnt1[0].astype(np.int64)
+        weight = np.zeros(dev.L, np.float64)
+        if loci_u is None:
+            weight[:] = _sgs.locus_terms(s_l, n)[0]
+        else:
+            s_l = s_l[loci_u]
+            weight[loci_u] = _sgs.locus_terms(s_l, n)[0]
+        obs = dev.sgs_sums(edges, slots, mask, weight, None, max_work)
+        pI = pS = None
+        if nperm:
+            rows = _mmrr.draw_row_shuffles(n, int(nperm), seed=seed, rng=self._rng)
+            pI = np.empty((int(nperm),) + obs['isums'].shape, np.int64)
+            pS = np.empty((int(nperm),) + obs['fsums'].shape, np.float64)
+            for p, r in enumerate(rows):                  # position i takes the genome of r[i]
+                got = dev.sgs_sums(edges, slots, mask, weight, r.astype(np.int32), max_work)
+                pI[p], pS[p] = got['isums'], got['fsums']
+        out = _sgs.spatial_structure(obs['isums'], obs['fsums'], s_l, n, fit_range, pI, pS)
+        out.update(edges=edges, n_zero=obs['n_zero'], work=work, ids=ids)
+        return out
+
     # -- lineages through the recorded pedigree (structs/pedigree.py; csrc/gnx_lineage.hip) ----
     # The reference simplifies its tables with tskit's default, which drops unary nodes: its
     # lineage at a locus lists only the ancestors that survive simplification for the current

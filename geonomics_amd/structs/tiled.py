@@ -68,6 +68,12 @@ class TiledSpecies(Species):
         raise NotImplementedError('run_mantel with a Species tiled over several GPUs is not '
                                   'implemented; run the model on one GPU')
 
+    # -- spatial genetic structure: not over tiles (pairs across a tile border: the border
+    # cells of the neighbours' samples would have to be exchanged)
+    def _calc_spatial_structure(self, *args, **kw):
+        raise NotImplementedError('calc_spatial_structure with a Species tiled over several '
+                                  'GPUs is not implemented; run the model on one GPU')
+
     # -- lineages: not over tiles (each rank records its own births: the pedigree of a tiled
     # Species is in pieces, and a lineage crosses them)
     def _get_lineage_dicts(self, *args, **kw):

@@ -698,6 +698,37 @@ int gnx_dist_perm_sums(gnx_state* h, int64_t n, const int64_t* slots, const uint
                        int32_t n_pred, const int32_t* pred_off, const int32_t* pred_cols,
                        int32_t n_perm, const int32_t* perm, double* sums, double* moments);
 
+/* ---- fine-scale spatial genetic structure (csrc/gnx_sgs.hip; the reference has no such
+ *      analysis: its IBD demo, demos/_IBD_IBE.py, ends at MMRR on a sample) ----------------
+ * The sums over the pairs of individuals closer than the largest distance class, from which mean
+ * kinship per class, its slope on ln(distance), Sp and the neighbourhood size follow
+ * (geonomics_amd/sim/sgs.py).  n, slots, locus_mask and the preconditions as gnx_geno_gram, but
+ * no n x n matrix is formed: 1..2^24 individuals.  edges double [n_bins + 1], finite, strictly
+ * ascending, edges[0] >= 0; 1..32 classes.  For a pair a != b of the sample, dx and dy are the
+ * fp64 differences of the device's fp32 x and y, r = sqrt(dx dx + dy dy) in fp64 without
+ * contraction (IEEE sqrt); the pair is in class k when edges[k] <= r < edges[k + 1]; pairs with
+ * r == 0 are in no class and are counted in *n_zero; every unordered pair is visited once.  d is
+ * the dosage (0, 1, 2) at the masked loci; with perm int32 [n] sample index i stands at its own
+ * position with the genome of sample index perm[i].  dot_ab = sum_l d_al d_bl, self_a = sum_l
+ * d_al^2, w_a = sum_l locus_weight[l] d_al (double [L]; fp64, loci ascending; NULL: 0).
+ * HOST outputs:  isums int64 [n_bins][3] = {pairs, sum dot_ab, sum (self_a + self_b)}, exact;
+ * fsums double [n_bins][7] = {sum r, sum ln r, sum ln^2 r, sum dot_ab ln r,
+ * sum (self_a + self_b) ln r, sum (w_a + w_b), sum (w_a + w_b) ln r}.  The fp64 sums are taken
+ * without atomics in an order that the sample, the edges and the landscape fix (they do depend
+ * on that order, within the usual m 2^-53 sum |term|): a call repeated is bit-equal in all
+ * outputs.  *work = the candidate pairs (every pair of individuals in the same or adjacent cells
+ * of a grid whose side is just above edges[n_bins], larger where the landscape would have more
+ * than 2^22 cells) times the number of words the mask touches; it is known after the cell sort
+ * and before the operand is gathered.  max_work <= 0: only *work is written (isums, fsums and
+ * n_zero may be NULL).  Refused (return 1) before anything is launched: bad edges, n_bins or n,
+ * a slot out of range, a perm entry outside 0..n-1, n (n - 1) / 2 * 8 L >= 2^63; after the cell
+ * sort and before anything else: *work > max_work.  Nothing of the handle changes.          */
+int gnx_sgs_sums(gnx_state* h, int64_t n, const int64_t* slots, const uint64_t* locus_mask,
+                 int32_t n_bins, const double* edges /*[n_bins + 1]*/,
+                 const double* locus_weight /*[L] or NULL*/, const int32_t* perm /*[n] or NULL*/,
+                 int64_t max_work, int64_t* work, int64_t* isums /*[n_bins][3]*/,
+                 double* fsums /*[n_bins][7]*/, int64_t* n_zero);
+
 /* ---- lineages through the recorded pedigree (csrc/gnx_lineage.hip; reference
  *      structs/genome.py:1638-1782 _get_lineage_dicts, structs/species.py:1242-1343) ---------
  * The pedigree is recorded on the host (geonomics_amd/structs/pedigree.py, TreeTables.
