@@ -67,6 +67,7 @@ EXPORTS = [
     'gnx_lineage_trace', 'gnx_lineage_chains', 'gnx_lineage_budget', 'gnx_lineage_info',
     'gnx_pedigree_reach', 'gnx_lineage_forget', 'gnx_dist_perm_sums',
     'gnx_stats_group_counts', 'gnx_sgs_sums',
+    'gnx_ld_bins', 'gnx_ld_budget', 'gnx_ld_info',
 ]
 
 
@@ -1153,6 +1154,49 @@ class Device:
         if max_work <= 0:
             return dict(work=int(work[0]), isums=None, fsums=None, n_zero=None)
         return dict(work=int(work[0]), isums=isums, fsums=fsums, n_zero=int(nz[0]))
+
+    # -- genome-wide linkage disequilibrium (csrc/gnx_ld.hip) ------------------------------
+    def ld_bins(self, loci, pos, edges, slots=None, min_minor=1, morgans=False, max_work=0):
+        """per bin of pos[j] - pos[i] the locus pairs and the sums of r^2, r^4, the distance and
+        the drift weight over the kept pairs of `loci` (include/gnx_hip.h, gnx_ld_bins).  loci
+        int32 [n_loci] distinct; pos float64 [n_loci] non-decreasing; edges float64 [2..65]
+        ascending, the last may be inf.  max_work <= 0: only the work is computed.
+        -> dict(work, c1 int64 [n_loci], pairs int64 [n_bins], sum_r2, sum_r4, sum_d, sum_w
+        float64 [n_bins]); all but work are None when max_work <= 0"""
+        s, n = self._geno_slots(slots)
+        loci = _arr(loci, np.int32).ravel()
+        pos = _arr(pos, np.float64).ravel()
+        if pos.size != loci.size:
+            raise ValueError('pos: %d entries for %d loci' % (pos.size, loci.size))
+        e = _arr(edges, np.float64).ravel()
+        nb = int(e.size) - 1
+        rows = nb if 1 <= nb <= 64 else 0         # (the library refuses the rest before it writes)
+        c1 = np.zeros(loci.size, np.int64)
+        pairs = np.zeros(rows, np.int64)
+        fs = np.zeros((rows, 4), np.float64)
+        work = np.zeros(1, np.int64)
+        self._chk(self.lib.gnx_ld_bins(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), C.c_int32(int(loci.size)),
+            _ptr(loci if loci.size else np.zeros(1, np.int32), C.c_int32),
+            _ptr(pos if pos.size else np.zeros(1), C.c_double), C.c_int32(int(e.size)),
+            _ptr(e if e.size else np.zeros(1), C.c_double), C.c_int32(int(min_minor)),
+            C.c_int32(int(bool(morgans))), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
+            _ptr(c1, C.c_int64), _ptr(pairs, C.c_int64), _ptr(fs, C.c_double)))
+        if max_work <= 0:
+            return dict(work=int(work[0]), c1=None, pairs=None, sum_r2=None, sum_r4=None,
+                        sum_d=None, sum_w=None)
+        return dict(work=int(work[0]), c1=c1, pairs=pairs, sum_r2=fs[:, 0].copy(),
+                    sum_r4=fs[:, 1].copy(), sum_d=fs[:, 2].copy(), sum_w=fs[:, 3].copy())
+
+    def ld_budget(self, n_bytes):
+        """bytes of transposed bit rows ld_bins keeps resident (0: the default, 256 MiB)"""
+        self._chk(self.lib.gnx_ld_budget(self.h, C.c_int64(int(n_bytes))))
+
+    def ld_info(self):
+        """of the last ld_bins: dict(kernel_ms, launches, locus_blocks)"""
+        ms, n, nb = C.c_double(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.gnx_ld_info(self.h, C.byref(ms), C.byref(n), C.byref(nb)))
+        return dict(kernel_ms=ms.value, launches=int(n.value), locus_blocks=int(nb.value))
 
     # -- lineages through the recorded pedigree (csrc/gnx_lineage.hip) -------------------
     @staticmethod

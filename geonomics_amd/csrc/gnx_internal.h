@@ -354,6 +354,12 @@ struct gnx_state {
   double lin_ms = 0.0;           // kernel time, launches and upload of the last call
   int64_t lin_launches = 0, lin_uploaded = 0;
 
+  // linkage disequilibrium (gnx_ld.hip): bytes of transposed bit rows resident at a time (0: the
+  // default), and the kernel time, launches and locus blocks of the last call
+  int64_t ld_budget = 0;
+  double ld_ms = 0.0;
+  int64_t ld_launches = 0, ld_blocks = 0;
+
   // traits etc
   GnxTrait traits[GNX_MAX_TRAITS];
   // selected loci: all trait loci concatenated trait-major (n_tl of them), then the

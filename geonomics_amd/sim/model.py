@@ -934,6 +934,34 @@ class Model:
             individs=self._test_sample(spp, individs, n), loci=loci, nperm=nperm, seed=seed,
             fit_range=fit_range, max_work=max_work)
 
+    def calc_ld_decay(self, spp=0, edges=None, n_bins=20, unit='c', max_dist=None,
+                      individs=None, n=None, loci=None, min_maf=0.05, max_work=None):
+        """the decay of linkage disequilibrium with distance, genome-wide (an extension: the
+        reference's 'ld' statistic is an L x L matrix): mean r^2 over the pairs of loci in each
+        bin of recombination fraction (unit 'c', from the architecture's recombination rates),
+        map distance ('morgans') or locus separation ('loci'), computed on the device for any
+        number of loci.  edges: the bins' bounds (default n_bins bins up to max_dist).
+        individs, or a random sample of n, and loci restrict the analysis; loci below min_maf
+        in the sample are left out.  max_work bounds the tile-words of the device call; a
+        request above it raises ValueError.
+        -> dict: edges, pairs, mean_r2, sd_r2, mean_dist, mean_c, expected_w (arrays over the
+        bins; E[mean_r2] ~ expected_w / N_e + 1 / n_chrom), n_chrom, n_loci_kept, c1, loci,
+        ids, work"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_ld_decay(edges=edges, n_bins=n_bins, unit=unit, max_dist=max_dist,
+                                  individs=self._test_sample(spp, individs, n), loci=loci,
+                                  min_maf=min_maf, max_work=max_work)
+
+    def calc_ne(self, spp=0, method='ld', min_c=0.05, min_maf=0.05, individs=None, n=None,
+                loci=None):
+        """the linkage-disequilibrium estimate of the effective population size (Waples 2006;
+        Weir & Hill 1980) from every pair of loci at recombination fraction >= min_c, computed
+        on the device.  No confidence interval.
+        -> dict: Ne, mean_r2, r2_drift, pairs, n_chrom, n_loci_kept, min_c"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_ne(method=method, min_c=min_c, min_maf=min_maf,
+                            individs=self._test_sample(spp, individs, n), loci=loci)
+
     # -- Fst, diversity and the SFS of groups of individuals (sim/fst.py) ----------------
     def calc_fst(self, groups, spp=0, loci=None, method='HsHt', mean=True, est_Hs=False,
                  include_zeros=False):

@@ -13,7 +13,9 @@ at the last timestep with 5-decimal floats (utils/io.py:126-168).
 Not kept: _plot_stat (plotting is outside the hot path).
 Added: the stat 'fst' (params: calc, freq, method, and either 'grid': (nx, ny) or 'lyr' and
 'edges'): the mean Fst of every pair of groups (sim/fst.py, from gnx_stats_group_counts), one
-row per sampled timestep in ..._FST.csv.
+row per sampled timestep in ..._FST.csv; the stat 'ne' (params: calc, freq, optionally min_c and
+min_maf): the linkage-disequilibrium estimate of the effective population size (sim/ld.py, from
+gnx_ld_bins), a column of OTHER_STATS.csv like 'Nt'.
 """
 import csv
 import os
@@ -108,6 +110,12 @@ def _calc_fst(spp, method='HsHt', grid=None, lyr=None, edges=None):
     return ['%s-%s' % k for k in res], [*res.values()]
 
 
+def _calc_ne(spp, min_c=0.05, min_maf=0.05):
+    """the LD estimate of the effective population size (Species._calc_ne): inf when the sample
+    size explains all the r^2 there is, NaN without a pair of loci to take it from"""
+    return float(spp._calc_ne(min_c=min_c, min_maf=min_maf)['Ne'])
+
+
 _OTHER = 'OTHER_STATS.csv'
 
 
@@ -121,10 +129,10 @@ def _fmt(v):
 
 class _StatsCollector:
     calc_fn_dict = {'Nt': _calc_Nt, 'ld': _calc_ld, 'het': _calc_het, 'maf': _calc_maf,
-                    'mean_fit': _calc_mean_fitness, 'fst': _calc_fst}
+                    'mean_fit': _calc_mean_fitness, 'fst': _calc_fst, 'ne': _calc_ne}
     file_suffix_dict = {'Nt': _OTHER, 'ld': 'LD.txt', 'het': 'HET.csv', 'maf': 'MAF.csv',
-                        'mean_fit': _OTHER, 'fst': 'FST.csv'}
-    _needs_genome = ('ld', 'het', 'maf', 'mean_fit', 'fst')
+                        'mean_fit': _OTHER, 'fst': 'FST.csv', 'ne': _OTHER}
+    _needs_genome = ('ld', 'het', 'maf', 'mean_fit', 'fst', 'ne')
 
     def __init__(self, model_name, params):
         self.model_name = model_name

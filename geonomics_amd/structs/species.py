@@ -1249,6 +1249,125 @@ class Species:
         out.update(edges=edges, n_zero=obs['n_zero'], work=work, ids=ids)
         return out
 
+    # -- genome-wide linkage disequilibrium (sim/ld.py; csrc/gnx_ld.hip) ---------------------
+    # tile-words (64 x 64-locus tiles x chromosome words) one call may take; a tile-word is 4096
+    # pair-words of the popcount tile, so this is four times _SGS_MAX_WORK
+    _LD_MAX_WORK = 1 << 33
+
+    def _ld_request(self, who, individs, loci, unit, min_maf):
+        """(ids, slots, loci ascending, their coordinates for the device, min_minor) of an LD
+        request"""
+        from ..sim import ld as _ld
+        if self.gen_arch is None or self._dev.L == 0:
+            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
+        if not self.__dict__.get('_genomes_assigned', False):
+            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
+                             'model in first' % who)
+        if unit not in ('c', 'morgans', 'loci'):
+            raise ValueError("%s: unit: 'c', 'morgans' or 'loci', not %r" % (who, unit))
+        ids, slots = self._geno_sample(individs)
+        if ids.size < 1 or ids.size > 2 ** 25:
+            raise ValueError('%s: 1..2^25 individuals per call (got %d): sample them with n=... '
+                             'or individs=...' % (who, ids.size))
+        loci_u, _ = self._geno_loci(loci)
+        if loci_u is None:
+            loci_u = np.arange(self._dev.L, dtype=np.int64)
+        if unit == 'loci':
+            pos = loci_u.astype(np.float64)
+        else:
+            rec = self.gen_arch.recombinations
+            rates = np.zeros(self._dev.L)
+            rates[rec._positions] = rec._rates
+            pos = _ld.map_positions(rates)[loci_u]
+        return ids, slots, loci_u, pos, _ld.min_minor(min_maf, 2 * ids.size)
+
+    def _ld_call(self, who, loci, pos, edges, slots, min_minor, morgans, max_work):
+        """one gnx_ld_bins call; the library's refusal of a request above max_work (it comes
+        before anything is launched) becomes a ValueError with advice"""
+        try:
+            return self._dev.ld_bins(loci, pos, edges, slots, min_minor, morgans, max_work)
+        except nat.GnxError as err:
+            if 'exceed max_work' not in str(err):
+                raise
+            raise ValueError('%s: %s: analyse a sample (n=...), fewer loci (loci=...) or a '
+                             'smaller max_dist, or raise max_work' % (who, err)) from None
+
+    def _calc_ld_decay(self, edges=None, n_bins=20, unit='c', max_dist=None, individs=None,
+                       loci=None, min_maf=0.05, max_work=None):
+        """the decay of linkage disequilibrium with distance: mean r^2 over the pairs of loci in
+        each distance bin, for all loci of the living individuals asked for (all by default), on
+        the device (gnx_ld_bins: no L x L matrix, any number of loci).  unit: 'c', the
+        recombination fraction between the two loci under the architecture's rates (sim/ld.py;
+        edges in c, an upper edge >= 0.5 taking in every looser pair); 'morgans', their map
+        distance; 'loci', the difference of their locus numbers.  edges: the bins' bounds
+        (default sim/ld.default_edges(unit, n_bins, max_dist)).  Loci whose minor-allele
+        frequency in the sample is below min_maf are left out.  max_work: the tile-words (tiles
+        of 64 x 64 loci x words of 64 chromosomes) the call may take
+        -> dict: edges, pairs, mean_r2, sd_r2, mean_dist (Morgans for 'c'), mean_c (c at the mean
+        map distance; NaN for 'loci'), expected_w (the mean of Weir & Hill's w(c), so that
+        E[mean_r2] ~ expected_w / N_e + 1 / n_chrom; inf in a bin holding a pair at distance 0;
+        NaN for 'loci'), n_chrom, n_loci_kept, c1 (1-alleles per locus), loci, ids, work"""
+        from ..sim import ld as _ld
+        who = 'calc_ld_decay'
+        ids, slots, loci_u, pos, mm = self._ld_request(who, individs, loci, unit, min_maf)
+        if edges is None:
+            edges = _ld.default_edges(unit, n_bins, max_dist, loci_u.size)
+        elif max_dist is not None:
+            raise ValueError('%s: give edges or max_dist, not both' % who)
+        edges = _ld.check_edges(edges)
+        dev_edges = _ld.c_to_morgans(edges) if unit == 'c' else edges
+        if unit == 'c' and ((edges < 0).any() or (edges[:-1] >= 0.5).any()):
+            raise ValueError('%s: edges in c lie in 0..0.5, at most the last at or above 0.5 '
+                             '(got %r)' % (who, edges.tolist()))
+        if max_work is None:
+            max_work = self._LD_MAX_WORK
+        if isinstance(max_work, bool) or int(max_work) != max_work or max_work < 1:
+            raise ValueError('%s: max_work: a positive number of tile-words (got %r)'
+                             % (who, max_work))
+        morgans = unit != 'loci'
+        got = self._ld_call(who, loci_u, pos, dev_edges, slots, mm, morgans, max_work)
+        work = got['work']
+        out = _ld.decay_stats(got['pairs'], got['sum_r2'], got['sum_r4'], got['sum_d'],
+                              got['sum_w'], morgans)
+        n_chrom = 2 * ids.size
+        c1 = got['c1']
+        out.update(edges=edges, pairs=got['pairs'], n_chrom=n_chrom,
+                   n_loci_kept=int((np.minimum(c1, n_chrom - c1) >= mm).sum()), c1=c1,
+                   loci=loci_u, ids=ids, work=work)
+        return out
+
+    def _calc_ne(self, method='ld', min_c=0.05, min_maf=0.05, individs=None, loci=None):
+        """the linkage-disequilibrium estimate of the effective population size (Waples 2006;
+        Weir & Hill 1980) from every pair of loci with recombination fraction >= min_c under the
+        architecture's rates (0.5: unlinked pairs only), in one device call:
+        N_e = mean w(c) / (mean r^2 - 1 / n_chrom) (sim/ld.ld_ne), for phase-known gametes under
+        random mating.  inf when the sample's own 1 / n_chrom explains all the r^2 there is, NaN
+        without pairs.  Confidence intervals are out of scope.  The call takes every tile of loci
+        at or beyond min_c, up to _LD_MAX_WORK tile-words (above it: ValueError; pass individs
+        or loci).
+        -> dict: Ne, mean_r2, r2_drift (mean_r2 - 1 / n_chrom), pairs, n_chrom, n_loci_kept,
+        min_c"""
+        from ..sim import ld as _ld
+        who = 'calc_ne'
+        if method != 'ld':
+            raise ValueError("%s: method: 'ld' (got %r)" % (who, method))
+        if not 0.0 <= float(min_c) <= 0.5:
+            raise ValueError('%s: min_c: a recombination fraction in 0..0.5 (got %r)'
+                             % (who, min_c))
+        ids, slots, loci_u, pos, mm = self._ld_request(who, individs, loci, 'c', min_maf)
+        # across a break the map puts BREAK_MORGANS: half of it already gives c = 0.5 exactly
+        lo = min(float(_ld.c_to_morgans(float(min_c))), _ld.BREAK_MORGANS / 2)
+        got = self._ld_call(who, loci_u, pos, np.array([lo, np.inf]), slots, mm, True,
+                            self._LD_MAX_WORK)
+        n_chrom = 2 * ids.size
+        m = int(got['pairs'][0])
+        mean = float(got['sum_r2'][0]) / m if m else float('nan')
+        c1 = got['c1']
+        return dict(Ne=_ld.ld_ne(m, got['sum_r2'][0], got['sum_w'][0], n_chrom), mean_r2=mean,
+                    r2_drift=mean - 1.0 / n_chrom, pairs=m, n_chrom=n_chrom,
+                    n_loci_kept=int((np.minimum(c1, n_chrom - c1) >= mm).sum()),
+                    min_c=float(min_c))
+
     # -- lineages through the recorded pedigree (structs/pedigree.py; csrc/gnx_lineage.hip) ----
     # The reference simplifies its tables with tskit's default, which drops unary nodes: its
     # lineage at a locus lists only the ancestors that survive simplification for the current

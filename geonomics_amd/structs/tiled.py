@@ -74,6 +74,14 @@ class TiledSpecies(Species):
         raise NotImplementedError('calc_spatial_structure with a Species tiled over several '
                                   'GPUs is not implemented; run the model on one GPU')
 
+    def _calc_ld_decay(self, *args, **kw):
+        raise NotImplementedError('calc_ld_decay with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
+    def _calc_ne(self, *args, **kw):
+        raise NotImplementedError('calc_ne with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
     # -- lineages: not over tiles (each rank records its own births: the pedigree of a tiled
     # Species is in pieces, and a lineage crosses them)
     def _get_lineage_dicts(self, *args, **kw):

@@ -729,6 +729,46 @@ int gnx_sgs_sums(gnx_state* h, int64_t n, const int64_t* slots, const uint64_t* 
                  int64_t max_work, int64_t* work, int64_t* isums /*[n_bins][3]*/,
                  double* fsums /*[n_bins][7]*/, int64_t* n_zero);
 
+/* ---- genome-wide linkage disequilibrium (csrc/gnx_ld.hip; the reference's _calc_ld,
+ *      sim/stats.py:359-390, is gnx_stats_ld above: an L x L matrix, at most 8192 loci) --------
+ * Per bin of the distance between two loci: the number of locus pairs and the sums of r^2, r^4,
+ * the distance and Weir & Hill's drift weight, from which the decay of r^2 with distance and the
+ * LD estimate of N_e follow (geonomics_amd/sim/ld.py).  Nothing n_loci x n_loci is formed.
+ * n, slots as gnx_geno_gram (1..2^25 individuals; slots distinct); the sample's chromosomes are
+ * 2 * sample index + homologue, N = 2 n of them.  loci int32 [n_loci], distinct, in any order of
+ * locus number; pos double [n_loci], finite and non-decreasing: the coordinate of loci[j] (the
+ * caller's unit).  edges double [n_edges], 2..65 of them, strictly ascending, finite but for the
+ * last, which may be +inf.  c1[j] = the 1-alleles of loci[j] over the N chromosomes; a locus is
+ * KEPT iff min(c1, N - c1) >= max(1, min_minor).  For kept loci i < j (indices of the request),
+ * c_ij = the chromosomes carrying 1 at both, in fp64 without contraction:
+ *   Dn = N c_ij - c_i c_j (int64, exact);  r2 = (Dn Dn) / ((c_i (N - c_i)) (c_j (N - c_j))), each
+ *   bracket exact, three IEEE roundings;  d = pos[j] - pos[i];  the pair is in bin b when
+ *   edges[b] <= d < edges[b + 1], in no bin otherwise;  with morgans != 0:
+ *   c = 0.5 |expm1(-2 d)| (= -0.5 expm1(-2 d), and +0 at d = 0 whatever zero expm1 returns),
+ *   w = ((1 - c)(1 - c) + c c) / ((2 c)(2 - c)), else w = 0.
+ * A pair at d = 0 has w = +inf under morgans, and so has the sum of its bin: not special-cased.
+ * HOST outputs: c1 int64 [n_loci], pairs int64 [n_edges - 1], fsums double [n_edges - 1][4] =
+ * {sum r2, sum r2 r2, sum d, sum w}.  The fp64 sums are taken without atomics in an order fixed
+ * by the arguments and gnx_ld_budget: a call repeated is bit-equal in all outputs.  *work = the
+ * 64 x 64-locus tiles whose distance range meets [edges[0], edges[last]) times the chromosome
+ * words ceil(N / 64); max_work <= 0: only *work is written (the outputs may be NULL).  Refused
+ * (return 1) before anything is launched: no genomes, ghost records, n out of range, a slot or
+ * locus out of range or listed twice, pos not non-decreasing, bad edges, *work > max_work.
+ * Nothing of the handle changes.                                                            */
+int gnx_ld_bins(gnx_state* h, int64_t n, const int64_t* slots, int32_t n_loci,
+                const int32_t* loci, const double* pos /*[n_loci]*/, int32_t n_edges,
+                const double* edges /*[n_edges]*/, int32_t min_minor, int32_t morgans,
+                int64_t max_work, int64_t* work, int64_t* c1 /*[n_loci]*/,
+                int64_t* pairs /*[n_edges - 1]*/, double* fsums /*[n_edges - 1][4]*/);
+/* bytes of transposed bit rows (loci rounded up to 64 x ceil(N / 64) rounded up to 16 x 8)
+ * gnx_ld_bins keeps resident: above it
+ * the loci are worked off in blocks of whole 64-locus tiles, two blocks at a time (0: the
+ * default, 256 MiB)                                                                          */
+int gnx_ld_budget(gnx_state* h, int64_t bytes);
+/* of the last gnx_ld_bins: its kernels' HIP-event time (ms), their number and the number of
+ * locus blocks; each may be NULL                                                             */
+int gnx_ld_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* locus_blocks);
+
 /* ---- lineages through the recorded pedigree (csrc/gnx_lineage.hip; reference
  *      structs/genome.py:1638-1782 _get_lineage_dicts, structs/species.py:1242-1343) ---------
  * The pedigree is recorded on the host (geonomics_amd/structs/pedigree.py, TreeTables.
