@@ -68,6 +68,7 @@ EXPORTS = [
     'gnx_pedigree_reach', 'gnx_lineage_forget', 'gnx_dist_perm_sums',
     'gnx_stats_group_counts', 'gnx_sgs_sums',
     'gnx_ld_bins', 'gnx_ld_budget', 'gnx_ld_info',
+    'gnx_tracts_self', 'gnx_tracts_pairs', 'gnx_tracts_info',
 ]
 
 
@@ -1197,6 +1198,79 @@ class Device:
         ms, n, nb = C.c_double(), C.c_int64(), C.c_int64()
         self._chk(self.lib.gnx_ld_info(self.h, C.byref(ms), C.byref(n), C.byref(nb)))
         return dict(kernel_ms=ms.value, launches=int(n.value), locus_blocks=int(nb.value))
+
+    # -- identity tracts of the phased genomes (csrc/gnx_tracts.hip) ------------------------
+    def _tract_args(self, pos, brk, edges):
+        pos = _arr(pos, np.int64).ravel()
+        if pos.size != self.L:
+            raise ValueError('pos: %d entries, not L = %d' % (pos.size, self.L))
+        b = None
+        if brk is not None:
+            b = _arr(brk, np.uint64).ravel()
+            if b.size != self.W64:
+                raise ValueError('brk: %d words, not %d' % (b.size, self.W64))
+        e, hist = None, None
+        if edges is not None:
+            e = _arr(edges, np.int64).ravel()
+            # (the library refuses fewer than 2 and more than 65 edges before it writes)
+            hist = np.zeros((e.size - 1 if 2 <= e.size <= 65 else 1, 2), np.int64)
+            if e.size == 0:
+                e = np.zeros(1, np.int64)
+        return pos, b, e, hist
+
+    def tracts_self(self, pos, brk=None, min_loci=1, min_len=0, edges=None, slots=None,
+                    cover=False):
+        """runs of homozygosity: the tracts over which homologue 0 and homologue 1 of each of
+        `slots` (all living slots by default) are identical (include/gnx_hip.h,
+        gnx_tracts_self).  pos int64 [L] non-decreasing; brk uint64 [W64] or None; edges int64
+        [2..65] ascending or None
+        -> dict(per int64 [n][4] = {tracts, loci, length, longest}, hist int64 [n_bins][2] or
+        None, cover int64 [L] or None)"""
+        s, n = self._geno_slots(slots)
+        pos, b, e, hist = self._tract_args(pos, brk, edges)
+        # (the library refuses n outside 1..2^25 before it writes)
+        per = np.zeros((n if 1 <= n <= 2 ** 25 else 1, 4), np.int64)
+        cov = np.zeros(self.L, np.int64) if cover else None
+        self._chk(self.lib.gnx_tracts_self(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(pos, C.c_int64), _ptr(b, C.c_uint64),
+            C.c_int32(int(min_loci)), C.c_int64(int(min_len)),
+            C.c_int32(0 if edges is None else int(np.size(edges))), _ptr(e, C.c_int64),
+            _ptr(per, C.c_int64), _ptr(hist, C.c_int64), _ptr(cov, C.c_int64)))
+        return dict(per=per, hist=hist, cover=cov)
+
+    def tracts_pairs(self, pos, brk=None, min_loci=1, min_len=0, edges=None, slots=None,
+                     cover=False, max_work=0):
+        """tracts shared between the haplotypes of every two of `slots` (at most 4096;
+        include/gnx_hip.h, gnx_tracts_pairs); the diagonal is the individual's own pair.
+        max_work <= 0: only the work is computed
+        -> dict(work, cnt int32 [n][n], len, longest int64 [n][n], hist, cover); all but work
+        are None when max_work <= 0"""
+        s, n = self._geno_slots(slots)
+        pos, b, e, hist = self._tract_args(pos, brk, edges)
+        run = max_work > 0 and 1 <= n <= 4096
+        m = n if run else 1
+        cnt = np.zeros((m, m), np.int32)
+        tot = np.zeros((m, m), np.int64)
+        longest = np.zeros((m, m), np.int64)
+        cov = np.zeros(self.L, np.int64) if cover else None
+        work = np.zeros(1, np.int64)
+        self._chk(self.lib.gnx_tracts_pairs(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(pos, C.c_int64), _ptr(b, C.c_uint64),
+            C.c_int32(int(min_loci)), C.c_int64(int(min_len)),
+            C.c_int32(0 if edges is None else int(np.size(edges))), _ptr(e, C.c_int64),
+            C.c_int64(int(max_work)), _ptr(work, C.c_int64), _ptr(cnt, C.c_int32),
+            _ptr(tot, C.c_int64), _ptr(longest, C.c_int64), _ptr(hist, C.c_int64),
+            _ptr(cov, C.c_int64)))
+        if max_work <= 0:
+            return dict(work=int(work[0]), cnt=None, len=None, longest=None, hist=None,
+                        cover=None)
+        return dict(work=int(work[0]), cnt=cnt, len=tot, longest=longest, hist=hist, cover=cov)
+
+    def tracts_info(self):
+        """of the last tracts_self / tracts_pairs: dict(kernel_ms, launches, bytes_read)"""
+        ms, n, nb = C.c_double(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.gnx_tracts_info(self.h, C.byref(ms), C.byref(n), C.byref(nb)))
+        return dict(kernel_ms=ms.value, launches=int(n.value), bytes_read=int(nb.value))
 
     # -- lineages through the recorded pedigree (csrc/gnx_lineage.hip) -------------------
     @staticmethod

@@ -360,6 +360,11 @@ struct gnx_state {
   double ld_ms = 0.0;
   int64_t ld_launches = 0, ld_blocks = 0;
 
+  // identity tracts (gnx_tracts.hip): the kernel time and launches of the last call, and the
+  // genome bytes its scan read (blocks shared by both homologues are not read)
+  double tr_ms = 0.0;
+  int64_t tr_launches = 0, tr_bytes = 0;
+
   // traits etc
   GnxTrait traits[GNX_MAX_TRAITS];
   // selected loci: all trait loci concatenated trait-major (n_tl of them), then the

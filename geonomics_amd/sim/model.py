@@ -962,6 +962,43 @@ class Model:
         return spp._calc_ne(method=method, min_c=min_c, min_maf=min_maf,
                             individs=self._test_sample(spp, individs, n), loci=loci)
 
+    def calc_roh(self, spp=0, min_len=0.01, min_loci=50, unit='morgans', individs=None, n=None,
+                 edges=None, cover=False):
+        """runs of homozygosity and the genomic inbreeding coefficient F_ROH per individual (an
+        extension: the reference has no haplotype-tract analysis), scanned on the device from
+        the phased genomes: the tracts, at least min_len long (in the unit: 'morgans' on the
+        map of the architecture's recombination rates, or 'loci') and min_loci loci, over which
+        the two homologues are identical.  A rate of 0.5 or more is a chromosome boundary; under
+        the template's free recombination every locus is a break, so every tract is one locus
+        long.  individs, or a random sample of n, restrict the analysis.  edges: a histogram of
+        tract lengths; cover: per locus the individuals with a run over it
+        -> dict: ids, n_roh, roh_loci, roh_len, longest, f_roh, mean_f_roh, genome_len, hist (if
+        edges), cover (if asked), unit"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_roh(min_len=min_len, min_loci=min_loci, unit=unit,
+                             individs=self._test_sample(spp, individs, n), edges=edges,
+                             cover=cover)
+
+    def calc_ibs_sharing(self, spp=0, min_len=0.02, min_loci=50, unit='morgans', individs=None,
+                         n=None, edges=None, n_classes=10, max_dist=None, tract_edges=None,
+                         cover=False, max_work=None):
+        """long haplotype tracts shared between individuals by geographic distance (an
+        extension; the recent-dispersal signal that complements calc_spatial_structure): for
+        every two of at most 4096 individuals (individs, or a random sample of n) the tracts at
+        least min_len (in the unit) and min_loci loci long over which a haplotype of the one is
+        identical to a haplotype of the other, scanned on the device, and their summary per
+        distance class (edges, or n_classes classes up to max_dist as calc_spatial_structure).
+        Under the template's free recombination every locus is a break, so every tract is one
+        locus long.  max_work bounds the word steps of the device call; a request above it raises
+        ValueError
+        -> dict: ids, n_tracts, shared_len, longest ([n][n]), by_dist (the per-class table),
+        hist, cover, work, unit"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_ibs_sharing(min_len=min_len, min_loci=min_loci, unit=unit,
+                                     individs=self._test_sample(spp, individs, n), edges=edges,
+                                     n_classes=n_classes, max_dist=max_dist,
+                                     tract_edges=tract_edges, cover=cover, max_work=max_work)
+
     # -- Fst, diversity and the SFS of groups of individuals (sim/fst.py) ----------------
     def calc_fst(self, groups, spp=0, loci=None, method='HsHt', mean=True, est_Hs=False,
                  include_zeros=False):

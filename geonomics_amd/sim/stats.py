@@ -15,7 +15,9 @@ Added: the stat 'fst' (params: calc, freq, method, and either 'grid': (nx, ny) o
 'edges'): the mean Fst of every pair of groups (sim/fst.py, from gnx_stats_group_counts), one
 row per sampled timestep in ..._FST.csv; the stat 'ne' (params: calc, freq, optionally min_c and
 min_maf): the linkage-disequilibrium estimate of the effective population size (sim/ld.py, from
-gnx_ld_bins), a column of OTHER_STATS.csv like 'Nt'.
+gnx_ld_bins), a column of OTHER_STATS.csv like 'Nt'; the stat 'roh' (params: calc, freq,
+optionally min_len in Morgans and min_loci): the mean genomic inbreeding coefficient F_ROH over
+the living individuals (sim/tracts.py, from gnx_tracts_self), a column of OTHER_STATS.csv too.
 """
 import csv
 import os
@@ -116,6 +118,12 @@ def _calc_ne(spp, min_c=0.05, min_maf=0.05):
     return float(spp._calc_ne(min_c=min_c, min_maf=min_maf)['Ne'])
 
 
+def _calc_roh(spp, min_len=0.01, min_loci=50):
+    """the mean F_ROH of the living individuals (Species._calc_roh): the share of the map in
+    runs of homozygosity at least min_len Morgans and min_loci loci long"""
+    return float(spp._calc_roh(min_len=min_len, min_loci=min_loci)['mean_f_roh'])
+
+
 _OTHER = 'OTHER_STATS.csv'
 
 
@@ -129,10 +137,12 @@ def _fmt(v):
 
 class _StatsCollector:
     calc_fn_dict = {'Nt': _calc_Nt, 'ld': _calc_ld, 'het': _calc_het, 'maf': _calc_maf,
-                    'mean_fit': _calc_mean_fitness, 'fst': _calc_fst, 'ne': _calc_ne}
+                    'mean_fit': _calc_mean_fitness, 'fst': _calc_fst, 'ne': _calc_ne,
+                    'roh': _calc_roh}
     file_suffix_dict = {'Nt': _OTHER, 'ld': 'LD.txt', 'het': 'HET.csv', 'maf': 'MAF.csv',
-                        'mean_fit': _OTHER, 'fst': 'FST.csv', 'ne': _OTHER}
-    _needs_genome = ('ld', 'het', 'maf', 'mean_fit', 'fst', 'ne')
+                        'mean_fit': _OTHER, 'fst': 'FST.csv', 'ne': _OTHER,
+                        'roh': _OTHER}
+    _needs_genome = ('ld', 'het', 'maf', 'mean_fit', 'fst', 'ne', 'roh')
 
     def __init__(self, model_name, params):
         self.model_name = model_name

@@ -1368,6 +1368,142 @@ class Species:
                     n_loci_kept=int((np.minimum(c1, n_chrom - c1) >= mm).sum()),
                     min_c=float(min_c))
 
+    # -- identity tracts of the phased genomes (sim/tracts.py; csrc/gnx_tracts.hip) -----------
+    # word steps (haplotype pairs x genome words) one pair scan may take: 4096 individuals at
+    # 10^5 loci are 5.2e10
+    _TRACT_MAX_WORK = 1 << 37
+
+    def _tract_request(self, who, individs, unit, min_len, min_loci, n_max, advice):
+        """(ids, slots, pos, packed breaks, genome_len, min_len in units, min_loci) of a tract
+        request"""
+        from ..sim import tracts as _tr
+        if self.gen_arch is None or self._dev.L == 0:
+            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
+        if not self.__dict__.get('_genomes_assigned', False):
+            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
+                             'model in first' % who)
+        if unit not in ('morgans', 'loci'):
+            raise ValueError("%s: unit: 'morgans' or 'loci', not %r" % (who, unit))
+        if isinstance(min_loci, bool) or int(min_loci) != min_loci or min_loci < 1:
+            raise ValueError('%s: min_loci: a number of loci >= 1 (got %r)' % (who, min_loci))
+        if isinstance(min_len, bool) or not 0 <= float(min_len) < np.inf:
+            raise ValueError('%s: min_len: a finite length >= 0 in %s (got %r)'
+                             % (who, unit, min_len))
+        ids, slots = self._geno_sample(individs)
+        if ids.size < 1 or ids.size > n_max:
+            raise ValueError('%s: 1..%d individuals per call (got %d)%s'
+                             % (who, n_max, ids.size, advice))
+        rec = self.gen_arch.recombinations
+        rates = np.zeros(self._dev.L)
+        rates[rec._positions] = rec._rates
+        pos, brk, genome_len = _tr.tract_map(rates, unit)
+        return (ids, slots, pos, _tr.pack_breaks(brk, self._dev.W64), genome_len,
+                _tr.to_units(min_len, unit), int(min_loci))
+
+    def _tract_edges(self, who, edges, unit):
+        from ..sim import tracts as _tr
+        if edges is None:
+            return None
+        e = np.asarray(edges, dtype=np.float64).ravel()
+        if not 2 <= e.size <= 65 or np.isnan(e).any() or (e < 0).any() or \
+                (np.diff(e) <= 0).any():
+            raise ValueError('%s: tract length edges: 2..65 ascending lengths >= 0 (got %r)'
+                             % (who, edges))
+        return _tr.check_tract_edges([_tr.to_units(v, unit) for v in e])
+
+    def _calc_roh(self, min_len=0.01, min_loci=50, unit='morgans', individs=None, edges=None,
+                  cover=False):
+        """runs of homozygosity: the tracts over which an individual's two homologues are
+        identical, no shorter than min_len (in the unit: Morgans on the architecture's map, or
+        loci) and min_loci loci, for the living individuals asked for (all by default), scanned
+        on the device (gnx_tracts_self).  A recombination rate of 0.5 or more is a chromosome
+        boundary that no tract crosses: under the template's free recombination every locus is
+        a break, so every tract is one locus long.  edges: bounds of a histogram of tract
+        lengths (in the unit; the last may be inf).  cover: per locus, the individuals with a
+        run over it (ROH islands)
+        -> dict: ids, n_roh, roh_loci, roh_len, longest (per individual; lengths in the unit),
+        f_roh (roh_len / genome_len; for 'loci' roh_loci / L), mean_f_roh, genome_len, hist
+        (dict(edges, tracts, sum_len) if edges), cover (if asked), unit"""
+        from ..sim import tracts as _tr
+        who = 'calc_roh'
+        ids, slots, pos, brk, genome_len, ml, mloci = self._tract_request(
+            who, individs, unit, min_len, min_loci, 2 ** 25,
+            ': sample them with n=... or individs=...')
+        e = self._tract_edges(who, edges, unit)
+        got = self._dev.tracts_self(pos, brk, mloci, ml, e, slots, bool(cover))
+        per = got['per']
+        f, mean_f = _tr.roh_stats(per[:, 1], per[:, 2], genome_len, self._dev.L, unit)
+        out = dict(ids=ids, n_roh=per[:, 0].copy(), roh_loci=per[:, 1].copy(),
+                   roh_len=_tr.from_units(per[:, 2], unit),
+                   longest=_tr.from_units(per[:, 3], unit), f_roh=f, mean_f_roh=mean_f,
+                   genome_len=float(_tr.from_units(genome_len, unit)), unit=unit)
+        if e is not None:
+            out['hist'] = dict(edges=np.asarray(edges, dtype=np.float64).ravel(),
+                               tracts=got['hist'][:, 0].copy(),
+                               sum_len=_tr.from_units(got['hist'][:, 1], unit))
+        if cover:
+            out['cover'] = got['cover']
+        return out
+
+    def _calc_ibs_sharing(self, min_len=0.02, min_loci=50, unit='morgans', individs=None,
+                          edges=None, n_classes=10, max_dist=None, tract_edges=None, cover=False,
+                          max_work=None):
+        """long tracts shared identical-by-state between individuals as a function of their
+        geographic distance (the recent-dispersal signal of Ringbauer et al. 2017): for every
+        two of the individuals asked for (at most 4096) the tracts, no shorter than min_len (in
+        the unit) and min_loci loci, over which one haplotype of the one equals one haplotype of
+        the other (four haplotype pairs), scanned on the device (gnx_tracts_pairs).  Under the
+        template's free recombination every locus is a break, so every tract is one locus long.
+        edges: the distance classes' bounds (default n_classes classes of equal width in ln r
+        from one landscape cell to max_dist; default a quarter of the shorter side).
+        tract_edges: bounds of a histogram of tract lengths (in the unit).  cover: per locus, the
+        haplotype pairs with a tract over it.  max_work: the word steps (haplotype pairs x
+        genome words) the call may take
+        -> dict: ids, n_tracts, shared_len, longest ([n][n], the diagonal the individual's own
+        runs of homozygosity; lengths in the unit), by_dist (dict: edges, pairs, mean_tracts,
+        mean_len, share_with_tract, mean_dist per class), hist (or None), cover (or None), work,
+        unit"""
+        from ..sim import sgs as _sgs
+        from ..sim import tracts as _tr
+        who = 'calc_ibs_sharing'
+        ids, slots, pos, brk, _, ml, mloci = self._tract_request(
+            who, individs, unit, min_len, min_loci, 4096,
+            ' (the matrices are n x n): sample them with n=... or individs=...')
+        if edges is None:
+            dim = self._land_ref.dim
+            hi = min(dim) / 4.0 if max_dist is None else float(max_dist)
+            edges = _sgs.default_edges(1.0, hi, n_classes)
+        elif max_dist is not None:
+            raise ValueError('%s: give edges or max_dist, not both' % who)
+        edges = _sgs.check_edges(edges)
+        te = self._tract_edges(who, tract_edges, unit)
+        if max_work is None:
+            max_work = self._TRACT_MAX_WORK
+        if isinstance(max_work, bool) or int(max_work) != max_work or max_work < 1:
+            raise ValueError('%s: max_work: a positive number of word steps (got %r)'
+                             % (who, max_work))
+        try:
+            got = self._dev.tracts_pairs(pos, brk, mloci, ml, te, slots, bool(cover),
+                                         int(max_work))
+        except nat.GnxError as err:
+            if 'exceed max_work' not in str(err):
+                raise
+            raise ValueError('%s: %s: analyse a sample (n=... or individs=...), or raise '
+                             'max_work' % (who, err)) from None
+        x = self._field(nat.F_X)[slots]
+        y = self._field(nat.F_Y)[slots]
+        by = _tr.sharing_stats(x, y, got['cnt'], got['len'], edges)
+        by['mean_len'] = _tr.from_units(by['mean_len'], unit)
+        by['edges'] = edges
+        hist = None
+        if te is not None:
+            hist = dict(edges=np.asarray(tract_edges, dtype=np.float64).ravel(),
+                        tracts=got['hist'][:, 0].copy(),
+                        sum_len=_tr.from_units(got['hist'][:, 1], unit))
+        return dict(ids=ids, n_tracts=got['cnt'], shared_len=_tr.from_units(got['len'], unit),
+                    longest=_tr.from_units(got['longest'], unit), by_dist=by, hist=hist,
+                    cover=got['cover'], work=got['work'], unit=unit)
+
     # -- lineages through the recorded pedigree (structs/pedigree.py; csrc/gnx_lineage.hip) ----
     # The reference simplifies its tables with tskit's default, which drops unary nodes: its
     # lineage at a locus lists only the ancestors that survive simplification for the current

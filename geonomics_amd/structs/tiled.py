@@ -82,6 +82,16 @@ class TiledSpecies(Species):
         raise NotImplementedError('calc_ne with a Species tiled over several GPUs is not '
                                   'implemented; run the model on one GPU')
 
+    # -- identity tracts: not over tiles (a pair of individuals of different tiles: a gather of
+    # the sample)
+    def _calc_roh(self, *args, **kw):
+        raise NotImplementedError('calc_roh with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
+    def _calc_ibs_sharing(self, *args, **kw):
+        raise NotImplementedError('calc_ibs_sharing with a Species tiled over several GPUs is '
+                                  'not implemented; run the model on one GPU')
+
     # -- lineages: not over tiles (each rank records its own births: the pedigree of a tiled
     # Species is in pieces, and a lineage crosses them)
     def _get_lineage_dicts(self, *args, **kw):

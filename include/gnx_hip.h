@@ -769,6 +769,61 @@ int gnx_ld_budget(gnx_state* h, int64_t bytes);
  * locus blocks; each may be NULL                                                             */
 int gnx_ld_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* locus_blocks);
 
+/* ---- identity tracts of the phased genomes (csrc/gnx_tracts.hip; the reference has no such
+ *      analysis) -----------------------------------------------------------------------------
+ * Runs of homozygosity per individual and tracts shared between the haplotypes of two
+ * individuals (geonomics_amd/sim/tracts.py).  Definitions:
+ * A *haplotype pair* is two bit rows a, b of L loci.  D_l = a_l xor b_l for 0 <= l < L.  Padding
+ * bits past L never count and never extend a tract.
+ * `brk` is a bit mask over loci.  Bit l set means that a tract cannot continue from locus l-1
+ * into locus l, i.e. a chromosome boundary.  Bit 0 is ignored.  NULL means no breaks.
+ * A *tract* is a maximal stretch s..e with D_l = 0 for all s <= l <= e and brk_l = 0 for all
+ * s < l <= e.  A locus with D_l = 0 and brk_l = 1 ends one tract at l-1 and starts the next at l.
+ * `pos` is int64 [L], non-decreasing.  It is the locus coordinate in an integer unit chosen by
+ * the caller.
+ *   The tract's *locus count* is e - s + 1.
+ *   Its *length* is pos[e] - pos[s].
+ *   It *qualifies* iff count >= max(1, min_loci) and length >= min_len.
+ * Everything the device returns is an integer function of the qualifying tracts.  Every output is
+ * therefore exact, independent of order (integer atomics are fine), and bit-equal to the
+ * restatement.
+ * Masking loci is deliberately left out.  A monomorphic locus has D = 0 for every pair, so
+ * skipping it would change no tract's extent, only its locus count.
+ *
+ * gnx_tracts_self scans each listed individual's homologue 0 against its homologue 1, for
+ * 1..2^25 individuals (n, slots as gnx_geno_gram; slots distinct).  HOST outputs:
+ *   per[i] = {qualifying tracts, sum of their locus counts, sum of their lengths, the largest
+ *   length (0 without a tract)};
+ *   hist[b] = {tracts, sum of length} over all listed individuals; a tract is in bin b when
+ *   edges[b] <= length < edges[b + 1], in no bin otherwise; edges int64, 2..65 of them, strictly
+ *   ascending (hist NULL: n_edges = 0 and no edges);
+ *   cover[l] = the number of listed individuals with a qualifying tract that contains locus l.
+ * Refused (return 1) before anything is launched: no genomes, ghost records, n out of range, a
+ * slot out of range or listed twice, pos decreasing, bad edges, min_len < 0.  Nothing of the
+ * handle changes.                                                                             */
+int gnx_tracts_self(gnx_state* h, int64_t n, const int64_t* slots /*NULL: all living, n == N*/,
+                    const int64_t* pos /*[L]*/, const uint64_t* brk /*[W64] or NULL*/,
+                    int32_t min_loci, int64_t min_len, int32_t n_edges,
+                    const int64_t* edges /*[n_edges] or NULL*/, int64_t* per /*[n][4]*/,
+                    int64_t* hist /*[n_edges - 1][2] or NULL*/, int64_t* cover /*[L] or NULL*/);
+/* gnx_tracts_pairs takes a sample of 1..4096 individuals.  For a != b the unit is the four
+ * haplotype pairs (a_h, b_g): cnt (qualifying tracts), len (the sum of their lengths) and longest
+ * are summed (max for longest) over the four; they are symmetric, and each may be NULL.  The
+ * diagonal [a][a] is the individual's own pair (a_0, a_1), i.e. what gnx_tracts_self reports for
+ * it.  hist and cover are taken over the off-diagonal unordered pairs only; each haplotype pair
+ * counts once, so cover[l] <= 2 n (n - 1).  *work = (2 n (n - 1) + n) ceil(L / 64) word steps;
+ * max_work <= 0: only *work is written; *work > max_work is refused before the gather.  Other
+ * refusals as gnx_tracts_self.                                                                 */
+int gnx_tracts_pairs(gnx_state* h, int64_t n, const int64_t* slots, const int64_t* pos,
+                     const uint64_t* brk, int32_t min_loci, int64_t min_len, int32_t n_edges,
+                     const int64_t* edges, int64_t max_work, int64_t* work,
+                     int32_t* cnt /*[n][n]*/, int64_t* len /*[n][n]*/, int64_t* longest /*[n][n]*/,
+                     int64_t* hist, int64_t* cover);
+/* of the last gnx_tracts_self / gnx_tracts_pairs: its kernels' HIP-event time (ms), their number
+ * and the genome bytes the scan loaded (gnx_tracts_self: blocks that both homologues share are
+ * not read; gnx_tracts_pairs: the gather's); each may be NULL                                  */
+int gnx_tracts_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* bytes_read);
+
 /* ---- lineages through the recorded pedigree (csrc/gnx_lineage.hip; reference
  *      structs/genome.py:1638-1782 _get_lineage_dicts, structs/species.py:1242-1343) ---------
  * The pedigree is recorded on the host (geonomics_amd/structs/pedigree.py, TreeTables.
