@@ -69,6 +69,8 @@ EXPORTS = [
     'gnx_stats_group_counts', 'gnx_sgs_sums',
     'gnx_ld_bins', 'gnx_ld_budget', 'gnx_ld_info',
     'gnx_tracts_self', 'gnx_tracts_pairs', 'gnx_tracts_info',
+    'gnx_dist_perm_sums_mat',
+    'gnx_cost_surfaces', 'gnx_cost_matrix', 'gnx_cost_budget', 'gnx_cost_info',
 ]
 
 
@@ -1113,6 +1115,87 @@ class Device:
         sxx = sxx + np.triu(sxx, 1).T
         return sums, dict(m=mom[0], sy=mom[1], syy=mom[2], sx=mom[3:3 + k].copy(),
                           sxy=mom[3 + k:3 + 2 * k].copy(), sxx=sxx)
+
+    def dist_perm_sums_mat(self, predictors, mats, perm, slots=None, locus_mask=None):
+        """dist_perm_sums with n x n predictor matrices `mats` (float64 [n_mat][n][n], rows and
+        columns in the order of `slots`; finite, symmetric, zero diagonal) behind the column
+        predictors (which may be empty): sums float64 [n_perm][n_pred + n_mat] and the moments,
+        the columns first"""
+        s, n = self._geno_slots(slots)
+        m = None
+        if locus_mask is not None:
+            m = _arr(locus_mask, np.uint64)
+            if m.size != self.W64:
+                raise ValueError('locus_mask: %d words, not %d' % (m.size, self.W64))
+        predictors = list(predictors)
+        off = np.cumsum([0] + [len(p) for p in predictors]).astype(np.int32)
+        cols = _arr([c for p in predictors for c in p], np.int32).reshape(-1, 2)
+        mats = _arr(mats, np.float64)
+        mats = mats.reshape((0, n, n)) if mats.size == 0 else mats
+        if mats.ndim != 3 or mats.shape[1:] != (n, n):
+            raise ValueError('mats: [n_mat][%d][%d], not %s' % (n, n, mats.shape))
+        k = len(predictors) + mats.shape[0]
+        perm = _arr(perm, np.int32)
+        if perm.ndim != 2 or perm.shape[1] != n:
+            raise ValueError('perm: [n_perm][%d], not %s' % (n, perm.shape))
+        sums = np.zeros((perm.shape[0], k), np.float64)
+        mom = np.zeros(3 + 2 * k + k * (k + 1) // 2, np.float64)
+        self._chk(self.lib.gnx_dist_perm_sums_mat(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), len(predictors),
+            _ptr(off, C.c_int32), _ptr(cols if cols.size else None, C.c_int32),
+            int(mats.shape[0]), _ptr(mats if mats.size else None, C.c_double),
+            int(perm.shape[0]), _ptr(perm, C.c_int32), _ptr(sums, C.c_double),
+            _ptr(mom, C.c_double)))
+        sxx = np.zeros((k, k))
+        sxx[np.triu_indices(k)] = mom[3 + 2 * k:]
+        sxx = sxx + np.triu(sxx, 1).T
+        return sums, dict(m=mom[0], sy=mom[1], syy=mom[2], sx=mom[3:3 + k].copy(),
+                          sxy=mom[3 + k:3 + 2 * k].copy(), sxx=sxx)
+
+    # -- least-cost distances over the landscape (csrc/gnx_cost.hip) -----------------------
+    def _cost_raster(self, R):
+        R = _arr(R, np.float64)
+        if R.shape != (self.cfg.H, self.cfg.W):
+            raise ValueError('R: [%d][%d], not %s' % (self.cfg.H, self.cfg.W, R.shape))
+        return R
+
+    def cost_surfaces(self, R, res, src):
+        """the accumulated-cost raster of every source cell (y * W + x) over the resistance
+        raster R float64 [H][W] (inf: impassable) with cell size res = (res_x, res_y)
+        (include/gnx_hip.h, gnx_cost_surfaces) -> float64 [n_src][H][W]"""
+        R = self._cost_raster(R)
+        src = _arr(src, np.int32).ravel()
+        out = np.zeros((src.size, self.cfg.H, self.cfg.W), np.float64)
+        self._chk(self.lib.gnx_cost_surfaces(
+            self.h, _ptr(R, C.c_double), C.c_double(float(res[0])), C.c_double(float(res[1])),
+            C.c_int32(int(src.size)), _ptr(src if src.size else None, C.c_int32),
+            _ptr(out if out.size else None, C.c_double)))
+        return out
+
+    def cost_matrix(self, R, res, cells):
+        """the pairwise least-cost distances of distinct cells (y * W + x), exactly symmetric
+        (include/gnx_hip.h, gnx_cost_matrix) -> float64 [n_cells][n_cells]"""
+        R = self._cost_raster(R)
+        cells = _arr(cells, np.int32).ravel()
+        n = int(cells.size) if 1 <= cells.size <= 32768 else 0   # the library refuses the rest
+        D = np.zeros((n, n), np.float64)
+        self._chk(self.lib.gnx_cost_matrix(
+            self.h, _ptr(R, C.c_double), C.c_double(float(res[0])), C.c_double(float(res[1])),
+            C.c_int32(int(cells.size)), _ptr(cells if cells.size else None, C.c_int32),
+            _ptr(D if D.size else None, C.c_double)))
+        return D
+
+    def cost_budget(self, n_bytes):
+        """bytes of distance rasters one batch of sources may take (0: the default, 2 GiB)"""
+        self._chk(self.lib.gnx_cost_budget(self.h, C.c_int64(int(n_bytes))))
+
+    def cost_info(self):
+        """of the last cost_surfaces / cost_matrix: dict(kernel_ms, launches, rounds, batches)"""
+        ms, n, r, b = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.gnx_cost_info(self.h, C.byref(ms), C.byref(n), C.byref(r),
+                                         C.byref(b)))
+        return dict(kernel_ms=ms.value, launches=int(n.value), rounds=int(r.value),
+                    batches=int(b.value))
 
     # -- fine-scale spatial genetic structure (csrc/gnx_sgs.hip) ---------------------------
     def sgs_sums(self, edges, slots=None, locus_mask=None, locus_weight=None, perm=None,

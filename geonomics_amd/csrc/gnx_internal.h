@@ -365,6 +365,12 @@ struct gnx_state {
   double tr_ms = 0.0;
   int64_t tr_launches = 0, tr_bytes = 0;
 
+  // least-cost distances (gnx_cost.hip): bytes of distance rasters one batch of sources may
+  // take (0: the default), and the kernel time, launches, rounds and batches of the last call
+  int64_t cost_budget = 0;
+  double cost_ms = 0.0;
+  int64_t cost_launches = 0, cost_rounds = 0, cost_batches = 0;
+
   // traits etc
   GnxTrait traits[GNX_MAX_TRAITS];
   // selected loci: all trait loci concatenated trait-major (n_tl of them), then the

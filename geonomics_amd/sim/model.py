@@ -888,7 +888,9 @@ class Model:
         data/IBD_IBE_demo/MMRR.py, the last step of demos/_IBD_IBE.py): the genetic distances
         between the individuals (get_genetic_distances) regressed on the distances of the
         predictors - 'geo' (x, y), 'env' (the layers env_lyrs; default: the layers the Traits
-        are tied to, or all) and 'phn' (the Traits trts; default: all) - with nperm row-and-column
+        are tied to, or all), 'phn' (the Traits trts; default: all) and 'cost' (least-cost
+        distances as calc_cost_distances, or ('cost', dict(lyr=, kind=, barrier=, cost=, name=));
+        the key is the name, default 'cost') - with nperm row-and-column
         permutations of the genetic matrix, computed on the device.  individs, or a random
         sample of n, and loci restrict the analysis; at most 8192 individuals.  seed: the
         permutations of np.random.seed(seed) followed by the reference's shuffles (default: the
@@ -903,7 +905,7 @@ class Model:
     def run_mantel(self, x='geo', given=None, spp=0, env_lyrs=None, trts=None, individs=None,
                    n=None, loci=None, nperm=999, seed=None):
         """Mantel test of the genetic distances against the distances of predictor x ('geo',
-        'env' or 'phn', as run_mmrr), or the partial test given another predictor (reference
+        'env', 'phn' or 'cost', as run_mmrr), or the partial test given another predictor (reference
         data/IBD_IBE_demo/run_mantel.R: vegan's mantel.partial(gen, env, geo), the genetic
         matrix permuted), computed on the device.
         -> dict(r, p = (1 + #{r_perm >= r}) / (nperm + 1), nperm, perm_r [nperm])"""
@@ -911,6 +913,31 @@ class Model:
         return spp._run_mantel(x=x, given=given, env_lyrs=env_lyrs, trts=trts,
                                individs=self._test_sample(spp, individs, n), loci=loci,
                                nperm=nperm, seed=seed)
+
+    def calc_cost_distances(self, spp=0, lyr=None, kind='conductance', barrier=None, cost=None,
+                            individs=None, n=None):
+        """least-cost distances between the living individuals (an extension: isolation by
+        resistance; sim/cost.py states the graph): the cost of the cheapest path over the
+        landscape's cells, 8 neighbours each, a step between cells u, v costing
+        0.5 (R[u] + R[v]) times its length in units of the landscape's res, solved on the device.
+        R comes from Layer lyr (number or name; default: the Layer of the Species' move_surf):
+        kind='conductance': R = 1 / value, cells with value <= barrier (default 0) impassable;
+        kind='resistance': R = value, cells with value >= barrier impassable when barrier is
+        given; or cost=: an explicit [H][W] raster of R (inf / nan: impassable).  individs, or a
+        random sample of n, as run_mmrr; at most 8192 individuals.  An individual stands on the
+        cell get_cells reports; two on one cell are at cost 0; inf: no path
+        -> dict(ids, cells [n][2], dist float64 [n][n])"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_cost_distances(lyr=lyr, kind=kind, barrier=barrier, cost=cost,
+                                        individs=self._test_sample(spp, individs, n))
+
+    def calc_cost_surface(self, x, y, spp=0, lyr=None, kind='conductance', barrier=None,
+                          cost=None):
+        """the accumulated-cost raster of k points (x, y: scalars or arrays in landscape
+        coordinates, floored to cells as get_cells does) over the resistance raster that
+        calc_cost_distances describes -> float64 [k][H][W] (inf: not reachable)"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_cost_surface(x, y, lyr=lyr, kind=kind, barrier=barrier, cost=cost)
 
     def calc_spatial_structure(self, spp=0, edges=None, n_classes=10, max_dist=None,
                                individs=None, n=None, loci=None, nperm=0, seed=None,

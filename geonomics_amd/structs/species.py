@@ -150,6 +150,54 @@ def _check_introduction_compat(recip, source):
                 % (attr, t))
 
 
+_COST_OPTS = ('lyr', 'kind', 'barrier', 'cost', 'name')
+
+
+def _is_cost_spec(p):
+    return (isinstance(p, (tuple, list)) and len(p) == 2 and isinstance(p[0], str)
+            and p[0] == 'cost' and isinstance(p[1], dict))
+
+
+def _predictor_list(predictors):
+    """the predictors of a Mantel / MMRR request as a list: one name, or one ('cost', opts),
+    stands for itself"""
+    if isinstance(predictors, str) or _is_cost_spec(predictors):
+        return [predictors]
+    return list(predictors)
+
+
+def _split_predictors(spp, who, predictors, env_lyrs, trts):
+    """(names in the caller's order, the device columns of the column predictors in that order
+    (Species._dist_predictors), [(name, opts)] of the cost predictors in that order).  A cost
+    predictor is 'cost' (the defaults of calc_cost_distances) or ('cost', opts) with any of lyr,
+    kind, barrier, cost, name; its name is opts['name'], default 'cost'"""
+    names, col_names, costs = [], [], []
+    for p in _predictor_list(predictors):
+        if isinstance(p, str) and p == 'cost':
+            p = ('cost', {})
+        if _is_cost_spec(p):
+            opts = dict(p[1])
+            extra = sorted(set(opts) - set(_COST_OPTS))
+            if extra:
+                raise ValueError("%s: a 'cost' predictor takes %s, not %s"
+                                 % (who, ', '.join(_COST_OPTS), ', '.join(extra)))
+            name = str(opts.pop('name', 'cost'))
+            costs.append((name, opts))
+            names.append(name)
+        else:
+            col_names.append(p)
+            names.append(p)
+    cols = []
+    if col_names or not costs:
+        _, cols = spp._dist_predictors(who, col_names, env_lyrs, trts)
+    if len(set(names)) != len(names):
+        raise ValueError('%s: a predictor is listed twice' % who)
+    if len(names) > 4:
+        raise ValueError('%s: at most 4 predictors and 8 columns (layers, traits, x, y) '
+                         'together' % who)
+    return names, cols, costs
+
+
 class Species:
     def __init__(self, name, idx, land, spp_params, genomic_architecture=None,
                  seed=0, device=0, rng=None):
@@ -1108,7 +1156,7 @@ class Species:
                     raise ValueError('%s: trts: Traits among %s' % (who, sorted(traits)))
                 cols.append([(nat.F_Z, t) for t in nums])
             else:
-                raise ValueError("%s: unknown predictor %r ('geo', 'env' or 'phn')"
+                raise ValueError("%s: unknown predictor %r ('geo', 'env', 'phn' or 'cost')"
                                  % (who, name))
         if len(set(predictors)) != len(predictors):
             raise ValueError('%s: a predictor is listed twice' % who)
@@ -1116,6 +1164,78 @@ class Species:
             raise ValueError('%s: at most 4 predictors and 8 columns (layers, traits, x, y) '
                              'together' % who)
         return predictors, cols
+
+    # -- least-cost distances (sim/cost.py; csrc/gnx_cost.hip) ------------------------------
+    def _cost_raster(self, who, lyr=None, kind='conductance', barrier=None, cost=None):
+        """the resistance raster R [H][W] of a request (sim/cost.resistance_raster): an explicit
+        cost raster, or the values of Layer lyr (default: the Layer of the move_surf) read as
+        kind"""
+        from ..sim import cost as _cost
+        W, H = self._land_dim
+        if cost is not None:
+            return _cost.resistance_raster(cost=cost, shape=(H, W))
+        land = self._land_ref
+        if lyr is None:
+            if not self._move_surf:
+                raise ValueError('%s: the Species has no move_surf to take the conductance '
+                                 'from: pass lyr=... or cost=...' % who)
+            lyr = self._spp_params.movement.move_surf['layer']
+        if isinstance(lyr, str):
+            nums = [k for k, l in land.items() if l.name == lyr]
+            if len(nums) != 1:
+                raise ValueError('%s: lyr: no single Layer is named %r' % (who, lyr))
+            lyr = nums[0]
+        if isinstance(lyr, bool) or int(lyr) != lyr or int(lyr) not in land:
+            raise ValueError('%s: lyr: a Layer among %s (got %r)' % (who, sorted(land), lyr))
+        return _cost.resistance_raster(land[int(lyr)].rast, kind=kind, barrier=barrier,
+                                       shape=(H, W))
+
+    def _cost_res(self):
+        return abs(float(self._land_res[0])), abs(float(self._land_res[1]))
+
+    def _cost_matrix_of_cells(self, R, cells):
+        """least-cost distances [n][n] of individuals standing on cells [n][2] = (x, y): the
+        distinct cells' matrix from the device, expanded (two individuals on one cell: 0)"""
+        from ..sim import cost as _cost
+        cells = np.asarray(cells, np.int64).reshape(-1, 2)
+        lin = cells[:, 1] * int(self._land_dim[0]) + cells[:, 0]
+        uniq, inverse = np.unique(lin, return_inverse=True)
+        return _cost.expand(self._dev.cost_matrix(R, self._cost_res(), uniq), inverse)
+
+    def _calc_cost_distances(self, lyr=None, kind='conductance', barrier=None, cost=None,
+                             individs=None):
+        """pairwise least-cost distances between the cells of the living individuals asked for
+        (all by default; at most 8192) over the resistance raster of the request, solved on the
+        device -> dict(ids ascending, cells [n][2], dist float64 [n][n])"""
+        who = 'calc_cost_distances'
+        ids, _ = self._geno_sample(individs)
+        if ids.size > 8192:
+            raise ValueError('%s: at most 8192 individuals per call (the distance matrix is '
+                             'n x n), got %d: sample them with n=... or individs=...'
+                             % (who, ids.size))
+        if ids.size < 1:
+            raise ValueError('%s: no individuals' % who)
+        R = self._cost_raster(who, lyr=lyr, kind=kind, barrier=barrier, cost=cost)
+        cells = self._get_cells(individs=ids)
+        return dict(ids=ids, cells=cells, dist=self._cost_matrix_of_cells(R, cells))
+
+    def _calc_cost_surface(self, x, y, lyr=None, kind='conductance', barrier=None, cost=None):
+        """the accumulated-cost raster float64 [k][H][W] of k points (x, y) in landscape
+        coordinates, floored to cells as _get_cells does"""
+        who = 'calc_cost_surface'
+        x = np.atleast_1d(np.asarray(x, np.float64)).ravel()
+        y = np.atleast_1d(np.asarray(y, np.float64)).ravel()
+        if x.size != y.size or x.size < 1:
+            raise ValueError('%s: as many x as y, at least one point' % who)
+        W, H = self._land_dim
+        if not (np.isfinite(x).all() and np.isfinite(y).all()):
+            raise ValueError('%s: a point is not finite' % who)
+        cx, cy = np.floor(x).astype(np.int64), np.floor(y).astype(np.int64)
+        if (cx < 0).any() or (cx >= W).any() or (cy < 0).any() or (cy >= H).any():
+            raise ValueError('%s: a point lies outside the landscape (0 <= x < %d, 0 <= y < %d)'
+                             % (who, W, H))
+        R = self._cost_raster(who, lyr=lyr, kind=kind, barrier=barrier, cost=cost)
+        return self._dev.cost_surfaces(R, self._cost_res(), cy * int(W) + cx)
 
     def _dist_perm_sums(self, who, predictors, env_lyrs, trts, individs, loci, nperm, seed,
                         min_n):
@@ -1130,7 +1250,7 @@ class Species:
                              'model in first' % who)
         if isinstance(nperm, bool) or int(nperm) != nperm or nperm < 1:
             raise ValueError('%s: nperm: at least 1 permutation (got %r)' % (who, nperm))
-        names, cols = self._dist_predictors(who, predictors, env_lyrs, trts)
+        names, cols, costs = _split_predictors(self, who, predictors, env_lyrs, trts)
         ids, slots = self._geno_sample(individs)
         if ids.size > 8192:
             raise ValueError('%s: at most 8192 individuals per test (the distance matrix is '
@@ -1140,9 +1260,30 @@ class Species:
             raise ValueError('%s: %d individuals leave the test no degrees of freedom (at least '
                              '%d)' % (who, ids.size, min_n))
         _, mask = self._geno_loci(loci)
+        if not costs:
+            rows = _mmrr.draw_row_shuffles(ids.size, int(nperm), seed=seed, rng=self._rng)
+            sums, mom = self._dev.dist_perm_sums(cols, _mmrr.invert_rows(rows), slots, mask)
+            return names, sums, mom
+        # the cost matrices of the sample (rows in id order, as slots), built beside the columns
+        cells = self._get_cells(individs=ids)
+        mats = []
+        for name, opts in costs:
+            D = self._cost_matrix_of_cells(self._cost_raster(who, **opts), cells)
+            n_inf = int(np.isinf(D[np.tril_indices(ids.size, -1)]).sum())
+            if n_inf:
+                raise ValueError('%s: predictor %r: %d pairs of the sampled individuals are at '
+                                 'infinite cost (no path joins them): sample individuals that '
+                                 'can reach each other' % (who, name, n_inf))
+            mats.append(D)
         rows = _mmrr.draw_row_shuffles(ids.size, int(nperm), seed=seed, rng=self._rng)
-        sums, mom = self._dev.dist_perm_sums(cols, _mmrr.invert_rows(rows), slots, mask)
-        return names, sums, mom
+        sums, mom = self._dev.dist_perm_sums_mat(cols, np.stack(mats), _mmrr.invert_rows(rows),
+                                                 slots, mask)
+        # the library's order (columns, then matrices) back to the caller's
+        lib = [n for n in names if n not in dict(costs)] + [n for n, _ in costs]
+        o = [lib.index(n) for n in names]
+        mom = dict(mom, sx=np.asarray(mom['sx'])[o], sxy=np.asarray(mom['sxy'])[o],
+                   sxx=np.asarray(mom['sxx'])[np.ix_(o, o)])
+        return names, np.ascontiguousarray(np.asarray(sums)[:, o]), mom
 
     def _run_mmrr(self, predictors=('geo', 'env'), env_lyrs=None, trts=None, individs=None,
                   loci=None, nperm=999, seed=None):
@@ -1151,7 +1292,7 @@ class Species:
         it), every permutation's fit from cross-sums taken on the device
         -> the reference's OrderedDict (sim/mmrr.mmrr)"""
         from ..sim import mmrr as _mmrr
-        K = 1 if isinstance(predictors, str) else len(predictors)
+        K = len(_predictor_list(predictors))
         # n (n - 1) / 2 pairs must exceed the K + 1 coefficients
         min_n = 3
         while min_n * (min_n - 1) // 2 < K + 2:

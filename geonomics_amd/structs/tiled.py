@@ -68,6 +68,16 @@ class TiledSpecies(Species):
         raise NotImplementedError('run_mantel with a Species tiled over several GPUs is not '
                                   'implemented; run the model on one GPU')
 
+    # -- least-cost distances: not over tiles (a path crosses the tiles' borders; the raster
+    # would be solved on one rank anyway).  A 'cost' predictor reaches the refusals above
+    def _calc_cost_distances(self, *args, **kw):
+        raise NotImplementedError('calc_cost_distances with a Species tiled over several GPUs '
+                                  'is not implemented; run the model on one GPU')
+
+    def _calc_cost_surface(self, *args, **kw):
+        raise NotImplementedError('calc_cost_surface with a Species tiled over several GPUs is '
+                                  'not implemented; run the model on one GPU')
+
     # -- spatial genetic structure: not over tiles (pairs across a tile border: the border
     # cells of the neighbours' samples would have to be exchanged)
     def _calc_spatial_structure(self, *args, **kw):

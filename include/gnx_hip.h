@@ -697,6 +697,64 @@ int gnx_geno_locus_cross(gnx_state* h, int32_t n_loci, const int32_t* loci, int3
 int gnx_dist_perm_sums(gnx_state* h, int64_t n, const int64_t* slots, const uint64_t* locus_mask,
                        int32_t n_pred, const int32_t* pred_off, const int32_t* pred_cols,
                        int32_t n_perm, const int32_t* perm, double* sums, double* moments);
+/* The same with n x n predictor matrices behind the column predictors: predictor n_pred + k is
+ * x[a][b] = mats[k][a][b] (mats double [n_mat][n][n], HOST), 0..4 column predictors (pred_off and
+ * pred_cols may be NULL without any), 0..4 matrices, 1..4 predictors together.  Every matrix must
+ * be finite, exactly symmetric and zero on its diagonal: anything else is an error before anything
+ * is launched (checked on the host).  sums and moments as above with n_pred + n_mat predictors,
+ * the columns first: sums[p][k] = sum over a > b of Y[a][b] x_k[perm[p][a]][perm[p][b]], fp64,
+ * fixed order (a call repeated is bit-equal).  The column predictors have the terms of
+ * gnx_dist_perm_sums, added in another order: their sums are within that call's summation bound
+ * of its sums, not the same bits.  A matrix entry is gathered (perm a fixed over the inner
+ * loop: one row of the matrix at a time).                                                      */
+int gnx_dist_perm_sums_mat(gnx_state* h, int64_t n, const int64_t* slots,
+                           const uint64_t* locus_mask, int32_t n_pred, const int32_t* pred_off,
+                           const int32_t* pred_cols, int32_t n_mat,
+                           const double* mats /*[n_mat][n][n]*/, int32_t n_perm,
+                           const int32_t* perm, double* sums, double* moments);
+
+/* ---- least-cost distances over the landscape (csrc/gnx_cost.hip; the reference has no such
+ *      analysis: its Species move along conductance surfaces, but nothing measures the cost of
+ *      travelling through them) ----------------------------------------------------------------
+ * The graph (geonomics_amd/sim/cost.py restates it with scipy's Dijkstra).  Nodes: the H x W
+ * cells of the handle's landscape, cell = y * W + x.  Every cell is joined to its 8 neighbours.
+ * R double [H][W] (HOST): every entry > 0, or +inf where the cell is impassable (anything else,
+ * nan included, is an error).  The edge between passable cells u, v costs
+ *   w = (0.5 * (R[u] + R[v])) * len,
+ * evaluated in that order in fp64 without contraction, len = res_x for a step along x, res_y along
+ * y and sqrt(res_x res_x + res_y res_y) for a diagonal one (res_x, res_y > 0, finite); an edge
+ * exists iff both ends are passable, and a diagonal step does not look at the two cells it passes
+ * between.  d(s, t) = the cost of the cheapest path, the fp64 sum of its edges from s on;
+ * d(s, s) = 0, also on an impassable cell; d = +inf where there is no path, so an impassable
+ * source is at +inf from every other cell.  The distances are the unique fixed point of
+ * d[v] = min_u (d[u] + w_uv) below d[s] = 0 and do not depend on the order of relaxation: a call
+ * repeated, or made under another gnx_cost_budget, is bit-equal.
+ * Refused (return 1) by all four entry points, before any other check: ghost records (a tile).
+ * Refused before anything is launched: a bad R entry or res,
+ * a cell outside 0..H W - 1, a budget below one source's raster; gnx_cost_matrix: a cell listed
+ * twice, n_cells outside 1..32768.  A solve that has not settled after H W + 2 rounds ends with
+ * the error "did not converge" (it cannot on a valid graph).  Nothing of the handle changes.
+ * gnx_cost_surfaces: out double [n_src][H][W] (HOST), the accumulated-cost raster of every
+ * source (sources may repeat).                                                               */
+int gnx_cost_surfaces(gnx_state* h, const double* R /*[H][W]*/, double res_x, double res_y,
+                      int32_t n_src, const int32_t* src /*cell = y * W + x*/,
+                      double* out /*[n_src][H][W]*/);
+/* gnx_cost_matrix: D double [n_cells][n_cells] (HOST) of distinct cells.  Every cell is solved
+ * as a source and its raster is gathered at the listed cells on the device: only D crosses the
+ * bus.  D is exactly symmetric: for a > b, D[a][b] = D[b][a] = the distance computed from source
+ * cells[b] (the lower index) at cells[a]; the diagonal is 0.                                   */
+int gnx_cost_matrix(gnx_state* h, const double* R /*[H][W]*/, double res_x, double res_y,
+                    int32_t n_cells, const int32_t* cells /*distinct*/,
+                    double* D /*[n_cells][n_cells]*/);
+/* bytes of distance rasters (H W 8 per source) one batch of sources may take: more sources are
+ * worked off batch by batch (0: the default, 2 GiB).  Negative, or positive and below one
+ * source's raster: an error                                                                    */
+int gnx_cost_budget(gnx_state* h, int64_t bytes);
+/* of the last gnx_cost_surfaces / gnx_cost_matrix: its kernels' HIP-event time (ms), their
+ * number, the rounds (one launch over the active (tile, source) pairs each, summed over the
+ * batches) and the batches of sources; each may be NULL                                        */
+int gnx_cost_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* rounds,
+                  int64_t* batches);
 
 /* ---- fine-scale spatial genetic structure (csrc/gnx_sgs.hip; the reference has no such
  *      analysis: its IBD demo, demos/_IBD_IBE.py, ends at MMRR on a sample) ----------------
