@@ -998,15 +998,19 @@ class Device:
         s = _arr(slots, np.int64)
         return s, int(s.size)
 
+    def _locus_mask_words(self, locus_mask):
+        if locus_mask is None:
+            return None
+        m = _arr(locus_mask, np.uint64)
+        if m.size != self.W64:
+            raise ValueError('locus_mask: %d words, not %d' % (m.size, self.W64))
+        return m
+
     def geno_gram(self, slots=None, locus_mask=None):
         """G = D D^T of the dosages of `slots` (all living slots by default), exact int64
         [n][n]; locus_mask: uint64 [W64] bit mask of the loci to use (None: all)"""
         s, n = self._geno_slots(slots)
-        m = None
-        if locus_mask is not None:
-            m = _arr(locus_mask, np.uint64)
-            if m.size != self.W64:
-                raise ValueError('locus_mask: %d words, not %d' % (m.size, self.W64))
+        m = self._locus_mask_words(locus_mask)
         # (the library refuses n outside 1..8192 before it writes: no n x n buffer for that)
         out = np.zeros((n, n) if 1 <= n <= 8192 else (0, 0), np.int64)
         self._chk(self.lib.gnx_geno_gram(self.h, C.c_int64(n), _ptr(s, C.c_int64),
@@ -1092,60 +1096,43 @@ class Device:
         of (field, index) columns, e.g. [[(F_X, 0), (F_Y, 0)], [(F_E, 1)]], read as the device
         holds them.  -> sums float64 [n_perm][n_pred], dict(m, sy, syy, sx [n_pred],
         sxy [n_pred], sxx [n_pred][n_pred]) of the unpermuted pairs"""
-        s, n = self._geno_slots(slots)
-        m = None
-        if locus_mask is not None:
-            m = _arr(locus_mask, np.uint64)
-            if m.size != self.W64:
-                raise ValueError('locus_mask: %d words, not %d' % (m.size, self.W64))
-        off = np.cumsum([0] + [len(p) for p in predictors]).astype(np.int32)
-        cols = _arr([c for p in predictors for c in p], np.int32).reshape(-1, 2)
-        k = len(predictors)
-        perm = _arr(perm, np.int32)
-        if perm.ndim != 2 or perm.shape[1] != n:
-            raise ValueError('perm: [n_perm][%d], not %s' % (n, perm.shape))
-        sums = np.zeros((perm.shape[0], k), np.float64)
-        mom = np.zeros(3 + 2 * k + k * (k + 1) // 2, np.float64)
-        self._chk(self.lib.gnx_dist_perm_sums(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), k,
-            _ptr(off, C.c_int32), _ptr(cols, C.c_int32), int(perm.shape[0]),
-            _ptr(perm, C.c_int32), _ptr(sums, C.c_double), _ptr(mom, C.c_double)))
-        sxx = np.zeros((k, k))
-        sxx[np.triu_indices(k)] = mom[3 + 2 * k:]
-        sxx = sxx + np.triu(sxx, 1).T
-        return sums, dict(m=mom[0], sy=mom[1], syy=mom[2], sx=mom[3:3 + k].copy(),
-                          sxy=mom[3 + k:3 + 2 * k].copy(), sxx=sxx)
+        return self._dist_perm_sums(predictors, None, perm, slots, locus_mask)
 
     def dist_perm_sums_mat(self, predictors, mats, perm, slots=None, locus_mask=None):
         """dist_perm_sums with n x n predictor matrices `mats` (float64 [n_mat][n][n], rows and
         columns in the order of `slots`; finite, symmetric, zero diagonal) behind the column
         predictors (which may be empty): sums float64 [n_perm][n_pred + n_mat] and the moments,
         the columns first"""
+        return self._dist_perm_sums(predictors, mats, perm, slots, locus_mask)
+
+    def _dist_perm_sums(self, predictors, mats, perm, slots, locus_mask):
+        """both calls above; mats None: gnx_dist_perm_sums, which takes no matrices"""
         s, n = self._geno_slots(slots)
-        m = None
-        if locus_mask is not None:
-            m = _arr(locus_mask, np.uint64)
-            if m.size != self.W64:
-                raise ValueError('locus_mask: %d words, not %d' % (m.size, self.W64))
+        m = self._locus_mask_words(locus_mask)
         predictors = list(predictors)
         off = np.cumsum([0] + [len(p) for p in predictors]).astype(np.int32)
         cols = _arr([c for p in predictors for c in p], np.int32).reshape(-1, 2)
-        mats = _arr(mats, np.float64)
-        mats = mats.reshape((0, n, n)) if mats.size == 0 else mats
-        if mats.ndim != 3 or mats.shape[1:] != (n, n):
-            raise ValueError('mats: [n_mat][%d][%d], not %s' % (n, n, mats.shape))
-        k = len(predictors) + mats.shape[0]
+        k = len(predictors)
+        if mats is not None:
+            mats = _arr(mats, np.float64)
+            mats = mats.reshape((0, n, n)) if mats.size == 0 else mats
+            if mats.ndim != 3 or mats.shape[1:] != (n, n):
+                raise ValueError('mats: [n_mat][%d][%d], not %s' % (n, n, mats.shape))
+            k += mats.shape[0]
         perm = _arr(perm, np.int32)
         if perm.ndim != 2 or perm.shape[1] != n:
             raise ValueError('perm: [n_perm][%d], not %s' % (n, perm.shape))
         sums = np.zeros((perm.shape[0], k), np.float64)
         mom = np.zeros(3 + 2 * k + k * (k + 1) // 2, np.float64)
-        self._chk(self.lib.gnx_dist_perm_sums_mat(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), len(predictors),
-            _ptr(off, C.c_int32), _ptr(cols if cols.size else None, C.c_int32),
-            int(mats.shape[0]), _ptr(mats if mats.size else None, C.c_double),
-            int(perm.shape[0]), _ptr(perm, C.c_int32), _ptr(sums, C.c_double),
-            _ptr(mom, C.c_double)))
+        head = (self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), len(predictors),
+                _ptr(off, C.c_int32), _ptr(cols if cols.size else None, C.c_int32))
+        tail = (int(perm.shape[0]), _ptr(perm, C.c_int32), _ptr(sums, C.c_double),
+                _ptr(mom, C.c_double))
+        if mats is None:
+            self._chk(self.lib.gnx_dist_perm_sums(*head, *tail))
+        else:
+            self._chk(self.lib.gnx_dist_perm_sums_mat(
+                *head, int(mats.shape[0]), _ptr(mats if mats.size else None, C.c_double), *tail))
         sxx = np.zeros((k, k))
         sxx[np.triu_indices(k)] = mom[3 + 2 * k:]
         sxx = sxx + np.triu(sxx, 1).T
@@ -1207,11 +1194,7 @@ class Device:
         -> dict(work, isums int64 [n_bins][3], fsums float64 [n_bins][7], n_zero); isums,
         fsums and n_zero are None when max_work <= 0"""
         s, n = self._geno_slots(slots)
-        m = None
-        if locus_mask is not None:
-            m = _arr(locus_mask, np.uint64)
-            if m.size != self.W64:
-                raise ValueError('locus_mask: %d words, not %d' % (m.size, self.W64))
+        m = self._locus_mask_words(locus_mask)
         e = _arr(edges, np.float64).ravel()
         nb = int(e.size) - 1
         wt = None

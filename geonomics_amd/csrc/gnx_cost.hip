@@ -236,7 +236,7 @@ struct CostRun {
 
 // the checks every entry point makes, the raster on the device and the batch's scratch
 int cost_begin(gnx_state* h, const char* who, const double* R, double res_x, double res_y,
-               int64_t n_src, Scratch& sc, CostRun& c) {
+               int64_t n_src, GnxScratch& sc, CostRun& c) {
   if (!R) {
     gnx_set_error("%s: null R", who);
     return 1;
@@ -405,7 +405,7 @@ extern "C" int gnx_cost_surfaces(gnx_state* h, const double* R, double res_x, do
     return 1;
   }
   GNXCHK(cost_check_cells(who, "src", n_src, src, (int64_t)h->cfg.H * h->cfg.W, false));
-  Scratch sc;
+  GnxScratch sc(who);
   CostRun c;
   GNXCHK(cost_begin(h, who, R, res_x, res_y, n_src, sc, c));
   for (int s0 = 0; s0 < n_src; s0 += c.nb_max) {
@@ -426,7 +426,7 @@ extern "C" int gnx_cost_matrix(gnx_state* h, const double* R, double res_x, doub
     return 1;
   }
   GNXCHK(cost_check_cells(who, "cells", n_cells, cells, (int64_t)h->cfg.H * h->cfg.W, true));
-  Scratch sc;
+  GnxScratch sc(who);
   CostRun c;
   GNXCHK(cost_begin(h, who, R, res_x, res_y, n_cells, sc, c));
   int32_t* d_cells = nullptr;

@@ -203,7 +203,7 @@ struct LocusList {
   int n_lines = 0;
 };
 
-int locus_list(gnx_state* h, const char* who, int32_t n_loci, const int32_t* loci, Scratch& s,
+int locus_list(gnx_state* h, const char* who, int32_t n_loci, const int32_t* loci, GnxScratch& s,
                LocusList& ll) {
   if (n_loci < 1 || n_loci > 8192 || !loci) {
     gnx_set_error("%s: 1..8192 loci per call (the matrix is n_loci x n_loci)", who);
@@ -250,7 +250,7 @@ extern "C" int gnx_geno_locus_gram(gnx_state* h, int32_t n_loci, const int32_t* 
     gnx_set_error("%s: 1..2^29 individuals per call", who);
     return 1;
   }
-  Scratch s;
+  GnxScratch s(who);
   LocusList ll;
   GNXCHK(locus_list(h, who, n_loci, loci, s, ll));
   if (!C || !s_out) {
@@ -291,7 +291,7 @@ extern "C" int gnx_geno_locus_cross(gnx_state* h, int32_t n_loci, const int32_t*
     gnx_set_error("%s: n >= 1 and a layer in 0..%d", who, h->cfg.n_layers - 1);
     return 1;
   }
-  Scratch s;
+  GnxScratch s(who);
   LocusList ll;
   GNXCHK(locus_list(h, who, n_loci, loci, s, ll));
   if (!DtZ || !ZtZ || !Zt1) {

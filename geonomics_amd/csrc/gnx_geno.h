@@ -1,7 +1,9 @@
 // What the entry points that read the dosage matrix share (gnx_geno.hip: products over the
-// individuals; gnx_gea.hip: cross-products over the loci;
-// gnx_mantel.hip: distance cross-sums under permutation): the call's device scratch, the
-// preconditions, the slots' genome rows, and the 64 x 64 popcount tile kernel.
+// individuals; gnx_gea.hip: cross-products over the loci; gnx_mantel.hip: distance cross-sums
+// under permutation; gnx_sgs.hip, gnx_ld.hip, gnx_tracts.hip: pair statistics): the
+// preconditions, the slots' genome rows, the masked word list, the gathered operand
+// X [rows][2][words] of the 64 x 64 tile kernels, and the popcount Gram matrix on the device.
+// (The call's device scratch, GnxScratch, is in gnx_internal.h.)
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -27,24 +29,6 @@ __global__ void k_geno_gram(int64_t n, int Wm, const u64* __restrict__ X,
 
 namespace {
 
-// device scratch of one call, freed on every exit
-struct Scratch {
-  std::vector<void*> p;
-  ~Scratch() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <class T>
-  int get(T** out, size_t count) {
-    *out = nullptr;
-    if (hipMalloc((void**)out, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-      gnx_set_error("gnx_geno: out of device memory (%zu bytes)", count * sizeof(T));
-      return 1;
-    }
-    p.push_back(*out);
-    return 0;
-  }
-};
-
 // what every entry point checks first: genomes, no ghosts (tiles), the deferred crossover
 // joined (the newest offspring's genomes are written) and the living in slots [0, N)
 int geno_ready(gnx_state* h, const char* who) {
@@ -63,7 +47,7 @@ int geno_ready(gnx_state* h, const char* who) {
 
 // the slots' physical genome rows on the device; slots == null: all living slots (n == N).
 // d_slots_out (optional): the slots themselves on the device (null when slots == null)
-int geno_rows(gnx_state* h, const char* who, int64_t n, const int64_t* slots, Scratch& s,
+int geno_rows(gnx_state* h, const char* who, int64_t n, const int64_t* slots, GnxScratch& s,
               int32_t** d_rows, int64_t** d_slots_out = nullptr) {
   if (!slots && n != h->N) {
     gnx_set_error("%s: n = %lld but %lld individuals are alive (slots == null)", who,
@@ -86,6 +70,72 @@ int geno_rows(gnx_state* h, const char* who, int64_t n, const int64_t* slots, Sc
                        h->soa[h->cur].grow, *d_rows);
   HIPCHK(hipGetLastError());
   if (d_slots_out) *d_slots_out = d_slots;
+  return 0;
+}
+
+// the words that hold a locus of the mask (null: every locus), each with the mask of its loci;
+// the padding bits past L never count
+void geno_words(gnx_state* h, const uint64_t* locus_mask, std::vector<int32_t>& widx,
+                std::vector<u64>& wmask) {
+  const int L = h->cfg.L;
+  for (int w = 0; w < h->W64; ++w) {
+    u64 m = locus_mask ? locus_mask[w] : ~0ull;
+    const int64_t lo = (int64_t)w * 64;
+    if (lo >= L) m = 0;
+    else if (L - lo < 64) m &= (1ull << (L - lo)) - 1ull;
+    if (m) {
+      widx.push_back(w);
+      wmask.push_back(m);
+    }
+  }
+}
+
+// the operand of the 64 x 64 tile kernels on the device
+struct GenoOperand {
+  u64* X = nullptr;          // [n_pad][2][Wm], written by geno_gather
+  int32_t* widx = nullptr;   // [nw]: the genome word behind word q of X
+  u64* wmask = nullptr;      // [nw]: the loci of that word that count
+  int64_t n_pad = 0;
+  int Wm = 0, nw = 0;
+};
+
+// the operand's buffers for n_pad rows under the word list, the list uploaded: Wm is the
+// multiple of GRAM_GK that leaves at least zero_words words past the nw of the list
+int geno_operand(gnx_state* h, GnxScratch& s, int64_t n_pad, const std::vector<int32_t>& widx,
+                 const std::vector<u64>& wmask, int zero_words, GenoOperand* op) {
+  op->nw = (int)widx.size();
+  op->Wm = std::max(GRAM_GK, (op->nw + zero_words + GRAM_GK - 1) / GRAM_GK * GRAM_GK);
+  op->n_pad = n_pad;
+  GNXCHK(s.get(&op->widx, (size_t)op->nw));
+  GNXCHK(s.get(&op->wmask, (size_t)op->nw));
+  GNXCHK(s.get(&op->X, (size_t)n_pad * 2 * op->Wm));
+  if (op->nw) {
+    GNXCHK(gnx_h2d(h, op->widx, widx.data(), op->nw * sizeof(int32_t)));
+    GNXCHK(gnx_h2d(h, op->wmask, wmask.data(), op->nw * sizeof(u64)));
+  }
+  return 0;
+}
+
+// X of the genome rows d_rows [n]: rows n .. n_pad - 1 and words nw .. Wm - 1 are zero
+void geno_gather(gnx_state* h, const int32_t* d_rows, int64_t n, const GenoOperand& op) {
+  hipLaunchKernelGGL(k_geno_gather, dim3(gnx_grid(op.n_pad * 2 * op.Wm, 256, 256 * 64)),
+                     dim3(256), 0, h->stream, n, op.n_pad, op.nw, op.Wm, d_rows, op.widx,
+                     op.wmask, (const u64*)h->G, gnx_halves(h), op.X);
+}
+
+// G = D D^T of the rows under the mask, exact, into scratch: *d_G int64 [n][n]
+int geno_gram_dev(gnx_state* h, GnxScratch& s, const int32_t* d_rows, int64_t n,
+                  const uint64_t* locus_mask, int64_t** d_G) {
+  std::vector<int32_t> widx;
+  std::vector<u64> wmask;
+  geno_words(h, locus_mask, widx, wmask);
+  const int64_t n_pad = (n + 63) / 64 * 64;
+  GenoOperand op;
+  GNXCHK(geno_operand(h, s, n_pad, widx, wmask, 0, &op));
+  GNXCHK(s.get(d_G, (size_t)n * n));
+  geno_gather(h, d_rows, n, op);
+  const int T = (int)(n_pad / 64);
+  hipLaunchKernelGGL(k_geno_gram, dim3(T, T), dim3(256), 0, h->stream, n, op.Wm, op.X, *d_G);
   return 0;
 }
 

@@ -101,42 +101,11 @@ extern "C" int gnx_geno_gram(gnx_state* h, int64_t n, const int64_t* slots,
     gnx_set_error("%s: null output", who);
     return 1;
   }
-  Scratch s;
+  GnxScratch s(who);
   int32_t* d_rows = nullptr;
   GNXCHK(geno_rows(h, who, n, slots, s, &d_rows));
-  // the words that hold a locus of the mask (padding bits past L never count)
-  const int L = h->cfg.L;
-  std::vector<int32_t> widx;
-  std::vector<u64> wmask;
-  for (int w = 0; w < h->W64; ++w) {
-    u64 m = locus_mask ? locus_mask[w] : ~0ull;
-    const int64_t lo = (int64_t)w * 64;
-    if (lo >= L) m = 0;
-    else if (L - lo < 64) m &= (1ull << (L - lo)) - 1ull;
-    if (m) {
-      widx.push_back(w);
-      wmask.push_back(m);
-    }
-  }
-  const int nw = (int)widx.size();
-  const int Wm = std::max(GRAM_GK, (nw + GRAM_GK - 1) / GRAM_GK * GRAM_GK);
-  const int64_t n_pad = (n + 63) / 64 * 64;
-  int32_t* d_widx = nullptr;
-  u64 *d_wmask = nullptr, *X = nullptr;
   int64_t* d_out = nullptr;
-  GNXCHK(s.get(&d_widx, (size_t)nw));
-  GNXCHK(s.get(&d_wmask, (size_t)nw));
-  GNXCHK(s.get(&X, (size_t)n_pad * 2 * Wm));
-  GNXCHK(s.get(&d_out, (size_t)n * n));
-  if (nw) {
-    GNXCHK(gnx_h2d(h, d_widx, widx.data(), nw * sizeof(int32_t)));
-    GNXCHK(gnx_h2d(h, d_wmask, wmask.data(), nw * sizeof(u64)));
-  }
-  hipLaunchKernelGGL(k_geno_gather, dim3(gnx_grid(n_pad * 2 * Wm, 256, 256 * 64)), dim3(256), 0,
-                     h->stream, n, n_pad, nw, Wm, d_rows, d_widx, d_wmask, (const u64*)h->G,
-                     gnx_halves(h), X);
-  const int T = (int)(n_pad / 64);
-  hipLaunchKernelGGL(k_geno_gram, dim3(T, T), dim3(256), 0, h->stream, n, Wm, X, d_out);
+  GNXCHK(geno_gram_dev(h, s, d_rows, n, locus_mask, &d_out));
   HIPCHK(hipGetLastError());
   return gnx_d2h(h, Gout, d_out, (size_t)n * n * sizeof(int64_t));
 }
@@ -201,7 +170,7 @@ extern "C" int gnx_geno_matmul(gnx_state* h, int32_t k, const float* M, float* Y
     gnx_set_error("%s: 1 <= k <= 64, n >= 0 and device pointers M, Y", who);
     return 1;
   }
-  Scratch s;
+  GnxScratch s(who);
   int32_t* d_rows = nullptr;
   GNXCHK(geno_rows(h, who, n, slots, s, &d_rows));
   if (n > 0)
@@ -300,7 +269,7 @@ extern "C" int gnx_geno_rmatmul(gnx_state* h, int32_t k, const float* Y, float* 
     gnx_set_error("%s: 1 <= k <= 64, n >= 0 and device pointers Y, Z", who);
     return 1;
   }
-  Scratch s;
+  GnxScratch s(who);
   int32_t* d_rows = nullptr;
   GNXCHK(geno_rows(h, who, n, slots, s, &d_rows));
   const int L = h->cfg.L;

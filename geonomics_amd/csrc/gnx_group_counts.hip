@@ -152,26 +152,6 @@ k_group_counts(int W64, int L, const u64* __restrict__ G, const int32_t* __restr
   gc_flush<GC_K + 1>((const uint32_t*)pl, wave, lane, w0, W64, L, c1);
 }
 
-namespace {
-struct GcScratch {
-  std::vector<void*> p;
-  ~GcScratch() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <class T>
-  int get(T** out, size_t count) {
-    *out = nullptr;
-    if (hipMalloc((void**)out, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-      gnx_set_error("gnx_stats_group_counts: out of device memory (%zu bytes)",
-                    count * sizeof(T));
-      return 1;
-    }
-    p.push_back(*out);
-    return 0;
-  }
-};
-}  // namespace
-
 extern "C" int gnx_stats_group_counts(gnx_state* h, int64_t n, const int32_t* slots, int32_t G,
                                       const int64_t* group_start, int32_t* cnt1,
                                       int32_t* cnt_het) {
@@ -226,7 +206,7 @@ extern "C" int gnx_stats_group_counts(gnx_state* h, int64_t n, const int32_t* sl
     for (int64_t s = group_start[g]; s < group_start[g + 1]; s += GC_CHUNK)
       chunks.push_back({s, (int32_t)std::min<int64_t>(GC_CHUNK, group_start[g + 1] - s), g});
 
-  GcScratch sc;
+  GnxScratch sc(who);
   const size_t cells = (size_t)G * L;
   int32_t *d1 = nullptr, *d2 = nullptr, *d_slots = nullptr;
   GcChunk* d_chunks = nullptr;

@@ -934,25 +934,22 @@ static inline int gnx_grid(int64_t n, int block, int max_blocks = 1 << 20) {
   return (int)g;
 }
 
-// ---- lineage calls (gnx_lineage.hip, gnx_simplify.hip) -----------------------------------
-#define LIN_BUDGET (256ll << 20)  // bytes of output per launch unless gnx_lineage_budget says so
-
-// the handle takes lineage requests; the node table is on the device (uploaded, or the copy of
-// an earlier call when nothing was appended since) and every index in it is in range
-int lin_table(gnx_state* h, const char* who, int64_t n_rows, const int32_t* tab,
-              const int32_t* bt, int32_t t_curr);
-
-// device buffers of one call, freed on every exit
-struct LinScratch {
+// ---- what the statistics calls share -------------------------------------------------------
+// device scratch of one call, freed on every exit; who: the caller, for the message
+struct GnxScratch {
+  const char* who;
   std::vector<void*> p;
-  ~LinScratch() {
-    for (void* q : p) (void)hipFree(q);
+  explicit GnxScratch(const char* who_) : who(who_) {}
+  GnxScratch(const GnxScratch&) = delete;
+  ~GnxScratch() {
+    for (void* d : p) (void)hipFree(d);
   }
   template <class T>
   int get(T** out, size_t count) {
     *out = nullptr;
     if (hipMalloc((void**)out, (count > 0 ? count : 1) * sizeof(T)) != hipSuccess) {
-      gnx_set_error("gnx_lineage: out of device memory (%zu bytes)", count * sizeof(T));
+      (void)hipGetLastError();                       // the next HIPCHK must not report it again
+      gnx_set_error("%s: out of device memory (%zu bytes of scratch)", who, count * sizeof(T));
       return 1;
     }
     p.push_back(*out);
@@ -960,17 +957,20 @@ struct LinScratch {
   }
 };
 
-// HIP events around the launches of one call: gnx_lineage_info's kernel time and launches
-struct LinTimer {
+// HIP events around the launches of one call, added to the kernel time and the launch count that
+// the call's *_info reports (the caller zeroes them where its call begins)
+struct GnxCallTimer {
   gnx_state* h;
+  double* ms_sum;
+  int64_t* launch_sum;
   hipEvent_t a = nullptr, b = nullptr;
-  explicit LinTimer(gnx_state* h_) : h(h_) {
+  GnxCallTimer(gnx_state* h_, double* ms, int64_t* launches)
+      : h(h_), ms_sum(ms), launch_sum(launches) {
     (void)hipEventCreate(&a);
     (void)hipEventCreate(&b);
-    h->lin_ms = 0.0;
-    h->lin_launches = 0;
   }
-  ~LinTimer() {
+  GnxCallTimer(const GnxCallTimer&) = delete;
+  ~GnxCallTimer() {
     if (a) (void)hipEventDestroy(a);
     if (b) (void)hipEventDestroy(b);
   }
@@ -979,8 +979,16 @@ struct LinTimer {
     (void)hipEventRecord(b, h->stream);
     HIPCHK(hipStreamSynchronize(h->stream));
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) h->lin_ms += ms;
-    h->lin_launches += launches;
+    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) *ms_sum += ms;
+    *launch_sum += launches;
     return 0;
   }
 };
+
+// ---- lineage calls (gnx_lineage.hip, gnx_simplify.hip) -----------------------------------
+#define LIN_BUDGET (256ll << 20)  // bytes of output per launch unless gnx_lineage_budget says so
+
+// the handle takes lineage requests; the node table is on the device (uploaded, or the copy of
+// an earlier call when nothing was appended since) and every index in it is in range
+int lin_table(gnx_state* h, const char* who, int64_t n_rows, const int32_t* tab,
+              const int32_t* bt, int32_t t_curr);

@@ -279,33 +279,6 @@ __global__ void k_ld_total(int blocks, const long long* __restrict__ ipart,
   }
 }
 
-namespace {
-
-// HIP events around the launches of one call (gnx_ld_info)
-struct LdTimer {
-  gnx_state* h;
-  hipEvent_t a = nullptr, b = nullptr;
-  explicit LdTimer(gnx_state* h_) : h(h_) {
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-  }
-  ~LdTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  void start() { (void)hipEventRecord(a, h->stream); }
-  int stop(int64_t launches) {
-    (void)hipEventRecord(b, h->stream);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) h->ld_ms += ms;
-    h->ld_launches += launches;
-    return 0;
-  }
-};
-
-}  // namespace
-
 extern "C" int gnx_ld_budget(gnx_state* h, int64_t bytes) {
   if (bytes < 0) {
     gnx_set_error("gnx_ld_budget: bytes >= 0 (0: the default)");
@@ -467,7 +440,7 @@ extern "C" int gnx_ld_bins(gnx_state* h, int64_t n, const int64_t* slots, int32_
       max_tasks = std::max(max_tasks, m);
     }
 
-  Scratch s;
+  GnxScratch s(who);
   int32_t* d_rows = nullptr;
   GNXCHK(geno_rows(h, who, n, slots, s, &d_rows));
   const int64_t buf_words = (int64_t)tpb * 64 * pitch;
@@ -518,7 +491,7 @@ extern "C" int gnx_ld_bins(gnx_state* h, int64_t n, const int64_t* slots, int32_
   };
   const long long mm = std::max<long long>(1, min_minor);
   std::vector<LdTask> tasks;
-  LdTimer tm(h);
+  GnxCallTimer tm(h, &h->ld_ms, &h->ld_launches);
   for (int bi = 0; bi < nblk; ++bi) {
     bool have_a = false;
     for (int bj = bi; bj < nblk; ++bj) {

@@ -248,7 +248,7 @@ namespace {
 
 // the sample nodes and the loci, checked and uploaded
 int lin_request(gnx_state* h, const char* who, int64_t n_rows, int64_t n_nodes,
-                const int32_t* nodes, int32_t n_loci, const int32_t* loci, LinScratch& s,
+                const int32_t* nodes, int32_t n_loci, const int32_t* loci, GnxScratch& s,
                 int32_t** d_nodes, int32_t** d_loci) {
   if (n_nodes < 1 || n_loci < 1 || !nodes || !loci) {
     gnx_set_error("%s: at least one sample node and one locus", who);
@@ -324,7 +324,7 @@ extern "C" int gnx_lineage_trace(gnx_state* h, int64_t n_rows, const int32_t* no
     return 1;
   }
   GNXCHK(lin_table(h, who, n_rows, node_tab, birth_t, t_curr));
-  LinScratch s;
+  GnxScratch s(who);
   int32_t *d_nodes = nullptr, *d_loci = nullptr;
   GNXCHK(lin_request(h, who, n_rows, n_nodes, nodes, n_loci, loci, s, &d_nodes, &d_loci));
   int32_t* host[4] = {root, first, last, n_kept};
@@ -347,7 +347,9 @@ extern "C" int gnx_lineage_trace(gnx_state* h, int64_t n_rows, const int32_t* no
   }
   const LinWindow w{t_curr, drop_before_sim != 0, min_ago, max_ago};
   const int64_t n_groups = (n_nodes + LIN_NPT - 1) / LIN_NPT;
-  LinTimer tm(h);
+  h->lin_ms = 0.0;
+  h->lin_launches = 0;
+  GnxCallTimer tm(h, &h->lin_ms, &h->lin_launches);
   for (int64_t q0 = 0; q0 < n_loci; q0 += per) {
     const int n_q = (int)std::min<int64_t>(per, n_loci - q0);
     LinGrid g;
@@ -377,7 +379,7 @@ extern "C" int gnx_lineage_chains(gnx_state* h, int64_t n_rows, const int32_t* n
                                   const int64_t* offsets, int32_t* chain_nodes) {
   const char* who = "gnx_lineage_chains";
   GNXCHK(lin_table(h, who, n_rows, node_tab, birth_t, t_curr));
-  LinScratch s;
+  GnxScratch s(who);
   int32_t *d_nodes = nullptr, *d_loci = nullptr;
   GNXCHK(lin_request(h, who, n_rows, n_nodes, nodes, n_loci, loci, s, &d_nodes, &d_loci));
   const int64_t nq = (int64_t)n_loci * n_nodes;
@@ -399,7 +401,9 @@ extern "C" int gnx_lineage_chains(gnx_state* h, int64_t n_rows, const int32_t* n
   int32_t* d_bad = nullptr;
   GNXCHK(s.get(&d_bad, 1));
   HIPCHK(hipMemsetAsync(d_bad, 0, 4, h->stream));
-  LinTimer tm(h);
+  h->lin_ms = 0.0;
+  h->lin_launches = 0;
+  GnxCallTimer tm(h, &h->lin_ms, &h->lin_launches);
   for (int64_t q0 = 0; q0 < n_loci;) {
     // loci of this launch: chain entries (4 bytes) and offsets (8 bytes) under the budget
     int64_t q1 = q0 + 1;
@@ -408,7 +412,7 @@ extern "C" int gnx_lineage_chains(gnx_state* h, int64_t n_rows, const int32_t* n
       ++q1;
     const int n_q = (int)(q1 - q0);
     const int64_t n_ent = offsets[q1 * n_nodes] - offsets[q0 * n_nodes];
-    LinScratch cs;
+    GnxScratch cs(who);
     int64_t* d_off = nullptr;
     int32_t* d_chain = nullptr;
     GNXCHK(cs.get(&d_off, (size_t)n_q * n_nodes + 1));

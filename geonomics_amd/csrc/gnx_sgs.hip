@@ -337,21 +337,10 @@ extern "C" int gnx_sgs_sums(gnx_state* h, int64_t n, const int64_t* slots,
                   (long long)n, L);
     return 1;
   }
-  // the words that hold a locus of the mask (padding bits past L never count)
   std::vector<int32_t> widx;
   std::vector<u64> wmask;
-  for (int wq = 0; wq < h->W64; ++wq) {
-    u64 m = locus_mask ? locus_mask[wq] : ~0ull;
-    const int64_t lo = (int64_t)wq * 64;
-    if (lo >= L) m = 0;
-    else if (L - lo < 64) m &= (1ull << (L - lo)) - 1ull;
-    if (m) {
-      widx.push_back(wq);
-      wmask.push_back(m);
-    }
-  }
+  geno_words(h, locus_mask, widx, wmask);
   const int nw = (int)widx.size();
-  const int Wm = std::max(GRAM_GK, (nw + GRAM_GK - 1) / GRAM_GK * GRAM_GK);
   // the grid: a side a little above the largest edge (so that rounding in r or in the cell
   // number cannot part two individuals closer than it by more than one cell), larger where
   // the landscape would have more than SGS_MAX_CELLS cells
@@ -371,7 +360,7 @@ extern "C" int gnx_sgs_sums(gnx_state* h, int64_t n, const int64_t* slots,
   int bits = 1;
   while ((1ll << bits) < n_cells) ++bits;
 
-  Scratch s;
+  GnxScratch s(who);
   int32_t* d_rows = nullptr;
   int64_t* d_slots = nullptr;
   GNXCHK(geno_rows(h, who, n, slots, s, &d_rows, &d_slots));
@@ -451,15 +440,12 @@ extern "C" int gnx_sgs_sums(gnx_state* h, int64_t n, const int64_t* slots,
   const int mi = (SGS_NB + 1) * SGS_NI, mf = SGS_NB * SGS_NF;
   // a tile reads 64 rows from its first: 64 zero rows behind the sample
   const int64_t n_pad = n + 64;
-  int32_t *d_widx = nullptr, *d_rows_sorted = nullptr, *d_self = nullptr;
-  u64 *d_wmask = nullptr, *X = nullptr;
+  int32_t *d_rows_sorted = nullptr, *d_self = nullptr;
   float *d_xs = nullptr, *d_ys = nullptr;
   double *d_w = nullptr, *d_weight = nullptr, *d_edges = nullptr, *d_fpart = nullptr,
          *d_ftot = nullptr;
   long long *d_ipart = nullptr, *d_itot = nullptr;
   SgsTask* d_tasks = nullptr;
-  GNXCHK(s.get(&d_widx, (size_t)nw));
-  GNXCHK(s.get(&d_wmask, (size_t)nw));
   GNXCHK(s.get(&d_rows_sorted, (size_t)n));
   GNXCHK(s.get(&d_xs, (size_t)n));
   GNXCHK(s.get(&d_ys, (size_t)n));
@@ -471,7 +457,6 @@ extern "C" int gnx_sgs_sums(gnx_state* h, int64_t n, const int64_t* slots,
   GNXCHK(s.get(&d_fpart, (size_t)blocks * mf));
   GNXCHK(s.get(&d_itot, (size_t)mi));
   GNXCHK(s.get(&d_ftot, (size_t)mf));
-  GNXCHK(s.get(&X, (size_t)n_pad * 2 * Wm));
   if (perm) {
     GNXCHK(s.get(&d_perm, (size_t)n));
     GNXCHK(gnx_h2d(h, d_perm, perm, (size_t)n * sizeof(int32_t)));
@@ -483,21 +468,17 @@ extern "C" int gnx_sgs_sums(gnx_state* h, int64_t n, const int64_t* slots,
     GNXCHK(s.get(&d_weight, wt.size()));
     GNXCHK(gnx_h2d(h, d_weight, wt.data(), wt.size() * sizeof(double)));
   }
-  if (nw) {
-    GNXCHK(gnx_h2d(h, d_widx, widx.data(), nw * sizeof(int32_t)));
-    GNXCHK(gnx_h2d(h, d_wmask, wmask.data(), nw * sizeof(u64)));
-  }
   GNXCHK(gnx_h2d(h, d_edges, edges, ((size_t)n_bins + 1) * sizeof(double)));
   if (n_tasks) GNXCHK(gnx_h2d(h, d_tasks, tasks.data(), (size_t)n_tasks * sizeof(SgsTask)));
   hipLaunchKernelGGL(k_sgs_arrange, dim3(gnx_grid(n, 256)), dim3(256), 0, h->stream, n, d_order,
                      d_slots, d_perm, d_rows, a.x, a.y, d_rows_sorted, d_xs, d_ys);
-  hipLaunchKernelGGL(k_geno_gather, dim3(gnx_grid(n_pad * 2 * Wm, 256, 256 * 64)), dim3(256), 0,
-                     h->stream, n, n_pad, nw, Wm, d_rows_sorted, d_widx, d_wmask,
-                     (const u64*)h->G, gnx_halves(h), X);
-  hipLaunchKernelGGL(k_sgs_self, dim3(gnx_grid(n, 64)), dim3(64), 0, h->stream, n, nw, Wm, X,
-                     d_widx, d_weight, d_self, d_w);
-  hipLaunchKernelGGL(k_sgs_pairs, dim3(blocks), dim3(256), 0, h->stream, n_tasks, Wm,
-                     (int)n_bins, d_tasks, X, d_xs, d_ys, d_self, d_w, d_edges, d_ipart,
+  GenoOperand op;
+  GNXCHK(geno_operand(h, s, n_pad, widx, wmask, 0, &op));
+  geno_gather(h, d_rows_sorted, n, op);
+  hipLaunchKernelGGL(k_sgs_self, dim3(gnx_grid(n, 64)), dim3(64), 0, h->stream, n, nw, op.Wm,
+                     op.X, op.widx, d_weight, d_self, d_w);
+  hipLaunchKernelGGL(k_sgs_pairs, dim3(blocks), dim3(256), 0, h->stream, n_tasks, op.Wm,
+                     (int)n_bins, d_tasks, op.X, d_xs, d_ys, d_self, d_w, d_edges, d_ipart,
                      d_fpart);
   hipLaunchKernelGGL(k_sgs_total, dim3(gnx_grid(mi + mf, 256)), dim3(256), 0, h->stream, blocks,
                      d_ipart, d_fpart, d_itot, d_ftot);

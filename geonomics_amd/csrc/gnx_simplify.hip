@@ -164,7 +164,7 @@ extern "C" int gnx_pedigree_reach(gnx_state* h, int64_t n_rows, const int32_t* n
     gnx_set_error("%s: the table is too large for one launch; lower the byte budget", who);
     return 1;
   }
-  LinScratch s;
+  GnxScratch s(who);
   int32_t *d_off = nullptr, *d_child = nullptr, *d_loci = nullptr, *d_req = nullptr;
   uint8_t *d_samp = nullptr, *d_nz = nullptr;
   u64 *d_mask = nullptr, *d_out = nullptr;
@@ -187,7 +187,7 @@ extern "C" int gnx_pedigree_reach(gnx_state* h, int64_t n_rows, const int32_t* n
   GNXCHK(gnx_h2d(h, d_child, child.data(), child.size() * 4));
   GNXCHK(gnx_h2d(h, d_samp, is_sample.data(), (size_t)n_rows));
   HIPCHK(hipMemsetAsync(d_loci, 0, (size_t)2 * n_rows * 4, h->stream));
-  LinTimer tm(h);
+  GnxCallTimer tm(h, &h->lin_ms, &h->lin_launches);
   for (int w0 = 0; w0 < W64; w0 += (int)Wb) {
     const int C = (int)std::min<int64_t>(Wb, W64 - w0) / 2;
     HIPCHK(hipMemsetAsync(d_nz, 0, (size_t)2 * n_rows, h->stream));

@@ -343,29 +343,6 @@ k_tract_cover(int L, const int* __restrict__ cdiff, long long* __restrict__ cove
 
 namespace {
 
-// HIP events around the launches of one call (gnx_tracts_info)
-struct TrTimer {
-  gnx_state* h;
-  hipEvent_t a = nullptr, b = nullptr;
-  explicit TrTimer(gnx_state* h_) : h(h_) {
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-  }
-  ~TrTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  void start() { (void)hipEventRecord(a, h->stream); }
-  int stop(int64_t launches) {
-    (void)hipEventRecord(b, h->stream);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) h->tr_ms += ms;
-    h->tr_launches += launches;
-    return 0;
-  }
-};
-
 // what both entry points refuse before anything is launched
 int tracts_check(gnx_state* h, const char* who, int64_t n, int64_t n_max, const int64_t* slots,
                  const int64_t* pos, int64_t min_len, int32_t n_edges, const int64_t* edges,
@@ -443,7 +420,7 @@ struct TractDev {
   int n_bins = 0;
 };
 
-int tracts_stage(gnx_state* h, Scratch& s, const int64_t* pos, const uint64_t* brk,
+int tracts_stage(gnx_state* h, GnxScratch& s, const int64_t* pos, const uint64_t* brk,
                  int32_t n_edges, const int64_t* edges, bool want_cover, TractDev& d) {
   const int L = h->cfg.L, W64 = h->W64;
   GNXCHK(s.get(&d.pos, (size_t)L));
@@ -504,7 +481,7 @@ extern "C" int gnx_tracts_self(gnx_state* h, int64_t n, const int64_t* slots, co
     return 1;
   }
   const int L = h->cfg.L, Wv = (L + 63) / 64;
-  Scratch s;
+  GnxScratch s(who);
   int32_t* d_rows = nullptr;
   GNXCHK(geno_rows(h, who, n, slots, s, &d_rows));
   TractDev d;
@@ -515,7 +492,7 @@ extern "C" int gnx_tracts_self(gnx_state* h, int64_t n, const int64_t* slots, co
   GNXCHK(s.get(&d_words, 1));
   HIPCHK(hipMemsetAsync(d_words, 0, sizeof(unsigned long long), h->stream));
   const int ml = std::max(1, min_loci);
-  TrTimer tm(h);
+  GnxCallTimer tm(h, &h->tr_ms, &h->tr_launches);
   tm.start();
   hipLaunchKernelGGL(k_tract_self, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream, n,
                      d_rows, (const u64*)h->G, gnx_halves(h), L, Wv, d.pos, d.brk, ml,
@@ -552,43 +529,34 @@ extern "C" int gnx_tracts_pairs(gnx_state* h, int64_t n, const int64_t* slots, c
                   (long long)max_work);
     return 1;
   }
-  Scratch s;
+  GnxScratch s(who);
   int32_t* d_rows = nullptr;
   GNXCHK(geno_rows(h, who, n, slots, s, &d_rows));
   TractDev d;
   GNXCHK(tracts_stage(h, s, pos, brk, n_edges, edges, cover != nullptr, d));
-  // the operand of k_geno_gather: every word that holds a locus under the full mask, and at
-  // least one zero word after them
-  std::vector<int32_t> widx((size_t)Wv);
-  std::vector<u64> wmask((size_t)Wv, ~0ull);
-  for (int w = 0; w < Wv; ++w) widx[(size_t)w] = w;
-  if (L & 63) wmask[(size_t)Wv - 1] = (1ull << (L & 63)) - 1ull;
-  const int Wm = (Wv + 1 + GRAM_GK - 1) / GRAM_GK * GRAM_GK;
-  const int64_t n_pad = (n + 63) / 64 * 64;
-  int32_t *d_widx = nullptr, *d_cnt = nullptr;
-  u64 *d_wmask = nullptr, *X = nullptr;
+  int32_t* d_cnt = nullptr;
   long long *d_len = nullptr, *d_longest = nullptr;
-  GNXCHK(s.get(&d_widx, (size_t)Wv));
-  GNXCHK(s.get(&d_wmask, (size_t)Wv));
-  GNXCHK(s.get(&X, (size_t)n_pad * 2 * Wm));
   GNXCHK(s.get(&d_cnt, (size_t)n * n));
   GNXCHK(s.get(&d_len, (size_t)n * n));
   GNXCHK(s.get(&d_longest, (size_t)n * n));
-  GNXCHK(gnx_h2d(h, d_widx, widx.data(), (size_t)Wv * sizeof(int32_t)));
-  GNXCHK(gnx_h2d(h, d_wmask, wmask.data(), (size_t)Wv * sizeof(u64)));
   HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)n * n * sizeof(int32_t), h->stream));
   HIPCHK(hipMemsetAsync(d_len, 0, (size_t)n * n * sizeof(long long), h->stream));
   HIPCHK(hipMemsetAsync(d_longest, 0, (size_t)n * n * sizeof(long long), h->stream));
   const int ml = std::max(1, min_loci);
+  // the operand: every word that holds a locus, and at least one zero word after them
+  std::vector<int32_t> widx;
+  std::vector<u64> wmask;
+  geno_words(h, nullptr, widx, wmask);
+  const int64_t n_pad = (n + 63) / 64 * 64;
   const int T = (int)(n_pad / 64);
-  TrTimer tm(h);
+  GenoOperand op;
+  GNXCHK(geno_operand(h, s, n_pad, widx, wmask, 1, &op));
+  GnxCallTimer tm(h, &h->tr_ms, &h->tr_launches);
   tm.start();
-  hipLaunchKernelGGL(k_geno_gather, dim3(gnx_grid(n_pad * 2 * Wm, 256, 256 * 64)), dim3(256), 0,
-                     h->stream, n, n_pad, Wv, Wm, d_rows, d_widx, d_wmask, (const u64*)h->G,
-                     gnx_halves(h), X);
-  hipLaunchKernelGGL(k_tract_pairs, dim3(T, T), dim3(256), 0, h->stream, n, Wm, L, h->W64, X,
-                     d.pos, d.brk, ml, (long long)min_len, (int)(ml >= 63), d.n_bins, d.edges,
-                     d_cnt, d_len, d_longest, d.hist, d.cdiff);
+  geno_gather(h, d_rows, n, op);
+  hipLaunchKernelGGL(k_tract_pairs, dim3(T, T), dim3(256), 0, h->stream, n, op.Wm, L, h->W64,
+                     op.X, d.pos, d.brk, ml, (long long)min_len, (int)(ml >= 63), d.n_bins,
+                     d.edges, d_cnt, d_len, d_longest, d.hist, d.cdiff);
   hipLaunchKernelGGL(k_tract_mirror, dim3(gnx_grid(n * n, 256, 256 * 64)), dim3(256), 0,
                      h->stream, n, d_cnt, d_len, d_longest);
   if (cover)

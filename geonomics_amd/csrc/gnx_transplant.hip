@@ -28,26 +28,6 @@
 
 namespace {
 
-// device scratch of one call, freed on every exit
-struct Scratch {
-  std::vector<void*> p;
-  ~Scratch() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <class T>
-  int get(T** out, size_t count) {
-    *out = nullptr;
-    if (hipMalloc((void**)out, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      gnx_set_error("gnx_transplant: out of device memory (%zu bytes of scratch)",
-                    count * sizeof(T));
-      return 1;
-    }
-    p.push_back(*out);
-    return 0;
-  }
-};
-
 struct TpTable {
   int32_t* key;     // [T] source block, -1 = empty
   int32_t* ref;     // [T] newcomers' table entries that name it
@@ -295,7 +275,7 @@ extern "C" int gnx_transplant(gnx_state* dst, gnx_state* src, int64_t n, const i
     return 2;
   }
 
-  Scratch sc;
+  GnxScratch sc("gnx_transplant");
   int64_t* d_slots = nullptr;
   float *d_x = nullptr, *d_y = nullptr;
   GNXCHK(sc.get(&d_slots, (size_t)n));

@@ -703,10 +703,12 @@ int gnx_dist_perm_sums(gnx_state* h, int64_t n, const int64_t* slots, const uint
  * be finite, exactly symmetric and zero on its diagonal: anything else is an error before anything
  * is launched (checked on the host).  sums and moments as above with n_pred + n_mat predictors,
  * the columns first: sums[p][k] = sum over a > b of Y[a][b] x_k[perm[p][a]][perm[p][b]], fp64,
- * fixed order (a call repeated is bit-equal).  The column predictors have the terms of
- * gnx_dist_perm_sums, added in another order: their sums are within that call's summation bound
- * of its sums, not the same bits.  A matrix entry is gathered (perm a fixed over the inner
- * loop: one row of the matrix at a time).                                                      */
+ * fixed order (a call repeated is bit-equal).  Without a matrix (n_mat = 0) the call is
+ * gnx_dist_perm_sums: the same bits.  In front of a matrix the column predictors have the terms
+ * of gnx_dist_perm_sums, added in stripes of 8 columns of the sample where that call takes 16
+ * with 4 predictor columns or fewer: their sums are the bits of its sums with 5..8 predictor
+ * columns, and within its summation bound of them with fewer.  A matrix entry is gathered
+ * (perm a fixed over the inner loop: one row of the matrix at a time).                         */
 int gnx_dist_perm_sums_mat(gnx_state* h, int64_t n, const int64_t* slots,
                            const uint64_t* locus_mask, int32_t n_pred, const int32_t* pred_off,
                            const int32_t* pred_cols, int32_t n_mat,

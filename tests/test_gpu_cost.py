@@ -324,6 +324,50 @@ def test_a_random_matrix_alone_and_behind_columns(big):
     _within(mom['sxx'][:2, :2], old_m['sxx'], old_m['sxx'], m, 16, 'sxx', worst)
 
 
+ENV012 = [(5, 0), (5, 1), (5, 2)]
+WIDE = [ENV012[:2] * 2, ENV012[1:] * 2]                 # 8 columns: stripes of 8, not 16
+
+
+def _assert_same_bits(got, want, k):
+    """the sums and every moment of the first k predictors of `got` are those of `want`"""
+    (s, mom), (s0, mom0) = got, want
+    np.testing.assert_array_equal(s[:, :k], s0)
+    for key in ('m', 'sy', 'syy'):
+        np.testing.assert_array_equal(mom[key], mom0[key])
+    for key in ('sx', 'sxy'):
+        np.testing.assert_array_equal(mom[key][:k], mom0[key])
+    np.testing.assert_array_equal(mom['sxx'][:k, :k], mom0['sxx'])
+
+
+@pytest.mark.parametrize('sample', [None, 65], ids=['all', 'slots65'])
+@pytest.mark.parametrize('cols', [[GEO, ENV1], WIDE], ids=['D3_stripes16', 'D8_stripes8'])
+def test_no_matrix_is_the_column_call(big, cols, sample):
+    """the matrix entry without a matrix takes the column path: the bits of dist_perm_sums, at
+    both stripe widths"""
+    nat, dev, host = big
+    slots = None if sample is None else \
+        np.random.RandomState(7).choice(1031, sample, replace=False).astype(np.int64)
+    n = 1031 if sample is None else sample
+    perm = M.invert_rows(M.draw_row_shuffles(n, 65, seed=5))
+    got = dev.dist_perm_sums_mat(cols, np.zeros((0, n, n)), perm, slots)
+    assert got[0].shape == (65, len(cols))
+    _assert_same_bits(got, dev.dist_perm_sums(cols, perm, slots), len(cols))
+
+
+def test_wide_columns_in_front_of_a_matrix_are_the_column_call(big):
+    """with more than 4 columns the column-only call works in stripes of 8 as the matrix path
+    does, so a column predictor's terms are added in the same order: the same bits (with 4
+    columns or fewer the widths differ, and the bound asserted in
+    test_a_random_matrix_alone_and_behind_columns is what holds)"""
+    nat, dev, host = big
+    slots = np.random.RandomState(8).choice(1031, 131, replace=False).astype(np.int64)
+    cols = [GEO, ENV012]
+    perm = M.invert_rows(M.draw_row_shuffles(131, 65, seed=6))
+    got = dev.dist_perm_sums_mat(cols, host['A'][np.ix_(slots, slots)][None], perm, slots)
+    assert got[0].shape == (65, 3)
+    _assert_same_bits(got, dev.dist_perm_sums(cols, perm, slots), 2)
+
+
 @pytest.mark.parametrize('n', [2, 65])
 def test_a_sample_of_slots(big, n):
     nat, dev, host = big
