@@ -71,6 +71,7 @@ EXPORTS = [
     'gnx_tracts_self', 'gnx_tracts_pairs', 'gnx_tracts_info',
     'gnx_dist_perm_sums_mat',
     'gnx_cost_surfaces', 'gnx_cost_matrix', 'gnx_cost_budget', 'gnx_cost_info',
+    'gnx_admix_sweep', 'gnx_admix_info',
 ]
 
 
@@ -1264,6 +1265,57 @@ class Device:
         ms, n, nb = C.c_double(), C.c_int64(), C.c_int64()
         self._chk(self.lib.gnx_ld_info(self.h, C.byref(ms), C.byref(n), C.byref(nb)))
         return dict(kernel_ms=ms.value, launches=int(n.value), locus_blocks=int(nb.value))
+
+    # -- model-based ancestry (csrc/gnx_admix.hip) -------------------------------------------
+    def admix_sweep(self, Q, F, slots=None, locus_mask=None, want_loglik=True, budget=None,
+                    want_B=True):
+        """one EM sweep of the admixture model (include/gnx_hip.h, gnx_admix_sweep): Q torch
+        fp64 [n][K] and F torch fp64 [K][L] on the handle's device -> dict(A [n][K], B1 [K][L],
+        B0 [K][L] torch fp64 on the device, loglik float or None).  want_B=False (F held fixed)
+        skips B1 and B0 (None); budget: bytes of partial sums per chunk of individuals (None:
+        the default).  The call waits for the current torch stream before it reads Q and F and
+        returns with the outputs complete."""
+        import torch
+        for t, name in ((Q, 'Q'), (F, 'F')):
+            if not torch.cuda.is_available():
+                raise GnxError('torch sees no HIP device: initialise it (torch.cuda.init()) '
+                               'before the first Device is created, as bench.py does')
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != 2:
+                raise ValueError('%s: a 2-d torch tensor on the device' % name)
+        Q = Q.to(torch.float64).contiguous()
+        F = F.to(torch.float64).contiguous()
+        s, n = self._geno_slots(slots)
+        K = int(Q.shape[1])
+        if Q.shape[0] != n:
+            raise ValueError('Q: %d rows, not n = %d' % (Q.shape[0], n))
+        if F.shape[0] != K or F.shape[1] != self.L:
+            raise ValueError('F: %s, not (K, L) = (%d, %d)' % (tuple(F.shape), K, self.L))
+        m = self._locus_mask_words(locus_mask)
+        A = torch.empty((n, K), dtype=torch.float64, device=Q.device)
+        B1 = B0 = None
+        if want_B:
+            B1 = torch.empty((K, self.L), dtype=torch.float64, device=Q.device)
+            B0 = torch.empty((K, self.L), dtype=torch.float64, device=Q.device)
+        ll = C.c_double(0.0)
+        torch.cuda.current_stream(Q.device).synchronize()
+        self._chk(self.lib.gnx_admix_sweep(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), C.c_int32(K),
+            C.c_void_p(Q.data_ptr() or None), C.c_void_p(F.data_ptr() or None),
+            C.c_void_p(A.data_ptr() or None),
+            C.c_void_p(B1.data_ptr() or None) if want_B else None,
+            C.c_void_p(B0.data_ptr() or None) if want_B else None,
+            C.byref(ll) if want_loglik else None, C.c_int32(0 if want_B else 1),
+            C.c_int64(int(budget or 0))))
+        return dict(A=A, B1=B1, B0=B0, loglik=float(ll.value) if want_loglik else None)
+
+    def admix_info(self):
+        """of the last admix_sweep: dict(kernel_ms, launches, chunks (over the individuals),
+        instance (the K of the template instance that ran))"""
+        ms, n, nc, inst = C.c_double(), C.c_int64(), C.c_int64(), C.c_int32()
+        self._chk(self.lib.gnx_admix_info(self.h, C.byref(ms), C.byref(n), C.byref(nc),
+                                          C.byref(inst)))
+        return dict(kernel_ms=ms.value, launches=int(n.value), chunks=int(nc.value),
+                    instance=int(inst.value))
 
     # -- identity tracts of the phased genomes (csrc/gnx_tracts.hip) ------------------------
     def _tract_args(self, pos, brk, edges):

@@ -371,6 +371,12 @@ struct gnx_state {
   double cost_ms = 0.0;
   int64_t cost_launches = 0, cost_rounds = 0, cost_batches = 0;
 
+  // admixture sweeps (gnx_admix.hip): the kernel time and launches of the last call, its chunks
+  // over the individuals and the template instance (K) that ran
+  double admix_ms = 0.0;
+  int64_t admix_launches = 0, admix_chunks = 0;
+  int32_t admix_instance = 0;
+
   // traits etc
   GnxTrait traits[GNX_MAX_TRAITS];
   // selected loci: all trait loci concatenated trait-major (n_tl of them), then the

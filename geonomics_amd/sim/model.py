@@ -989,6 +989,31 @@ class Model:
         return spp._calc_ne(method=method, min_c=min_c, min_maf=min_maf,
                             individs=self._test_sample(spp, individs, n), loci=loci)
 
+    def calc_ancestry(self, K, spp=0, individs=None, n=None, loci=None, init='pca', seed=None,
+                      accelerate=True, tol=1e-4, max_sweeps=2000, fixed_F=None):
+        """model-based ancestry (an extension: the reference has no such analysis): the
+        admixture model of STRUCTURE / ADMIXTURE with K ancestral populations (1..16), fitted
+        by EM with every sweep computed on the device from the packed genomes - individual
+        ancestry proportions Q and ancestral allele frequencies F, the description of clines,
+        contact zones and introductions (add_individuals) and the usual covariate beside PCs
+        in a GEA.  individs, or a random sample of n, and loci (a list, or 'neutral': the loci
+        under no selection) restrict the analysis.  init: 'pca' (Q from the first K - 1 genetic
+        PCs, min-max scaled; no clustering), 'random' (from seed) or a pair of arrays (Q, F).
+        accelerate: SQUAREM extrapolation, each accepted only if it does not lower the
+        log-likelihood.  The fit stops when an accepted step gains less than tol in
+        log-likelihood, or after max_sweeps sweeps.
+        fixed_F [K][loci used] holds the frequencies and fits Q alone (projection).  For a large
+        population fit on a sample first, res = calc_ancestry(K, n=2000), then project
+        everybody onto its frequencies: calc_ancestry(K, fixed_F=res['F']) - one pass over the
+        genomes per sweep and no frequency update.
+        -> dict: Q [n][K] (rows: individs, ascending ids; components by decreasing mean
+        ancestry, under fixed_F in its order), F [K][loci used], loci, individs, loglik (the
+        trace of accepted log-likelihoods), n_sweeps, converged, n_params, aic, bic"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_ancestry(K, individs=self._test_sample(spp, individs, n), loci=loci,
+                                  init=init, seed=seed, accelerate=accelerate, tol=tol,
+                                  max_sweeps=max_sweeps, fixed_F=fixed_F)
+
     def calc_roh(self, spp=0, min_len=0.01, min_loci=50, unit='morgans', individs=None, n=None,
                  edges=None, cover=False):
         """runs of homozygosity and the genomic inbreeding coefficient F_ROH per individual (an

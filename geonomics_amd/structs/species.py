@@ -1509,6 +1509,50 @@ class Species:
                     n_loci_kept=int((np.minimum(c1, n_chrom - c1) >= mm).sum()),
                     min_c=float(min_c))
 
+    # -- model-based ancestry (sim/ancestry.py; csrc/gnx_admix.hip) ---------------------------
+    def _calc_ancestry(self, K, individs=None, loci=None, init='pca', seed=None, accelerate=True,
+                       tol=1e-4, max_sweeps=2000, fixed_F=None, budget=None):
+        """the admixture model of STRUCTURE / ADMIXTURE fitted by (accelerated) EM to the living
+        individuals asked for (all by default) at `loci` (all by default; 'neutral': the loci
+        under no selection), every sweep taken on the device from the packed genomes
+        (gnx_admix_sweep; sim/ancestry.fit describes the driver, its initialisations and what it
+        returns).  fixed_F [K][the loci used]: projection onto held frequencies.  seed None
+        with init='random': drawn from the Species' generator.  budget: bytes of partial sums
+        per chunk of individuals of one sweep (None: the library's default)
+        -> sim/ancestry.fit's dict; individs = the ids (ascending, the rows of Q), loci = the
+        loci used (ascending, the columns of F)"""
+        import torch
+        from ..sim import ancestry as _an
+        who = 'calc_ancestry'
+        K = _an.check_K(K)
+        if self.gen_arch is None or self._dev.L == 0:
+            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
+        if not self.__dict__.get('_genomes_assigned', False):
+            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
+                             'model in first' % who)
+        ids, slots = self._geno_sample(individs)
+        if ids.size < 1:
+            raise ValueError('%s: at least one individual' % who)
+        if isinstance(loci, str):
+            if loci != 'neutral':
+                raise ValueError("%s: loci: a list of loci, None or 'neutral' (got %r)"
+                                 % (who, loci))
+            loci = self.gen_arch.neut_loci
+        loci_u, mask = self._geno_loci(loci)
+        L_u = self._dev.L if loci_u is None else int(loci_u.size)
+        pcs = None
+        if isinstance(init, str) and init == 'pca' and K > 1:
+            _, pcs, _ = self._calc_genetic_PCA(n_pcs=K - 1, individs=ids, loci=loci_u)
+        if seed is None and isinstance(init, str) and init == 'random':
+            seed = int(self._rng.randint(0, 2 ** 31 - 1))
+        tdev = torch.device('cuda', int(self._dev.cfg.device))
+        sweep = _an.device_sweep(self._dev, slots, loci_u, mask, budget)
+        return _an.fit(sweep, ids.size, L_u, K, init=init, seed=seed, accelerate=accelerate,
+                       tol=tol, max_sweeps=max_sweeps, fixed_F=fixed_F, pcs=pcs,
+                       put=lambda a: torch.as_tensor(np.asarray(a, np.float64), device=tdev),
+                       loci=np.arange(L_u, dtype=np.int64) if loci_u is None else loci_u,
+                       individs=ids)
+
     # -- identity tracts of the phased genomes (sim/tracts.py; csrc/gnx_tracts.hip) -----------
     # word steps (haplotype pairs x genome words) one pair scan may take: 4096 individuals at
     # 10^5 loci are 5.2e10

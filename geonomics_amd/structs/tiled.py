@@ -92,6 +92,10 @@ class TiledSpecies(Species):
         raise NotImplementedError('calc_ne with a Species tiled over several GPUs is not '
                                   'implemented; run the model on one GPU')
 
+    def _calc_ancestry(self, *args, **kw):
+        raise NotImplementedError('calc_ancestry with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
     # -- identity tracts: not over tiles (a pair of individuals of different tiles: a gather of
     # the sample)
     def _calc_roh(self, *args, **kw):

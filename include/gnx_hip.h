@@ -884,6 +884,52 @@ int gnx_tracts_pairs(gnx_state* h, int64_t n, const int64_t* slots, const int64_
  * not read; gnx_tracts_pairs: the gather's); each may be NULL                                  */
 int gnx_tracts_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* bytes_read);
 
+/* ---- model-based ancestry (csrc/gnx_admix.hip; the reference has no such analysis) -------------
+ * One EM sweep of the admixture model of STRUCTURE / ADMIXTURE: individual i draws each of its
+ * two alleles at locus l from ancestral population k with probability q_ik, and that allele is 1
+ * with probability f_kl.  The sweep returns the numerators of the FRAPPE / ADMIXTURE EM update
+ * and the log-likelihood; the update, its clamps and the acceleration are the caller's
+ * (geonomics_amd/sim/ancestry.py).
+ * Inputs: the sample of n individuals (n, slots as in the genetic PCA calls above); the loci of
+ * locus_mask (u64 [W64], NULL: all L), L_u of them - padding bits past L, masked-out loci and
+ * the zero words of the padding contribute to nothing; dosages d_il in {0, 1, 2}; 1 <= K <= 16;
+ * Q fp64 [n][K] with positive rows; F fp64 [K][L] in [eps, 1 - eps], indexed by genome locus
+ * (entries of unused loci are never read into a result); g_kl = 1 - f_kl rounded to fp64.
+ * Per genotype of a used locus:
+ *   p_il = sum_k q_ik f_kl,   r_il = sum_k q_ik g_kl,   u = d / p,   v = (2 - d) / r.
+ * Outputs, fp64:
+ *   A[i][k]  = sum over used l of (u f_kl + v g_kl)         the ancestry numerators
+ *   B1[k][l] = sum_i u q_ik,   B0[k][l] = sum_i v q_ik        the frequency numerators; 0 at
+ *                                                             every unused locus
+ *   *loglik  = sum_il d ln p + (2 - d) ln r                   only when loglik != NULL (the two
+ *                                                             logarithms cost as much as the rest)
+ * The EM update is q'_ik = q_ik A_ik / (2 L_u) and f'_kl = f_kl B1 / (f_kl B1 + g_kl B0), f'
+ * clamped to [eps, 1 - eps], q' clamped below at eps and its rows renormalised, eps = 1e-6.
+ * For every valid input sum_k q_ik A_ik = 2 L_u.
+ * The device takes p and r by K FMAs each and u, v from ONE division: t = 1 / (p r),
+ * u = d (r t), v = (2 - d) (p t), three roundings beside those of p (r), and one logarithm
+ * per genotype: 2 ln r, ln(p r) or 2 ln p for d = 0, 1, 2; its sums are taken in
+ * an order fixed by the arguments and the budget, without floating-point atomics, so a call
+ * repeated is bit-equal in every output.  Error bounds: tests/test_gpu_ancestry.py.
+ * Q, F, A, B1, B0 are DEVICE pointers with the synchronisation contract of gnx_geno_matmul;
+ * loglik is a HOST double.  skip_b != 0: B1 and B0 are not computed and may be NULL (F held
+ * fixed: projection).  budget: bytes of partial sums one chunk of individuals may take (0: the
+ * default, 256 MiB); above it the individuals are worked off in chunks of whole 64-row tiles,
+ * one after the other (at least one tile per chunk).  Preconditions as the genetic PCA calls; a
+ * pending crossover is cut first and an uncompacted population gathered; no individual, genome
+ * or later draw is changed.  Refused (return 1) before anything is launched: no genomes, ghost
+ * records, K outside 1..16, n < 1, an empty locus set, a null pointer, budget < 0, a slot out
+ * of range.                                                                                   */
+int gnx_admix_sweep(gnx_state* h, int64_t n, const int64_t* slots /*NULL: all living*/,
+                    const uint64_t* locus_mask, int32_t K, const double* Q /*[n][K]*/,
+                    const double* F /*[K][L]*/, double* A /*[n][K]*/, double* B1 /*[K][L]*/,
+                    double* B0 /*[K][L]*/, double* loglik /*host, or NULL*/, int32_t skip_b,
+                    int64_t budget);
+/* of the last gnx_admix_sweep: its kernels' HIP-event time (ms), their number, the chunks over
+ * the individuals and the template instance that ran (its K); each may be NULL               */
+int gnx_admix_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* chunks,
+                   int32_t* instance);
+
 /* ---- lineages through the recorded pedigree (csrc/gnx_lineage.hip; reference
  *      structs/genome.py:1638-1782 _get_lineage_dicts, structs/species.py:1242-1343) ---------
  * The pedigree is recorded on the host (geonomics_amd/structs/pedigree.py, TreeTables.
