@@ -72,6 +72,7 @@ EXPORTS = [
     'gnx_dist_perm_sums_mat',
     'gnx_cost_surfaces', 'gnx_cost_matrix', 'gnx_cost_budget', 'gnx_cost_info',
     'gnx_admix_sweep', 'gnx_admix_info',
+    'gnx_sweeps_scan', 'gnx_sweeps_info',
 ]
 
 
@@ -1389,6 +1390,63 @@ class Device:
         ms, n, nb = C.c_double(), C.c_int64(), C.c_int64()
         self._chk(self.lib.gnx_tracts_info(self.h, C.byref(ms), C.byref(n), C.byref(nb)))
         return dict(kernel_ms=ms.value, launches=int(n.value), bytes_read=int(nb.value))
+
+    # -- haplotype sweep scans (csrc/gnx_sweeps.hip) -------------------------------------------
+    def sweeps_scan(self, loci, pos, brk=None, cls=None, cores=None, slots=None, min_minor=2,
+                    cut_num=0, cut_den=1, max_gap=0, max_extent=0, max_work=0, curve=False):
+        """the area under the curve of identical haplotype pairs around core loci
+        (include/gnx_hip.h, gnx_sweeps_scan).  loci int32 [n_loci] distinct; pos int64 [n_loci]
+        non-decreasing; brk uint8 [n_loci] or None; cls uint8 [2 n] of 0 / 1 / 255 or None (the
+        class is the allele at the core); cores: request indices or None (every kept locus).
+        max_work <= 0: only the work and c1 are computed
+        -> dict(work, c1 int64 [n_loci], area int64, steps int32, status uint8 [n_loci][2][2],
+        curve int64 [2][2][n_loci] or None); all but work and c1 are None when max_work <= 0"""
+        s, n = self._geno_slots(slots)
+        loci = _arr(loci, np.int32).ravel()
+        pos = _arr(pos, np.int64).ravel()
+        if pos.size != loci.size:
+            raise ValueError('pos: %d entries for %d loci' % (pos.size, loci.size))
+        b = None
+        if brk is not None:
+            b = _arr(np.asarray(brk) != 0, np.uint8).ravel()
+            if b.size != loci.size:
+                raise ValueError('brk: %d entries for %d loci' % (b.size, loci.size))
+        k = None
+        if cls is not None:
+            k = _arr(cls, np.uint8).ravel()
+            if k.size != 2 * n:
+                raise ValueError('cls: %d entries for %d chromosomes' % (k.size, 2 * n))
+        co, n_cores = None, 0
+        if cores is not None:
+            co = _arr(cores, np.int32).ravel()
+            n_cores = int(co.size)
+            if n_cores == 0:
+                co = np.zeros(1, np.int32)
+        m = max(1, int(loci.size))
+        c1 = np.zeros(m, np.int64)
+        area = np.zeros((m, 2, 2), np.int64)
+        steps = np.zeros((m, 2, 2), np.int32)
+        status = np.zeros((m, 2, 2), np.uint8)
+        cv = np.zeros((2, 2, m), np.int64) if curve else None
+        work = np.zeros(1, np.int64)
+        self._chk(self.lib.gnx_sweeps_scan(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), C.c_int32(int(loci.size)),
+            _ptr(loci if loci.size else np.zeros(1, np.int32), C.c_int32),
+            _ptr(pos if pos.size else np.zeros(1, np.int64), C.c_int64), _ptr(b, C.c_uint8),
+            _ptr(k, C.c_uint8), C.c_int32(n_cores), _ptr(co, C.c_int32),
+            C.c_int32(int(min_minor)), C.c_int32(int(cut_num)), C.c_int32(int(cut_den)),
+            C.c_int64(int(max_gap)), C.c_int64(int(max_extent)), C.c_int64(int(max_work)),
+            _ptr(work, C.c_int64), _ptr(c1, C.c_int64), _ptr(area, C.c_int64),
+            _ptr(steps, C.c_int32), _ptr(status, C.c_uint8), _ptr(cv, C.c_int64)))
+        if max_work <= 0:
+            return dict(work=int(work[0]), c1=c1, area=None, steps=None, status=None, curve=None)
+        return dict(work=int(work[0]), c1=c1, area=area, steps=steps, status=status, curve=cv)
+
+    def sweeps_info(self):
+        """of the last sweeps_scan: dict(kernel_ms, launches, steps_total)"""
+        ms, n, ns = C.c_double(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.gnx_sweeps_info(self.h, C.byref(ms), C.byref(n), C.byref(ns)))
+        return dict(kernel_ms=ms.value, launches=int(n.value), steps_total=int(ns.value))
 
     # -- lineages through the recorded pedigree (csrc/gnx_lineage.hip) -------------------
     @staticmethod

@@ -365,6 +365,11 @@ struct gnx_state {
   double tr_ms = 0.0;
   int64_t tr_launches = 0, tr_bytes = 0;
 
+  // haplotype sweep scans (gnx_sweeps.hip): the kernel time and launches of the last call and
+  // the completed steps summed over its scans
+  double sw_ms = 0.0;
+  int64_t sw_launches = 0, sw_steps = 0;
+
   // least-cost distances (gnx_cost.hip): bytes of distance rasters one batch of sources may
   // take (0: the default), and the kernel time, launches, rounds and batches of the last call
   int64_t cost_budget = 0;
@@ -990,6 +995,17 @@ struct GnxCallTimer {
     return 0;
   }
 };
+
+// gnx_ld.hip: the bit rows of a whole request into scratch, by the kernels of gnx_ld_bins
+// (k_ld_bits, k_ld_rowsum).  (*T)[j][q], row pitch *pitch words (the chromosome words rounded up
+// to 16; the words past the sample and the bits past n_chrom are 0), = the bits of the sampled
+// chromosomes 64 q .. 64 q + 63 (d_rows: the sample's genome rows) at loci[j]; (*c1)[j] = the
+// popcount of row j.  jof [W64 * 64]: locus -> index in the request or -1, the loci checked by
+// the caller.  The launches are timed by tm
+int gnx_ld_bit_rows(gnx_state* h, GnxScratch& s, GnxCallTimer& tm, const int32_t* d_rows,
+                    int64_t n_chrom, int32_t n_loci, const int32_t* loci,
+                    const std::vector<int32_t>& jof, unsigned long long** T, int64_t* pitch,
+                    long long** c1);
 
 // ---- lineage calls (gnx_lineage.hip, gnx_simplify.hip) -----------------------------------
 #define LIN_BUDGET (256ll << 20)  // bytes of output per launch unless gnx_lineage_budget says so

@@ -279,6 +279,49 @@ __global__ void k_ld_total(int blocks, const long long* __restrict__ ipart,
   }
 }
 
+// buf [buf_words], zeroed here, = the bit rows of the request's indices ja .. ja + nj - 1 (row
+// pitch `pitch` words; rows past nj and words past the sample stay 0); lines[n_lines]: the genome
+// lines that hold one of them; c1 != null: c1[0 .. nj) = their popcounts.  -> kernels launched
+static int ld_transpose(gnx_state* h, int64_t n_chrom, int64_t nq, int64_t pitch, int n_lines,
+                        const int32_t* d_lines, const int32_t* d_rows, const int32_t* d_jof,
+                        int ja, int nj, u64* buf, int64_t buf_words, long long* c1) {
+  (void)hipMemsetAsync(buf, 0, (size_t)buf_words * sizeof(u64), h->stream);
+  hipLaunchKernelGGL(k_ld_bits, dim3((unsigned)((nq + 3) / 4), (unsigned)std::min(n_lines, 64)),
+                     dim3(256), 0, h->stream, n_chrom, nq, pitch, n_lines, d_lines, d_rows,
+                     (const LdChunk*)h->G, gnx_halves(h), h->W64, d_jof, ja, nj, buf);
+  if (!c1) return 1;
+  hipLaunchKernelGGL(k_ld_rowsum, dim3((unsigned)((nj + 3) / 4)), dim3(256), 0, h->stream, nj, nq,
+                     pitch, buf, c1);
+  return 2;
+}
+
+// see gnx_internal.h: the bit rows of a whole request at once, for the callers outside this file
+int gnx_ld_bit_rows(gnx_state* h, GnxScratch& s, GnxCallTimer& tm, const int32_t* d_rows,
+                    int64_t n_chrom, int32_t n_loci, const int32_t* loci,
+                    const std::vector<int32_t>& jof, unsigned long long** T, int64_t* pitch_out,
+                    long long** c1) {
+  const int64_t nq = (n_chrom + 63) / 64;
+  const int64_t pitch = (nq + LD_K - 1) / LD_K * LD_K;
+  std::vector<int32_t> lines((size_t)n_loci);
+  for (int j = 0; j < n_loci; ++j) lines[(size_t)j] = loci[j] >> 10;
+  std::sort(lines.begin(), lines.end());
+  lines.erase(std::unique(lines.begin(), lines.end()), lines.end());
+  int32_t *d_jof = nullptr, *d_lines = nullptr;
+  GNXCHK(s.get(T, (size_t)n_loci * pitch));
+  GNXCHK(s.get(c1, (size_t)n_loci));
+  GNXCHK(s.get(&d_jof, jof.size()));
+  GNXCHK(s.get(&d_lines, lines.size()));
+  GNXCHK(gnx_h2d(h, d_jof, jof.data(), jof.size() * sizeof(int32_t)));
+  GNXCHK(gnx_h2d(h, d_lines, lines.data(), lines.size() * sizeof(int32_t)));
+  tm.start();
+  const int launches = ld_transpose(h, n_chrom, nq, pitch, (int)lines.size(), d_lines, d_rows,
+                                    d_jof, 0, n_loci, *T, (int64_t)n_loci * pitch, *c1);
+  HIPCHK(hipGetLastError());
+  GNXCHK(tm.stop(launches));
+  *pitch_out = pitch;
+  return 0;
+}
+
 extern "C" int gnx_ld_budget(gnx_state* h, int64_t bytes) {
   if (bytes < 0) {
     gnx_set_error("gnx_ld_budget: bytes >= 0 (0: the default)");
@@ -470,24 +513,17 @@ extern "C" int gnx_ld_bins(gnx_state* h, int64_t n, const int64_t* slots, int32_
   HIPCHK(hipMemsetAsync(d_ftot, 0, mf * sizeof(double), h->stream));
   HIPCHK(hipMemsetAsync(d_c1, 0, (size_t)n_loci * sizeof(long long), h->stream));
 
-  const GnxHalves H = gnx_halves(h);
   std::vector<bool> counted((size_t)nblk, false);
   // block bk into buf (rows past the block and words past the sample: 0), and its c1 the first
   // time; -> kernels launched
   auto transpose = [&](int bk, u64* buf) -> int {
     const int ja = bk * tpb * 64;
     const int nj = (int)std::min<int64_t>(n_loci - ja, (int64_t)tpb * 64);
-    const int n_lines = line_off[(size_t)bk + 1] - line_off[(size_t)bk];
-    (void)hipMemsetAsync(buf, 0, (size_t)buf_words * sizeof(u64), h->stream);
-    hipLaunchKernelGGL(k_ld_bits, dim3((unsigned)((nq + 3) / 4), (unsigned)std::min(n_lines, 64)),
-                       dim3(256), 0, h->stream, n_chrom, nq, pitch, n_lines,
-                       d_lines + line_off[(size_t)bk], d_rows, (const LdChunk*)h->G, H, W64, d_jof,
-                       ja, nj, buf);
-    if (counted[(size_t)bk]) return 1;
+    const bool first = !counted[(size_t)bk];
     counted[(size_t)bk] = true;
-    hipLaunchKernelGGL(k_ld_rowsum, dim3((unsigned)((nj + 3) / 4)), dim3(256), 0, h->stream, nj, nq,
-                       pitch, buf, d_c1 + ja);
-    return 2;
+    return ld_transpose(h, n_chrom, nq, pitch, line_off[(size_t)bk + 1] - line_off[(size_t)bk],
+                        d_lines + line_off[(size_t)bk], d_rows, d_jof, ja, nj, buf, buf_words,
+                        first ? d_c1 + ja : nullptr);
   };
   const long long mm = std::max<long long>(1, min_minor);
   std::vector<LdTask> tasks;

@@ -1051,6 +1051,71 @@ class Model:
                                      n_classes=n_classes, max_dist=max_dist,
                                      tract_edges=tract_edges, cover=cover, max_work=max_work)
 
+    def calc_ihs(self, spp=0, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None,
+                 max_extent=None, individs=None, n=None, loci=None, n_freq_bins=20,
+                 keep_edge=False, max_work=None):
+        """the integrated haplotype score iHS of every locus (an extension: the reference has no
+        haplotype-based scan for selection), from the phased genomes of at most 2048
+        individuals (individs, or a random sample of n), scanned on the device: the haplotypes
+        carrying the derived allele (1) at a core locus and those carrying the ancestral one are
+        followed outwards until their EHH falls below cutoff; iHH is the area under each curve
+        and ihs_unstd = ln(iHH_1 / iHH_0), large where the derived allele sits on unusually long
+        haplotypes - a sweep in progress.  unit: 'morgans' (the architecture's map), 'loci' or
+        'sites' (nSL).  Loci below min_maf in the sample are left out.  A rate of 0.5 or more is
+        a chromosome boundary; under the template's free recombination every scan ends at once.
+        max_gap, max_extent (in the unit) bound a step and the whole scan; keep_edge keeps the
+        loci whose scans reached an edge before the cutoff.  max_work bounds the word steps of
+        the device call; a request above it raises ValueError
+        -> dict: loci, pos, freq, ihh1, ihh0, ihs_unstd, ihs (standardised within n_freq_bins
+        bins of the derived-allele frequency), status, steps ([n_loci][2][2]: direction,
+        class), kept, c1, n_chrom, work, ids, unit"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_ihs(unit=unit, min_maf=min_maf, cutoff=cutoff, max_gap=max_gap,
+                             max_extent=max_extent, individs=self._test_sample(spp, individs, n),
+                             loci=loci, n_freq_bins=n_freq_bins, keep_edge=keep_edge,
+                             max_work=max_work)
+
+    def calc_nsl(self, spp=0, min_maf=0.05, cutoff=0.05, max_gap=None, max_extent=None,
+                 individs=None, n=None, loci=None, n_freq_bins=20, keep_edge=False,
+                 max_work=None):
+        """nSL (Ferrer-Admetlla et al. 2014): calc_ihs with unit='sites', distances counted in
+        kept (segregating) loci, which needs no map -> as calc_ihs"""
+        return self.calc_ihs(spp=spp, unit='sites', min_maf=min_maf, cutoff=cutoff,
+                             max_gap=max_gap, max_extent=max_extent, individs=individs, n=n,
+                             loci=loci, n_freq_bins=n_freq_bins, keep_edge=keep_edge,
+                             max_work=max_work)
+
+    def calc_xpehh(self, groups, spp=0, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None,
+                   max_extent=None, individs=None, n=None, loci=None, keep_edge=False,
+                   max_work=None):
+        """XP-EHH of every locus between two groups of individuals (an extension; groups as
+        calc_fst takes them, exactly two, at most 2048 individuals together: individs, or a
+        random sample of n of the living, restrict them): iHH of all haplotypes of each group
+        around each core locus, scanned on the device, and xpehh_unstd = ln(iHH_a / iHH_b) -
+        positive where a sweep is complete or nearly so in group a and not in group b.  One
+        departure from selscan: each population is scanned to its own cutoff, not to the cutoff
+        of the pooled EHH.  The other arguments as calc_ihs
+        -> dict: loci, pos, ihh_a, ihh_b, xpehh_unstd, xpehh (standardised over all defined
+        loci), status, steps, kept, c1, names, n_a, n_b, work, ids, unit"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_xpehh(groups, unit=unit, min_maf=min_maf, cutoff=cutoff,
+                               max_gap=max_gap, max_extent=max_extent,
+                               individs=self._test_sample(spp, individs, n), loci=loci,
+                               keep_edge=keep_edge, max_work=max_work)
+
+    def calc_ehh(self, locus, spp=0, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None,
+                 max_extent=None, individs=None, n=None, loci=None, max_work=None):
+        """the decay of extended haplotype homozygosity around one core locus (an extension):
+        per locus the scan reached, the share of pairs of haplotypes carrying the derived
+        (ehh1) or ancestral allele (ehh0) at the core that are identical from the core to there,
+        scanned on the device.  The arguments as calc_ihs
+        -> dict: locus, loci, pos, ehh1, ehh0 (NaN at loci not kept and past the scan's end),
+        status, steps ([2][2]: direction, class), c1, n_chrom, ids, unit"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_ehh(locus, unit=unit, min_maf=min_maf, cutoff=cutoff, max_gap=max_gap,
+                             max_extent=max_extent, individs=self._test_sample(spp, individs, n),
+                             loci=loci, max_work=max_work)
+
     # -- Fst, diversity and the SFS of groups of individuals (sim/fst.py) ----------------
     def calc_fst(self, groups, spp=0, loci=None, method='HsHt', mean=True, est_Hs=False,
                  include_zeros=False):

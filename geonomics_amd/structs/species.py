@@ -1689,6 +1689,181 @@ class Species:
                     longest=_tr.from_units(got['longest'], unit), by_dist=by, hist=hist,
                     cover=got['cover'], work=got['work'], unit=unit)
 
+    # -- haplotype sweep scans (sim/sweeps.py; csrc/gnx_sweeps.hip) ----------------------------
+    # word steps (scanned cores x 4 scans x chromosome words x kept loci) one call may take: the
+    # bound no scan reaches, since a scan ends at its cutoff
+    _SWEEP_MAX_WORK = 1 << 42
+
+    def _sweep_request(self, who, individs, loci, unit, min_maf, cutoff, max_gap, max_extent,
+                       max_work):
+        """what the sweep calls share: the request checks of _ld_request, the integer map of the
+        unit (for 'sites' after a probe call that only counts c1), the thresholds as integers
+        -> dict(ids, slots, loci, pos, brk, scale, min_minor, kw), kw the keyword arguments of
+        Device.sweeps_scan"""
+        from ..sim import sweeps as _sw
+        if unit not in ('morgans', 'loci', 'sites'):
+            raise ValueError("%s: unit: 'morgans', 'loci' or 'sites', not %r" % (who, unit))
+        num, den = _sw.cutoff_fraction(cutoff)
+        lim = {}
+        for name, v in (('max_gap', max_gap), ('max_extent', max_extent)):
+            if v is not None and (isinstance(v, bool) or not 0 < float(v) < np.inf):
+                raise ValueError('%s: %s: a positive length in %s, or None (got %r)'
+                                 % (who, name, unit, v))
+            lim[name] = v
+        if max_work is None:
+            max_work = self._SWEEP_MAX_WORK
+        if isinstance(max_work, bool) or int(max_work) != max_work or max_work < 1:
+            raise ValueError('%s: max_work: a positive number of word steps (got %r)'
+                             % (who, max_work))
+        ids, slots, loci_u, _, mm = self._ld_request(who, individs, loci, 'loci', min_maf)
+        if ids.size > _sw.MAX_N:
+            raise ValueError('%s: 1..%d individuals per call (got %d): sample them with n=... or '
+                             'individs=...' % (who, _sw.MAX_N, ids.size))
+        mm = max(2, mm)
+        rec = self.gen_arch.recombinations
+        rates = np.zeros(self._dev.L)
+        rates[rec._positions] = rec._rates
+        kept = None
+        if unit == 'sites':
+            probe = self._dev.sweeps_scan(loci_u, loci_u, slots=slots, min_minor=mm, max_work=0)
+            kept = np.zeros(self._dev.L, bool)
+            kept[loci_u] = _sw.kept_loci(probe['c1'], 2 * ids.size, mm)
+        pos, brk, scale = _sw.sweep_map(rates, unit, kept)
+        nb = np.cumsum(brk)
+        b = np.zeros(loci_u.size, np.uint8)
+        b[1:] = nb[loci_u[1:]] > nb[loci_u[:-1]]
+        kw = dict(min_minor=mm, cut_num=num, cut_den=den, max_work=int(max_work))
+        for name, v in lim.items():
+            kw[name] = 0 if v is None else max(1, int(np.floor(float(v) * scale)))
+        return dict(ids=ids, slots=slots, loci=loci_u, pos=pos[loci_u], brk=b, scale=scale,
+                    min_minor=mm, kw=kw)
+
+    def _sweep_call(self, who, rq, cls=None, cores=None, curve=False):
+        """one gnx_sweeps_scan call; the library's refusal of a request above max_work becomes a
+        ValueError with advice"""
+        try:
+            return self._dev.sweeps_scan(rq['loci'], rq['pos'], rq['brk'], cls, cores,
+                                         rq['slots'], curve=curve, **rq['kw'])
+        except nat.GnxError as err:
+            if 'exceed max_work' not in str(err):
+                raise
+            raise ValueError('%s: %s: analyse a sample (n=...) or fewer loci (loci=...), or '
+                             'raise max_work' % (who, err)) from None
+
+    def _calc_ihs(self, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None, max_extent=None,
+                  individs=None, loci=None, n_freq_bins=20, keep_edge=False, max_work=None):
+        """the integrated haplotype score of every locus (Voight et al. 2006) from the phased
+        genomes of the living individuals asked for (at most 2048), scanned on the device
+        (gnx_sweeps_scan): around each core locus the haplotypes carrying the derived allele (1)
+        and those carrying the ancestral one (0) are followed outwards in both directions until
+        their EHH - the share of pairs still identical - falls below cutoff, and the area under
+        each curve is iHH.  unit: 'morgans' on the map of the architecture's recombination rates,
+        'loci' (locus numbers) or 'sites' (the rank among the loci kept: nSL).  Loci whose
+        minor-allele frequency in the sample is below min_maf (or whose minor count is below 2)
+        are neither cores nor steps.  A recombination rate of 0.5 or more is a chromosome
+        boundary no scan crosses: under the template's free recombination every scan ends at
+        once.  max_gap, max_extent (in the unit): a scan stops before a step longer than max_gap
+        and before leaving max_extent around the core.  A locus one of whose scans reached an
+        edge, a break or a gap before the cutoff has no score unless keep_edge.  ihs is ihs_unstd
+        standardised within n_freq_bins bins of the derived-allele frequency.  max_work: the
+        word steps (cores x 4 scans x words of 64 chromosomes x kept loci) the call may take
+        -> dict: loci, pos (in the unit), freq (of allele 1), ihh1, ihh0 (in the unit),
+        ihs_unstd = ln(ihh1 / ihh0), ihs, status [n_loci][2][2] ([direction: left, right]
+        [class]; 0 cutoff, 1 edge or break, 2 gap, 3 extent, 4 class below two chromosomes, 5 not
+        scanned), steps, kept, c1, n_chrom, work, ids, unit"""
+        from ..sim import sweeps as _sw
+        who = 'calc_ihs'
+        rq = self._sweep_request(who, individs, loci, unit, min_maf, cutoff, max_gap, max_extent,
+                                 max_work)
+        got = self._sweep_call(who, rq)
+        n_chrom = 2 * rq['ids'].size
+        c1 = got['c1']
+        unstd, h1, h0 = _sw.ihs_unstandardized(got['area'], got['status'], c1, n_chrom,
+                                               keep_edge=bool(keep_edge))
+        freq = c1 / float(n_chrom)
+        return dict(loci=rq['loci'], pos=rq['pos'] / float(rq['scale']), freq=freq,
+                    ihh1=h1 / rq['scale'], ihh0=h0 / rq['scale'], ihs_unstd=unstd,
+                    ihs=_sw.standardize_by_frequency(unstd, freq, n_freq_bins),
+                    status=got['status'], steps=got['steps'],
+                    kept=_sw.kept_loci(c1, n_chrom, rq['min_minor']), c1=c1, n_chrom=n_chrom,
+                    work=got['work'], ids=rq['ids'], unit=unit)
+
+    def _calc_xpehh(self, groups, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None,
+                    max_extent=None, individs=None, loci=None, keep_edge=False, max_work=None):
+        """the cross-population extended haplotype homozygosity of every locus (Sabeti et al.
+        2007) between two groups of individuals (groups as calc_fst takes them; exactly two
+        groups; individs restricts both), scanned on the device: around each core locus the
+        haplotypes of group a and those of group b are followed outwards, whatever allele they
+        carry at the core, and xpehh_unstd = ln(iHH_a / iHH_b); positive where group a carries
+        the longer haplotypes.  Loci are kept by their frequency in the two groups pooled.  One
+        departure from selscan: each population is scanned to its own cutoff, not until the
+        pooled EHH falls below it.  The other arguments as calc_ihs
+        -> dict: loci, pos, ihh_a, ihh_b, xpehh_unstd, xpehh (standardised over all defined
+        loci), status, steps, kept, c1, names, n_a, n_b, work, ids, unit"""
+        from ..sim import fst as _fst
+        from ..sim import sweeps as _sw
+        who = 'calc_xpehh'
+        # (the request checks come first: every living individual, as the groups see them)
+        all_ids = self._ld_request(who, None, None, 'loci', min_maf)[0]
+        names, order, start = _fst.make_groups(all_ids, groups)
+        if len(names) != 2:
+            raise ValueError('%s: exactly two groups (got %d)' % (who, len(names)))
+        member = np.full(all_ids.size, -1, np.int64)
+        member[order[:start[1]]] = 0
+        member[order[start[1]:]] = 1
+        if individs is not None:
+            ids_in = np.asarray(individs, dtype=np.int64).ravel()
+            member[~np.isin(all_ids, ids_in)] = -1
+        sample = all_ids[member >= 0]
+        rq = self._sweep_request(who, sample, loci, unit, min_maf, cutoff, max_gap, max_extent,
+                                 max_work)
+        grp = member[np.searchsorted(all_ids, rq['ids'])]
+        n_a, n_b = int((grp == 0).sum()), int((grp == 1).sum())
+        got = self._sweep_call(who, rq, cls=np.repeat(grp, 2).astype(np.uint8))
+        ha, hb = _sw.ihh_both(got['area'], got['status'], _sw.class_pairs(2 * n_a),
+                              _sw.class_pairs(2 * n_b), keep_edge=bool(keep_edge))
+        unstd = _sw.log_ratio(ha, hb)
+        n_chrom = 2 * rq['ids'].size
+        return dict(loci=rq['loci'], pos=rq['pos'] / float(rq['scale']), ihh_a=ha / rq['scale'],
+                    ihh_b=hb / rq['scale'], xpehh_unstd=unstd, xpehh=_sw.standardize(unstd),
+                    status=got['status'], steps=got['steps'],
+                    kept=_sw.kept_loci(got['c1'], n_chrom, rq['min_minor']), c1=got['c1'],
+                    names=names, n_a=n_a, n_b=n_b, work=got['work'], ids=rq['ids'], unit=unit)
+
+    def _calc_ehh(self, locus, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None,
+                  max_extent=None, individs=None, loci=None, max_work=None):
+        """the decay of extended haplotype homozygosity around one core locus (Sabeti et al.
+        2002), scanned on the device: per kept locus the scan reached, the share of pairs of
+        haplotypes carrying the derived (ehh1) or the ancestral allele (ehh0) at the core that
+        are still identical from the core to there; 1 at the core, NaN at loci that are not kept
+        and past the scan's end (the first value below the cutoff is included).  The arguments
+        as calc_ihs; the core must be a kept locus
+        -> dict: locus, loci, pos, ehh1, ehh0, status [2][2], steps [2][2], c1 (of the core),
+        n_chrom, ids, unit"""
+        from ..sim import sweeps as _sw
+        who = 'calc_ehh'
+        if isinstance(locus, bool) or int(locus) != locus:
+            raise ValueError('%s: locus: one locus number (got %r)' % (who, locus))
+        rq = self._sweep_request(who, individs, loci, unit, min_maf, cutoff, max_gap, max_extent,
+                                 max_work)
+        core = int(np.searchsorted(rq['loci'], int(locus)))
+        if core >= rq['loci'].size or rq['loci'][core] != int(locus):
+            raise ValueError('%s: locus %d is not among the loci of the request'
+                             % (who, int(locus)))
+        got = self._sweep_call(who, rq, cores=[core], curve=True)
+        n_chrom = 2 * rq['ids'].size
+        c1 = got['c1']
+        kept = _sw.kept_loci(c1, n_chrom, rq['min_minor'])
+        if not kept[core]:
+            raise ValueError('%s: locus %d is not kept: %d of %d chromosomes carry allele 1, the '
+                             'minor count is below %d (min_maf)'
+                             % (who, int(locus), c1[core], n_chrom, rq['min_minor']))
+        T = (_sw.class_pairs(n_chrom - c1[core]), _sw.class_pairs(c1[core]))
+        e0, e1 = _sw.ehh_curve(got['curve'], kept, core, T, rq['loci'].size)
+        return dict(locus=int(locus), loci=rq['loci'], pos=rq['pos'] / float(rq['scale']),
+                    ehh1=e1, ehh0=e0, status=got['status'][core], steps=got['steps'][core],
+                    c1=int(c1[core]), n_chrom=n_chrom, ids=rq['ids'], unit=unit)
+
     # -- lineages through the recorded pedigree (structs/pedigree.py; csrc/gnx_lineage.hip) ----
     # The reference simplifies its tables with tskit's default, which drops unary nodes: its
     # lineage at a locus lists only the ancestors that survive simplification for the current

@@ -106,6 +106,19 @@ class TiledSpecies(Species):
         raise NotImplementedError('calc_ibs_sharing with a Species tiled over several GPUs is '
                                   'not implemented; run the model on one GPU')
 
+    # -- haplotype sweep scans: not over tiles (one bit row holds the whole sample: a gather)
+    def _calc_ihs(self, *args, **kw):
+        raise NotImplementedError('calc_ihs with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
+    def _calc_xpehh(self, *args, **kw):
+        raise NotImplementedError('calc_xpehh with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
+    def _calc_ehh(self, *args, **kw):
+        raise NotImplementedError('calc_ehh with a Species tiled over several GPUs is not '
+                                  'implemented; run the model on one GPU')
+
     # -- lineages: not over tiles (each rank records its own births: the pedigree of a tiled
     # Species is in pieces, and a lineage crosses them)
     def _get_lineage_dicts(self, *args, **kw):

@@ -884,6 +884,63 @@ int gnx_tracts_pairs(gnx_state* h, int64_t n, const int64_t* slots, const int64_
  * not read; gnx_tracts_pairs: the gather's); each may be NULL                                  */
 int gnx_tracts_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* bytes_read);
 
+/* ---- haplotype sweep scans (csrc/gnx_sweeps.hip; the reference has no such analysis) -----------
+ * Extended haplotype homozygosity around core loci of the phased genomes, from which EHH, iHS,
+ * nSL and XP-EHH follow on the host (geonomics_amd/sim/sweeps.py).  Definitions:
+ * Sample.  n individuals in the order of `slots` (n, slots as gnx_geno_gram; slots distinct).
+ *   Chromosome 2 i + h is homologue h of sample i.  N = 2 n, with 1 <= n <= 2048.
+ * Request.  loci int32 [n_loci], distinct, in any order of locus number.  pos int64 [n_loci],
+ *   non-decreasing: the coordinate of loci[j] in an integer unit of the caller's.  brk uint8
+ *   [n_loci]: brk[j] != 0 means no scan passes between request index j - 1 and j (a chromosome
+ *   boundary); brk[0] is ignored; NULL means no breaks.
+ * Kept loci.  c1[j] = the sampled chromosomes that carry 1 at loci[j].  Locus j is KEPT iff
+ *   min(c1, N - c1) >= max(2, min_minor).  A locus that is not kept does not exist for the scan:
+ *   it is neither a core nor a step.  Its break is inherited by the next kept locus: a break
+ *   anywhere between two consecutive kept loci separates them.
+ * Classes.  cls == NULL: the class of a chromosome at core j is its allele at j (0 ancestral, 1
+ *   derived).  Otherwise cls is uint8 [N] of 0, 1 or 255, the same for every core; 255: the
+ *   chromosome is in neither class and is ignored (XP-EHH's two populations).  m_c = the size of
+ *   class c, T_c = m_c (m_c - 1) / 2.
+ * Scan of (core j, direction d: 0 left, 1 right, class c).  k_0 = j and P_0 = T_c.  Step s goes
+ *   from kept locus k_{s-1} to the next kept locus k_s in direction d.  P_s = the unordered pairs
+ *   of class-c chromosomes identical at every kept locus from j to k_s inclusive - the core itself
+ *   only when cls == NULL, where that is vacuous: with a class row two chromosomes of a class may
+ *   differ at the core; P_0 = T_c still and the core's own column is not compared.
+ * Status.  Before step s the scan stops, in this order of tests: status 1: there is no next kept
+ *   locus, or a break lies between; status 2: max_gap > 0 and |pos[k_s] - pos[k_{s-1}]| > max_gap;
+ *   status 3: max_extent > 0 and |pos[k_s] - pos[j]| > max_extent; after computing P_s, status 0:
+ *   P_s cut_den < cut_num T_c (the cutoff: the step that falls below is not integrated).  A class
+ *   with m_c < 2 has status 4, area 0 and steps 0; a locus that is not kept, or not among cores,
+ *   has status 5, area 0 and steps 0.
+ * Integration.  Every completed step s adds (P_{s-1} + P_s) |pos[k_s] - pos[k_{s-1}]| to area,
+ *   so iHH = area / (2 T_c) in the caller's unit.  steps = the completed steps.
+ * Everything the device returns is an integer function of the sample: every output is exact,
+ * order-free, and bit-equal to the restatement (sim/sweeps.brute_scan) and to a repeated call.
+ * cores int32 [n_cores]: request indices of the loci to scan, distinct (NULL: every kept locus).
+ * HOST outputs: c1 int64 [n_loci]; area int64, steps int32, status uint8 [n_loci][2][2], indexed
+ * [direction][class]; curve int64 [2][2][n_loci] or NULL, accepted only with n_cores == 1:
+ * curve[d][c][s] = P_s of the single core for s = 0 and every step whose P_s was computed (the
+ * one that fell below the cutoff included), -1 past that and for a scan with status 4 or 5.
+ * *work = scanned cores (the listed ones that are kept) x 4 x ceil(N / 64) x (kept loci - 1).
+ * max_work <= 0: only *work and c1 are written (the other outputs may be NULL); *work > max_work
+ * is refused after c1 is taken and before the scan.  Refused (return 1) before anything is
+ * launched: no genomes, ghost records, n outside 1..2048, a slot or locus out of range or listed
+ * twice, pos decreasing, a core out of range or listed twice, cut_num < 0, cut_den <= 0,
+ * cut_num > cut_den, N (N - 1) (pos[last] - pos[0]) >= 2^62 (below it no area can overflow),
+ * curve with n_cores != 1, a cls value other than 0, 1 or 255.  Nothing of the handle changes.  */
+int gnx_sweeps_scan(gnx_state* h, int64_t n, const int64_t* slots, int32_t n_loci,
+                    const int32_t* loci, const int64_t* pos /*[n_loci]*/,
+                    const uint8_t* brk /*[n_loci] or NULL*/, const uint8_t* cls /*[2 n] or NULL*/,
+                    int32_t n_cores, const int32_t* cores /*[n_cores] or NULL*/, int32_t min_minor,
+                    int32_t cut_num, int32_t cut_den, int64_t max_gap, int64_t max_extent,
+                    int64_t max_work, int64_t* work, int64_t* c1 /*[n_loci]*/,
+                    int64_t* area /*[n_loci][2][2]*/, int32_t* steps /*[n_loci][2][2]*/,
+                    uint8_t* status /*[n_loci][2][2]*/, int64_t* curve /*[2][2][n_loci] or NULL*/);
+/* of the last gnx_sweeps_scan: its kernels' HIP-event time (ms), their number (the transpose's
+ * two, then one per batch of cores) and the completed steps summed over its scans; each may be
+ * NULL                                                                                         */
+int gnx_sweeps_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* steps_total);
+
 /* ---- model-based ancestry (csrc/gnx_admix.hip; the reference has no such analysis) -------------
  * One EM sweep of the admixture model of STRUCTURE / ADMIXTURE: individual i draws each of its
  * two alleles at locus l from ancestral population k with probability q_ik, and that allele is 1
