@@ -465,7 +465,8 @@ class Device:
         self._chk(self.lib.gnx_reset_totals(self.h))
 
     PATH_COUNTS = ('lazy_mortalities', 'xo_launch_p2', 'xo_flush', 'jobs_lanes_256',
-                   'jobs_lanes_512', 'sort_hist_gather', 'gc_with_pending_xo', 'make_dense')
+                   'jobs_lanes_512', 'sort_hist_gather', 'gc_with_pending_xo', 'make_dense',
+                   'moves_ahead')
 
     def path_counts(self):
         """dict of how often the host-driven steps took each path since the handle was made or

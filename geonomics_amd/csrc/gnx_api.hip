@@ -395,6 +395,7 @@ extern "C" int gnx_create(const gnx_config* cfg, gnx_state** out) {
   GNXCHK(dalloc(&h->fill_cnt, 4));
   HIPCHK(hipEventCreateWithFlags(&h->ev_fill, gnx_order_event_flags()));
   HIPCHK(hipEventCreateWithFlags(&h->ev_alive, gnx_order_event_flags()));
+  HIPCHK(hipEventCreateWithFlags(&h->ev_moved, gnx_order_event_flags()));
   HIPCHK(hipEventCreateWithFlags(&h->ev_perm_rest, gnx_order_event_flags()));
   {
     // (zero between sorts: k_permute wipes what a sort dirtied; + 16: the wipe is in uint4s)
@@ -563,6 +564,7 @@ extern "C" void gnx_destroy(gnx_state* h) {
   if (h->ev_compact) (void)hipEventDestroy(h->ev_compact);
   if (h->ev_fill) (void)hipEventDestroy(h->ev_fill);
   if (h->ev_alive) (void)hipEventDestroy(h->ev_alive);
+  if (h->ev_moved) (void)hipEventDestroy(h->ev_moved);
   if (h->ev_perm_rest) (void)hipEventDestroy(h->ev_perm_rest);
   if (h->ev_pairs) (void)hipEventDestroy(h->ev_pairs);
   if (h->ev_latP) (void)hipEventDestroy(h->ev_latP);
@@ -1176,7 +1178,10 @@ extern "C" int gnx_step_begin(gnx_state* h, int32_t burn) {
   h->last_xo_births = 0;
   h->step_burn = burn != 0;
   h->tile2_mode = false;        // (a handle that stepped through the tile protocol before)
-  if (h->sp.move) {
+  if (h->moved_ahead) {
+    // the last step's mortality launched this movement beside its job builder (gnx_l_move_ahead)
+    GNXCHK(gnx_move_ahead_join(h));
+  } else if (h->sp.move) {
     h->move_writes_keys = h->sp.mating_radius >= 0;     // the cell sort follows at once
     int rc = gnx_l_move(h, true, nullptr, nullptr, nullptr, nullptr, true);
     h->move_writes_keys = false;

@@ -524,8 +524,12 @@ extern "C" int gnx_walk_many(gnx_state** hs, int32_t n, int64_t T, int32_t burn,
         // (every step but the walk's last leaves its dead in place for the next one's cell sort:
         // nobody looks at the population in between - gnx_l_mortality_enqueue: lazy)
         hs[k]->eager_move = left[k] > 1;
+        // (... and one handle walked alone is certain to start its next step - several stop
+        // together when any of them fails - so that step's movement may be launched by this
+        // one's mortality: gnx_l_move_ahead)
+        hs[k]->move_ahead_ok = n == 1 && left[k] > 1;
         rc = gnx_step(hs[k], burn, with_selection);
-        hs[k]->eager_move = false;
+        hs[k]->eager_move = hs[k]->move_ahead_ok = false;
         if (!rc) {                  // (a step that failed half-way is no step of the history)
           hs[k]->dd_hist.push_back(n0);
           hs[k]->dd_hist.push_back(hs[k]->last_births);

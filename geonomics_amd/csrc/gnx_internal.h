@@ -277,6 +277,7 @@ enum {
   GNX_PC_SORT_GATHER,        // cell sorts whose first pass gathered through the index (k_move's counts)
   GNX_PC_GC_PENDING_XO,      // collections while a crossover was built and not yet joined
   GNX_PC_MAKE_DENSE,         // uncompacted populations gathered back by gnx_l_make_dense
+  GNX_PC_MOVE_AHEAD,         // next steps' movements launched beside the job builder (gnx_l_move_ahead)
   GNX_PC_COUNT
 };
 
@@ -651,6 +652,13 @@ struct gnx_state {
   bool tile_lazy_ok = false;     // set by gnx_tile_walk for every step but its last
   int64_t holes_flagged = 0;
   bool eager_move = false;       // set by gnx_walk for every step but the last
+  // ... and when the walk drives this handle alone, so that the next step is certain to be
+  // started: the lazy mortality launches that step's movement itself, on stream2 behind the
+  // death draws and beside the job builder (gnx_l_move_ahead).  moved_ahead: it is in flight or
+  // done, gnx_step_begin waits for ev_moved instead of moving.
+  bool move_ahead_ok = false;
+  bool moved_ahead = false;
+  hipEvent_t ev_moved = nullptr;
   bool move_writes_keys = false;     // set around the movement of gnx_step           // k_move has written this step's sort keys
   int n_bin_blocks = 0;
   double* nodes = nullptr;           // [Jy][Jx] scratch node values
@@ -758,6 +766,12 @@ int gnx_l_gather_e(gnx_state* h, int64_t first, int64_t n);
 int gnx_l_age(gnx_state* h);
 int gnx_l_move(gnx_state* h, bool inc_age, const float* inj_theta, const float* inj_dist,
                float* out_theta, float* out_dist, bool apply);
+// the movement gnx_step_begin of the NEXT step would launch (age increment, the cell sort's keys
+// and digit counts, step + 1) over the N slots the death draws have just flagged, on stream2
+// behind ev_alive; sets holes / holes_N / moved_ahead and records ev_moved
+int gnx_l_move_ahead(gnx_state* h, int64_t N);
+// ... waited for by the main stream (no-op when no movement ran ahead)
+int gnx_move_ahead_join(gnx_state* h);
 int gnx_l_sort_by_cell(gnx_state* h, bool split_rest = false);
 int gnx_wait_permute_rest(gnx_state* h);
 int gnx_permute_rest_launch(gnx_state* h);

@@ -1903,8 +1903,9 @@ int gnx_l_mortality_enqueue(gnx_state* h, const uint8_t* d_dead_inject) {
   // counts it needs itself (k_xo_jobs_lanes: cnt3), the lists and the host get theirs from
   // stream3, and this stream goes from the death draws straight to the job builder
   const bool side_scan = fill && xo && xo_B > 0 && jobs_fused_ok(h);
-  // lazy: gnx_walk, every step but the last - NO compaction (gnx_internal.h: holes).  (The next
-  // step's movement beside the job builder instead: measured and removed, profiles/r05_ab_runs.txt)
+  // lazy: gnx_walk, every step but the last - NO compaction (gnx_internal.h: holes).
+  // move_ahead: ... and the next step's movement beside the job builder (gnx_l_move_ahead), when
+  // the walk drives this handle alone
   // lazy_tile: the same inside gnx_tile_walk, without an index, when GNX_TILE_LAZY=1 asks for it
   // (read per call: the tests switch it; 1.64 ms/step with, 1.59-1.64 without, profiles/r06_ab_runs.txt)
   const bool lazy_common = fill && h->sp.move && h->sp.mating_radius >= 0;
@@ -1912,8 +1913,14 @@ int gnx_l_mortality_enqueue(gnx_state* h, const uint8_t* d_dead_inject) {
                          h->tile2_mode && h->tile_R * h->tile_C > 1 && !ord_keep;
   const bool lazy = lazy_tile || (lazy_common && h->eager_move && ord_keep && h->key_bits <= 24 &&
                                   h->n_ghost == 0 && !h->tile2_mode);
+  // (only with the late crossover launch: launched at once - small capacities, overlap mode 1 -
+  // this step's crossover is on stream2 before the movement could be, or would wait behind it)
+  const bool move_ahead = lazy && ord_keep && h->move_ahead_ok && h->stream2 != nullptr &&
+                          h->xo_launch_late;
+  // lazy_ord: a lazy mortality's index compaction reads the flags and the old index, not newslot
+  const bool lazy_ord = lazy && ord_keep;
+  if (side_scan || lazy_ord) HIPCHK(hipEventRecord(h->ev_alive, h->stream));
   if (side_scan) {
-    HIPCHK(hipEventRecord(h->ev_alive, h->stream));
     HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_alive, 0));
     GNXCHK(gnx_block_scan(h, 3, N, h->blk_cnt, h->blk_off, h->cnt_dev, h->h_pin_dev, 0, h->stream3));
     gnx_time_end(h, GNX_K_COMPACT, 0.0);
@@ -1946,9 +1953,37 @@ int gnx_l_mortality_enqueue(gnx_state* h, const uint8_t* d_dead_inject) {
     h->jobs_self_scan = false;
     if (h->xo_sort_waits && h->xo_wait_at == 2) GNXCHK(gnx_xo_wait_inflight(h));
   }
+  // the next step's movement, enqueued behind the job builder's launch: the builder needs all its
+  // workgroups resident in one round and gets the chip first.  (Enqueued before it:
+  // 0.489 against 0.482 ms/step young, 0.5225 against 0.5248 steady - profiles/move_ahead_ab_runs.txt)
+  if (move_ahead) GNXCHK(gnx_l_move_ahead(h, N));
   // the index's compaction of the PREVIOUS mortality round (stream3) still reads newslot when
   // no cell sort has waited for it in between (gnx_op_mortality right after a step)
   if (ord_keep && h->ord_inflight) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_ord, 0));
+  auto ord_launch = [&](hipStream_t os) {
+    GnxScanOut So{h->ord_off, nullptr, nullptr, 0, nullptr, h->tickets + 2, h->blk_stride};
+    // (one launch with a decoupled look-back instead of these two: measured and removed, 0.526
+    // against 0.519 ms/step beside the crossover - profiles/r06_ab_runs.txt)
+    hipLaunchKernelGGL(k_ord_flags, dim3(nb), dim3(256), 0, os, N, h->ord_n,
+                       h->ord[h->ord_cur], h->newslot, h->ord_cnt, So, (const GnxDD*)nullptr,
+                       lazy ? (const int32_t*)h->flag : (const int32_t*)nullptr);
+    hipLaunchKernelGGL(k_ord_write, dim3(nb), dim3(256), 0, os, N, h->ord_n,
+                       h->ord[h->ord_cur], h->newslot, h->ord_off, h->ord[h->ord_cur ^ 1],
+                       (const GnxDD*)nullptr, GnxDDEnd{}, 0,
+                       lazy ? (const int32_t*)h->flag : (const int32_t*)nullptr);
+  };
+  // lazy: nobody moves, so the index's compaction reads the flags and the old index only, not
+  // newslot - it needs neither the dead's rows nor the scan.  With the movement ahead it follows
+  // the job builder on this stream: the cell sort then waits for the movement alone.  (On stream3
+  // behind the scan, which takes 80 - 90 us beside the movement: 0.496 / 0.534 ms/step young /
+  // steady against 0.476 / 0.521 with the index here, same session, the parent at 0.504 / 0.545 -
+  // profiles/move_ahead_ab_runs.txt, session 2, variants a and c)
+  if (move_ahead) {
+    ord_launch(h->stream);
+    h->ord_inflight = false;
+    h->ord_covers_xo = false;
+    h->ord_cur ^= 1;
+  }
   gnx_time_begin(h);
   const double rec_bytes = 34.0 + 4.0 * c.n_layers + 4.0 * c.n_traits + 16.0 * h->TW;
   if (lazy) {
@@ -1984,20 +2019,21 @@ int gnx_l_mortality_enqueue(gnx_state* h, const uint8_t* d_dead_inject) {
                        ord_keep ? h->newslot : nullptr);
     gnx_time_end(h, GNX_K_COMPACT, (double)N * (24.0 + 2.0 * rec_bytes));
   }
-  if (ord_keep) {
-    HIPCHK(hipEventRecord(h->ev_compact, h->stream));
-    HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_compact, 0));
+  if (move_ahead) {
+    // (the index has followed the job builder on this stream)
+  } else if (ord_keep) {
+    if (!lazy_ord) {
+      HIPCHK(hipEventRecord(h->ev_compact, h->stream));
+      HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_compact, 0));
+    } else if (!side_scan) {
+      // lazy without a movement ahead (several handles, the crossover launched at once): stream3
+      // runs the index behind the death draws, not behind the dead's rows (with side_scan it has
+      // waited for them already, for its scan) - host-driven walk of 10^5 individuals in 2 x 10^5
+      // slots: 0.199 against 0.213 ms/step behind ev_compact, profiles/move_ahead_ab_runs.txt
+      HIPCHK(hipStreamWaitEvent(h->stream3, h->ev_alive, 0));
+    }
     if (h->ord_inflight) h->ord_inflight = false;       // (stream3 runs them in order)
-    GnxScanOut So{h->ord_off, nullptr, nullptr, 0, nullptr, h->tickets + 2, h->blk_stride};
-    // (one launch with a decoupled look-back instead of these two: measured and removed, 0.526
-    // against 0.519 ms/step beside the crossover - profiles/r06_ab_runs.txt)
-    hipLaunchKernelGGL(k_ord_flags, dim3(nb), dim3(256), 0, h->stream3, N, h->ord_n,
-                       h->ord[h->ord_cur], h->newslot, h->ord_cnt, So, (const GnxDD*)nullptr,
-                       lazy ? (const int32_t*)h->flag : (const int32_t*)nullptr);
-    hipLaunchKernelGGL(k_ord_write, dim3(nb), dim3(256), 0, h->stream3, N, h->ord_n,
-                       h->ord[h->ord_cur], h->newslot, h->ord_off, h->ord[h->ord_cur ^ 1],
-                       (const GnxDD*)nullptr, GnxDDEnd{}, 0,
-                       lazy ? (const int32_t*)h->flag : (const int32_t*)nullptr);
+    ord_launch(h->stream3);
     // the cell sort waits for the crossover AND for this: stream3 waits for the crossover here,
     // where nothing waits for stream3, and the sort's stream waits for one event instead of two
     h->ord_covers_xo = false;
@@ -2048,7 +2084,16 @@ int gnx_l_mortality_finish(gnx_state* h, int64_t* deaths_out) {
   h->fill_guess = N - survivors;
   h->N = survivors;
   h->n_ghost = 0;
-  if (survivors == 0) h->holes = false;        // (nobody left to move or sort)
+  if (survivors == 0) {                        // (nobody left to move or sort)
+    h->holes = false;
+    if (h->moved_ahead) {
+      // the movement launched ahead found every slot flagged dead and wrote nothing: no step
+      // will sort its keys
+      GNXCHK(gnx_move_ahead_join(h));
+      GNXCHK(gnx_os_hist_discard(h));
+      h->keys_fresh = false;
+    }
+  }
   if (!fill) h->cur ^= 1;
   if (ord_keep) h->ord_n = survivors;
   return 0;

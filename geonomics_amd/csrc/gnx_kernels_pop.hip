@@ -468,6 +468,10 @@ int gnx_l_move(gnx_state* h, bool inc_age, const float* inj_theta, const float* 
   // device-driven step (gnx_dd.hip): the grid covers the capacity, the kernel reads N itself
   const bool ddm = h->dd_active;
   if (!ddm && h->N == 0) return 0;
+  if (h->moved_ahead) {
+    gnx_set_error("internal: a movement while the next step's own is already in flight");
+    return 1;
+  }
   if (apply) {                            // bins counted before a movement are stale
     h->fb_adults = false;
     h->fb_pending = false;
@@ -551,6 +555,38 @@ int gnx_l_move(gnx_state* h, bool inc_age, const float* inj_theta, const float* 
   gnx_time_end(h, GNX_K_MOVE,
                (double)h->N * (32.0 + 8.0 * c.n_layers + (sp.move_surf ? 36.0 : 0.0)));
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// gnx_walk, one handle, not the walk's last step: the next step's movement needs nothing of this
+// step but the death draws' flags - not the survivor count, not the job builder's tables, not the
+// index - so the lazy mortality launches it on stream2, where it shares the chip with the job
+// builder (a chain of dependent round trips that leaves most issue slots idle) instead of
+// following it.  Exactly what gnx_step_begin would launch: same arguments, step + 1.
+int gnx_l_move_ahead(gnx_state* h, int64_t N) {
+  HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_alive, 0));
+  h->holes = true;
+  h->holes_N = N;
+  h->holes_flagged = N;
+  hipStream_t main = h->stream;
+  h->stream = h->stream2;                        // the timer events go where the kernel goes
+  h->step += 1;
+  h->move_writes_keys = true;                    // (lazy: mating_radius >= 0, the cell sort follows)
+  const int rc = gnx_l_move(h, true, nullptr, nullptr, nullptr, nullptr, true);
+  h->move_writes_keys = false;
+  h->step -= 1;
+  h->stream = main;
+  GNXCHK(rc);
+  HIPCHK(hipEventRecord(h->ev_moved, h->stream2));
+  h->moved_ahead = true;
+  ++h->pc[GNX_PC_MOVE_AHEAD];
+  return 0;
+}
+
+int gnx_move_ahead_join(gnx_state* h) {
+  if (!h->moved_ahead) return 0;
+  h->moved_ahead = false;
+  HIPCHK(hipStreamWaitEvent(h->stream, h->ev_moved, 0));
   return 0;
 }
 
@@ -787,6 +823,11 @@ int gnx_l_make_dense(gnx_state* h) {
   gnx_bins_adults_drop(h);
   GNXCHK(gnx_wait_permute_rest(h));
   GNXCHK(gnx_xo_flush_deferred(h));
+  // (a movement launched ahead for a step that was never started - an error between the two
+  // steps of a one-handle walk - has written positions and ages and stays applied: the handle is
+  // half a step ahead of its history, the next step moves again with the same step key.  It ends
+  // before the living are gathered, its keys are dropped.)
+  GNXCHK(gnx_move_ahead_join(h));
   GNXCHK(gnx_os_hist_discard(h));
   h->keys_fresh = false;
   if (h->ord_inflight) {        // the index's own compaction (stream3) has finished
@@ -815,7 +856,7 @@ int gnx_l_sort_by_cell(gnx_state* h, bool split_rest) {
   GNXCHK(gnx_wait_permute_rest(h));
   if (N == 0) {
     h->holes = false;                 // (nobody left: nothing to gather)
-    return 0;
+    return gnx_move_ahead_join(h);
   }
   GNXCHK(gnx_xo_flush_deferred(h));   // slots move: offspring still waiting for their crossover get it now
   // the radix sort runs alone, or beside a narrow tail.  (The index's compaction on stream3

@@ -243,7 +243,9 @@ int gnx_reset_totals(gnx_state* h);
  * a genome access); job-builder launches of the 256-thread and of the 512-thread
  * instantiation; cell sorts whose first pass gathered through the id-ordered index with the
  * digit counts of the movement; block collections that ran while a crossover was built but
- * not yet joined; uncompacted populations gathered back after a walk that was cut short.
+ * not yet joined; uncompacted populations gathered back after a walk that was cut short;
+ * movements of the next step launched beside the job builder (gnx_walk of one handle, every
+ * step but the last).
  * Returns how many counters there are.  Host-side integers only: no device access, no
  * effect on any result (gnx_totals is separate).  Steps of the device-driven walk are
  * captured once into a graph and replayed: they are not counted.                         */
