@@ -73,6 +73,7 @@ EXPORTS = [
     'gnx_cost_surfaces', 'gnx_cost_matrix', 'gnx_cost_budget', 'gnx_cost_info',
     'gnx_admix_sweep', 'gnx_admix_info',
     'gnx_sweeps_scan', 'gnx_sweeps_info',
+    'gnx_divmap_sums', 'gnx_divmap_info',
 ]
 
 
@@ -978,6 +979,41 @@ class Device:
             _ptr(gs if gs.size else np.zeros(1, np.int64), C.c_int64), _ptr(c1, C.c_int32),
             _ptr(ch, C.c_int32)))
         return c1, ch
+
+    # -- moving-window diversity sums (csrc/gnx_divmap.hip; sim/divmap.py) -----------------
+    def divmap_sums(self, slots, cell_start, nx, ny, r, locus_mask=None, max_counts=0):
+        """the four integers per window of an nx x ny map (gnx_divmap_sums): slots grouped by
+        map cell iy * nx + ix, cell_start [nx * ny + 1], windows of Chebyshev radius r
+        -> dict n, S (int32), sum_het, sum_cc (int64), each [ny][nx]"""
+        s = _arr(slots, np.int64).ravel()
+        if s.size and (s.min() < -2 ** 31 or s.max() >= 2 ** 31):
+            raise GnxError('gnx_divmap_sums: slot out of range')
+        s = s.astype(np.int32)
+        cs = _arr(cell_start, np.int64).ravel()
+        nx, ny, r = int(nx), int(ny), int(r)
+        if not -2 ** 31 <= min(nx, ny, r) <= max(nx, ny, r) < 2 ** 31:
+            raise ValueError('nx, ny, r: 32-bit integers')
+        cells = nx * ny if nx >= 1 and ny >= 1 and nx * ny <= 2 ** 20 else 0
+        if cells and cs.size != cells + 1:
+            raise ValueError('cell_start: %d entries, not nx * ny + 1 = %d' % (cs.size, cells + 1))
+        m = self._locus_mask_words(locus_mask)
+        # (the library refuses a map outside 1..2^20 cells before it writes: no raster for that)
+        shape = (ny, nx) if cells else (0, 0)
+        out = dict(n=np.zeros(shape, np.int32), S=np.zeros(shape, np.int32),
+                   sum_het=np.zeros(shape, np.int64), sum_cc=np.zeros(shape, np.int64))
+        self._chk(self.lib.gnx_divmap_sums(
+            self.h, C.c_int64(int(s.size)), _ptr(s, C.c_int32), C.c_int32(nx), C.c_int32(ny),
+            _ptr(cs if cs.size else np.zeros(1, np.int64), C.c_int64), C.c_int32(r),
+            _ptr(m, C.c_uint64), C.c_int64(int(max_counts)), _ptr(out['n'], C.c_int32),
+            _ptr(out['S'], C.c_int32), _ptr(out['sum_het'], C.c_int64),
+            _ptr(out['sum_cc'], C.c_int64)))
+        return out
+
+    def divmap_info(self):
+        """locus tiles, chunks and kernel launches of the last divmap_sums"""
+        t, c, n = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.gnx_divmap_info(self.h, C.byref(t), C.byref(c), C.byref(n)))
+        return dict(tiles=int(t.value), chunks=int(c.value), launches=int(n.value))
 
     def stats_ld(self, loci):
         loci = _arr(loci, np.int32)

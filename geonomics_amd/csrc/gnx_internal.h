@@ -383,6 +383,10 @@ struct gnx_state {
   int64_t admix_launches = 0, admix_chunks = 0;
   int32_t admix_instance = 0;
 
+  // moving-window diversity sums (gnx_divmap.hip): the locus tiles, the chunks of map cells
+  // and the kernel launches of the last call
+  int64_t dm_tiles = 0, dm_chunks = 0, dm_launches = 0;
+
   // traits etc
   GnxTrait traits[GNX_MAX_TRAITS];
   // selected loci: all trait loci concatenated trait-major (n_tl of them), then the

@@ -1139,6 +1139,16 @@ class Model:
         spp = self.comm[self._get_spp_num(spp)]
         return spp._calc_sfs(groups=groups, loci=loci, folded=folded)
 
+    def calc_diversity_map(self, spp=0, grid=None, win=3, min_n=2, loci=None, individs=None):
+        """moving-window diversity rasters (sim/divmap.py): the landscape cut into grid =
+        (nx, ny) map cells (default: (min(dim_x, 64), min(dim_y, 64))), a window of win x win
+        map cells (win odd) around each, clipped at the edges -> dict with 'n' and 'S' (int
+        rasters [ny][nx]), 'pi', 'theta_w', 'tajima_d', 'Ho', 'He', 'Fis' (float64 rasters, NaN
+        where a window holds fewer than min_n individuals), 'grid', 'win', 'n_loci'"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_diversity_map(grid=grid, win=win, min_n=min_n, loci=loci,
+                                       individs=individs)
+
     def group_by_layer(self, lyr, edges, spp=0):
         """labels of the living in id order: np.digitize(e on Layer lyr, edges) - 1, -1 outside"""
         spp = self.comm[self._get_spp_num(spp)]

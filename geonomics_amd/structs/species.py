@@ -1016,6 +1016,44 @@ class Species:
         iy = np.clip((xy[:, 1] * (int(ny) / dim[1])).astype(np.int64), 0, int(ny) - 1)
         return iy * int(nx) + ix
 
+    # -- moving-window diversity rasters (sim/divmap.py; csrc/gnx_divmap.hip) ----------------
+    def _calc_diversity_map(self, grid=None, win=3, min_n=2, loci=None, individs=None):
+        """rasters of n, S, pi, theta_w, tajima_d, Ho, He and Fis over overlapping windows of
+        win x win map cells (sim/divmap.py holds the definition): grid (nx, ny) cuts the
+        landscape as _group_by_grid does (None: (min(dim_x, 64), min(dim_y, 64))), win is odd,
+        windows of fewer than min_n individuals are NaN; loci and individs restrict what is
+        counted.  The four integers per window are taken on the device (gnx_divmap_sums)
+        -> dict of [ny][nx] rasters, and 'grid', 'win', 'n_loci'"""
+        from ..sim import divmap as _divmap
+        if self.gen_arch is None or self._dev.L == 0:
+            raise ValueError('the Species has no genomes (no gen_arch)')
+        if int(win) != win or int(win) < 1 or int(win) % 2 == 0:
+            raise ValueError('win: an odd number of map cells, at least 1 (got %r)' % (win,))
+        if int(min_n) != min_n or int(min_n) < 1:
+            raise ValueError('min_n: at least 1 (got %r)' % (min_n,))
+        dim = self._land_ref.dim
+        if grid is None:
+            grid = (min(int(dim[0]), 64), min(int(dim[1]), 64))
+        if len(grid) != 2 or int(grid[0]) < 1 or int(grid[1]) < 1:
+            raise ValueError('grid: (nx, ny), each at least 1 (got %r)' % (grid,))
+        nx, ny = int(grid[0]), int(grid[1])
+        lab = self._group_by_grid(nx, ny)                 # the living in id order
+        ids, slots = self._geno_sample(individs)
+        if individs is not None:
+            all_ids, _ = self._geno_sample(None)
+            lab = lab[np.searchsorted(all_ids, ids)]
+        loci, mask = self._geno_loci(loci)
+        order = np.argsort(lab, kind='stable')
+        cell_start = np.concatenate([[0], np.cumsum(np.bincount(lab, minlength=nx * ny))])
+        got = self._dev.divmap_sums(slots[order], cell_start.astype(np.int64), nx, ny,
+                                    (int(win) - 1) // 2, locus_mask=mask)
+        n_loci = int(self._dev.L if loci is None else loci.size)
+        out = {'n': got['n'], 'S': got['S']}
+        out.update(_divmap.window_stats(got['n'], got['S'], got['sum_het'], got['sum_cc'],
+                                        n_loci, min_n=int(min_n)))
+        out.update(grid=(nx, ny), win=int(win), n_loci=n_loci)
+        return out
+
     def _calc_genetic_PCA(self, n_pcs=3, individs=None, loci=None, method='auto', n_iter=8,
                           oversample=10, seed=0):
         """PCA of the mean genotypes of the living individuals asked for (reference

@@ -143,6 +143,12 @@ class TiledSpecies(Species):
         raise NotImplementedError('group counts (Fst, diversity, SFS) of a Species tiled over '
                                   'several GPUs are not implemented; run the model on one GPU')
 
+    # -- moving-window diversity rasters: not over tiles (a window reaches over a tile's edge:
+    # the four integers add over tiles, one all-reduce of O(map))
+    def _calc_diversity_map(self, *args, **kw):
+        raise NotImplementedError('calc_diversity_map with a Species tiled over several GPUs is '
+                                  'not implemented; run the model on one GPU')
+
     # -- introductions: not over tiles (the newcomers would have to be routed to their tiles)
     def _add_individuals(self, *args, **kw):
         raise NotImplementedError('add_individuals with a Species tiled over several GPUs is '

@@ -634,6 +634,30 @@ int gnx_stats_locus_counts(gnx_state* h, int32_t* cnt1 /*[L]*/, int32_t* cnt_het
 int gnx_stats_group_counts(gnx_state* h, int64_t n, const int32_t* slots /*[n], grouped*/,
                            int32_t G, const int64_t* group_start /*[G + 1]*/,
                            int32_t* cnt1 /*[G][L]*/, int32_t* cnt_het /*[G][L]*/);
+/* moving-window diversity sums over a map grid (csrc/gnx_divmap.hip; geonomics_amd/sim/divmap.py
+ * holds the definition and the host arithmetic): the landscape cut into nx x ny map cells
+ * (cell iy * nx + ix), slots[cell_start[c] .. cell_start[c + 1]) the slots of the individuals
+ * in map cell c, as gnx_stats_group_counts takes its groups.  The window of map cell (iy, ix)
+ * is every map cell within Chebyshev distance r, clipped at the map's edge.  Per window, over
+ * the loci of locus_mask (u64 [W64], NULL: all L; L' of them), rasters [ny][nx] on the HOST:
+ *   out_n    individuals n                          out_S    loci with 0 < c_l < 2n
+ *   out_het  sum over loci of the heterozygotes h_l  out_cc   sum over loci of c_l (2n - c_l)
+ * c_l: the window's 1-alleles at locus l over both homologues.  Exact integers, independent of
+ * the schedule and of the tile size.  The genome is processed in locus tiles of whole 64-locus
+ * words, sized so that one [cell][tile loci] table holds at most max_counts int32 entries
+ * (<= 0: 2^26), at least one word; four such tables are the call's scratch.
+ * Refused before anything is launched (return 1): no genomes; ghost records (a tile); nx or
+ * ny < 1; nx * ny above 2^20; r < 0; a null argument or n < 0; cell_start not starting at 0,
+ * decreasing, or not ending at n; a window of 2^30 individuals or more; L' * n_max^2 >= 2^63
+ * (out_cc is int64; n_max: the largest window); a slot outside [0, gnx_n_slots).  A pending
+ * crossover is cut first and an uncompacted population would be gathered, as there.
+ * gnx_divmap_info: the locus tiles, the chunks (runs of at most 511 individuals of one map
+ * cell) and the kernel launches of the last call.                                         */
+int gnx_divmap_sums(gnx_state* h, int64_t n, const int32_t* slots /*[n], grouped by map cell*/,
+                    int32_t nx, int32_t ny, const int64_t* cell_start /*[nx * ny + 1]*/,
+                    int32_t r, const uint64_t* locus_mask /*[W64] or NULL*/, int64_t max_counts,
+                    int32_t* out_n, int32_t* out_S, int64_t* out_het, int64_t* out_cc);
+int gnx_divmap_info(gnx_state* h, int64_t* tiles, int64_t* chunks, int64_t* launches);
 /* r^2 between the listed loci (_calc_ld); double [n][n], NaN on the diagonal */
 int gnx_stats_ld(gnx_state* h, int32_t n_loci, const int32_t* loci, double* r2);
 /* the counts behind r^2, which add over tiles: c[i] 1-alleles at locus i, cc[i][j]

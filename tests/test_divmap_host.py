@@ -1,0 +1,297 @@
+"""Moving-window diversity rasters on the host (geonomics_amd/sim/divmap.py): window_stats
+against sim/fst.diversity applied per window, box_sum against a double loop, and
+Species._calc_diversity_map over a numpy stand-in for the device.  Runs without a GPU.
+
+Bounds.  fst.diversity sums L' non-negative correctly-rounded terms per window; window_stats
+divides one exact integer once.  So pi, Ho and He agree within relative 2 L' 2^-53, and
+tajima_d = (pi - theta_w) / sd within 2 L' 2^-53 pi / sd + 2^-50 |D|."""
+import types
+
+import numpy as np
+import pytest
+
+from geonomics_amd.sim import divmap as DM
+from geonomics_amd.sim import fst as F
+from geonomics_amd.structs import species as S
+
+U53 = 2.0 ** -53
+
+
+def sums_numpy(gts, lab, nx, ny, r, loci=None):
+    """the four integer rasters [ny][nx] by brute force: gts [n][L][2], lab [n] map cells"""
+    g = gts.astype(np.int64)
+    if loci is not None:
+        g = g[:, np.asarray(loci)]
+    out = dict(n=np.zeros((ny, nx), np.int32), S=np.zeros((ny, nx), np.int32),
+               sum_het=np.zeros((ny, nx), np.int64), sum_cc=np.zeros((ny, nx), np.int64))
+    ix, iy = lab % nx, lab // nx
+    for wy in range(ny):
+        for wx in range(nx):
+            part = g[(abs(ix - wx) <= r) & (abs(iy - wy) <= r)]
+            n = part.shape[0]
+            c = part.sum(axis=(0, 2))
+            out['n'][wy, wx] = n
+            out['S'][wy, wx] = np.count_nonzero((c > 0) & (c < 2 * n))
+            out['sum_het'][wy, wx] = (part.sum(axis=2) == 1).sum()
+            out['sum_cc'][wy, wx] = (c * (2 * n - c)).sum()
+    return out
+
+
+def _gts(rng, n, L):
+    """frequencies spread over (0, 1), and loci fixed at 0 and at 1"""
+    p = rng.uniform(0, 1, L)
+    p[::17] = 0.0
+    p[5::29] = 1.0
+    return (rng.rand(n, L, 2) < p[None, :, None]).astype(np.uint8)
+
+
+@pytest.mark.parametrize('L', [200, 4097])
+def test_window_stats_against_fst_diversity(L):
+    rng = np.random.RandomState(L)
+    sizes = [1, 2, 3, 17, 541]
+    n = np.array(sizes)
+    cnt1 = np.zeros((len(sizes), L), np.int64)
+    cnt_het = np.zeros((len(sizes), L), np.int64)
+    for g, k in enumerate(sizes):
+        gts = _gts(rng, k, L).astype(np.int64)
+        cnt1[g] = gts.sum(axis=(0, 2))
+        cnt_het[g] = (gts.sum(axis=2) == 1).sum(axis=0)
+    want = F.diversity(cnt1, cnt_het, n)
+    m = 2 * n[:, None]
+    S_ = np.count_nonzero((cnt1 > 0) & (cnt1 < m), axis=1)
+    got = DM.window_stats(n, S_, cnt_het.sum(axis=1), (cnt1 * (m - cnt1)).sum(axis=1), L, min_n=1)
+    np.testing.assert_array_equal(S_, want['S'])
+    rel = 2 * L * U53
+    worst = 0.0
+    for k in ('pi', 'Ho', 'He'):
+        assert np.isfinite(want[k]).all()
+        err = np.abs(got[k] - want[k])
+        assert (err <= rel * np.abs(want[k])).all(), k
+        worst = max(worst, float((err / (rel * np.abs(want[k]))).max()))
+    np.testing.assert_array_equal(np.isnan(got['tajima_d']), np.isnan(want['tajima_d']))
+    assert np.isnan(want['tajima_d'][0]) and np.isfinite(want['tajima_d'][1:]).all()   # 2n < 4
+    for g in range(1, len(sizes)):
+        a1, a2, e1, e2 = F.tajima_constants(2 * sizes[g])
+        s = float(S_[g])
+        bound = rel * want['pi'][g] / np.sqrt(e1 * s + e2 * s * (s - 1)) \
+            + 2.0 ** -50 * abs(want['tajima_d'][g])
+        err = abs(got['tajima_d'][g] - want['tajima_d'][g])
+        assert err <= bound, (g, err, bound)
+        worst = max(worst, err / bound)
+    for k in ('theta_w', 'Fis'):
+        np.testing.assert_allclose(got[k], want[k], rtol=4 * rel, atol=4 * rel)
+    print('window_stats against fst.diversity, L = %d: worst error / bound %.3g' % (L, worst))
+
+
+def test_window_stats_nan_patterns_and_min_n():
+    n = np.array([[0, 1, 2], [3, 5, 5]])
+    S_ = np.array([[0, 3, 0], [4, 2, 0]])
+    het = np.array([[0, 3, 0], [5, 4, 0]])
+    cc = np.array([[0, 3, 0], [20, 18, 0]])
+    out = DM.window_stats(n, S_, het, cc, 10)
+    for k in DM.FLOAT_KEYS:
+        assert out[k].shape == n.shape and out[k].dtype == np.float64
+        assert np.isnan(out[k][0, :2]).all(), k                   # n < min_n = 2
+    assert out['pi'][0, 2] == 0.0 and np.isnan(out['tajima_d'][0, 2])   # S = 0
+    assert np.isnan(out['Fis'][0, 2]) and out['Ho'][0, 2] == 0.0        # He = 0
+    assert np.isfinite(out['tajima_d'][1, :2]).all() and np.isnan(out['tajima_d'][1, 2])
+    assert out['pi'][1, 0] == 20 / 15 and out['He'][1, 0] == 20 / 15 / 10
+    assert out['Ho'][1, 0] == 5 / 30 and out['theta_w'][1, 0] == 4 / F.tajima_constants(6)[0]
+    one = DM.window_stats(n, S_, het, cc, 10, min_n=1)
+    assert np.isnan(one['pi'][0, 0]) and one['pi'][0, 1] == 3.0        # n = 0 stays NaN
+    assert np.isnan(one['tajima_d'][0, 1]) and one['theta_w'][0, 1] == 3.0   # 2n < 4
+    big = DM.window_stats(n, S_, het, cc, 10, min_n=4)
+    assert np.isnan(big['pi']).sum() == 4
+    no_loci = DM.window_stats(n, S_ * 0, het * 0, cc * 0, 0)
+    assert np.isnan(no_loci['Ho']).all() and (no_loci['pi'][n >= 2] == 0).all()
+    with pytest.raises(ValueError, match='min_n'):
+        DM.window_stats(n, S_, het, cc, 10, min_n=0)
+    with pytest.raises(ValueError, match='one shape'):
+        DM.window_stats(n, S_[:1], het, cc, 10)
+
+
+def test_window_stats_takes_the_constants_once_per_distinct_n(monkeypatch):
+    calls = []
+    real = F.tajima_constants
+    monkeypatch.setattr(F, 'tajima_constants', lambda m: calls.append(m) or real(m))
+    n = np.array([[4, 4, 9], [9, 4, 0], [1, 9, 4]])
+    DM.window_stats(n, n * 0, n * 0, n * 0, 5)
+    assert sorted(calls) == [8, 18]
+
+
+@pytest.mark.parametrize('shape', [(4, 5), (1, 7), (7, 1), (1, 1), (6, 6)])
+def test_box_sum_against_a_double_loop(shape):
+    ny, nx = shape
+    a = np.random.RandomState(nx * 10 + ny).randint(0, 50, (ny, nx))
+    for r in (0, 1, 2, max(nx, ny), max(nx, ny) + 3):
+        want = np.zeros((ny, nx), np.int64)
+        for iy in range(ny):
+            for ix in range(nx):
+                want[iy, ix] = a[max(iy - r, 0):iy + r + 1, max(ix - r, 0):ix + r + 1].sum()
+        got = DM.box_sum(a, r)
+        assert got.dtype == np.int64
+        np.testing.assert_array_equal(got, want)
+        if r >= max(nx, ny):
+            assert (got == a.sum()).all()
+    with pytest.raises(ValueError, match='r >= 0'):
+        DM.box_sum(a, -1)
+    with pytest.raises(ValueError, match='2-d'):
+        DM.box_sum(a.ravel(), 1)
+
+
+# ------------------------------------------------------------------ the public calls
+class _Dev:
+    """the device's divmap_sums in numpy, on genotypes kept in slot order"""
+
+    def __init__(self, gts):
+        self.gts = gts
+        self.L = gts.shape[1]
+        self.W64 = (self.L + 1023) // 1024 * 16
+        self.calls = []
+
+    def divmap_sums(self, slots, cell_start, nx, ny, r, locus_mask=None, max_counts=0):
+        self.calls.append(dict(slots=slots, cell_start=cell_start, nx=nx, ny=ny, r=r,
+                               mask=locus_mask))
+        assert cell_start[0] == 0 and cell_start[-1] == len(slots) and len(cell_start) == nx * ny + 1
+        loci = np.arange(self.L)
+        if locus_mask is not None:
+            assert locus_mask.dtype == np.uint64 and locus_mask.size == self.W64
+            loci = loci[(locus_mask[loci >> 6] >> (loci & 63).astype(np.uint64)) & np.uint64(1) == 1]
+        lab = np.repeat(np.arange(nx * ny), np.diff(cell_start))
+        out = sums_numpy(self.gts[slots], lab, nx, ny, r, loci)
+        np.testing.assert_array_equal(
+            out['n'], DM.box_sum(np.diff(cell_start).reshape(ny, nx), r))
+        return out
+
+
+class _Species:
+    """a Species stand-in: the real _calc_diversity_map and _group_by_grid over the numpy
+    device, columns kept in slot order"""
+    _calc_diversity_map = S.Species._calc_diversity_map
+    _group_by_grid = S.Species._group_by_grid
+    _geno_loci = S.Species._geno_loci
+
+    def __init__(self, xy, gts, ids, dim):
+        self._dev = _Dev(gts)
+        self.xy, self.ids = xy, np.asarray(ids)
+        self.gen_arch = types.SimpleNamespace(traits={})
+        self._land_ref = types.SimpleNamespace(dim=dim)
+
+    def _get_coords(self):
+        return self.xy[np.argsort(self.ids)]
+
+    def _geno_sample(self, individs):
+        order = np.argsort(self.ids)
+        if individs is None:
+            return self.ids[order], order
+        ids = np.sort(np.asarray(individs))
+        return ids, order[np.searchsorted(self.ids[order], ids)]
+
+
+def _pop(n=150, L=140, dim=(20, 12), seed=3):
+    rng = np.random.RandomState(seed)
+    xy = rng.uniform(0, 1, (n, 2)) * np.array(dim)
+    west = xy[:, 0] < 0.45 * dim[0]                                 # map cells left empty
+    xy[west, 1] = np.minimum(xy[west, 1], 0.24 * dim[1])
+    xy[:3] = [[0.0, 0.0], [dim[0], dim[1]], [dim[0], 0.0]]          # on the landscape's edge
+    ids = rng.permutation(n) * 3 + 1                                # slot order != id order
+    return _Species(xy, _gts(rng, n, L), ids, dim), xy, ids
+
+
+def _labels(xy, dim, nx, ny):
+    ix = np.clip((xy[:, 0] * (nx / dim[0])).astype(np.int64), 0, nx - 1)
+    iy = np.clip((xy[:, 1] * (ny / dim[1])).astype(np.int64), 0, ny - 1)
+    return iy * nx + ix
+
+
+def _assert_result(res, want, n_loci, min_n=2):
+    np.testing.assert_array_equal(res['n'], want['n'])
+    np.testing.assert_array_equal(res['S'], want['S'])
+    st = DM.window_stats(want['n'], want['S'], want['sum_het'], want['sum_cc'], n_loci, min_n)
+    for k in DM.FLOAT_KEYS:
+        assert res[k].dtype == np.float64
+        np.testing.assert_array_equal(res[k], st[k], err_msg=k)
+        assert np.isnan(res[k][want['n'] < min_n]).all()
+    assert res['n_loci'] == n_loci
+
+
+def test_the_public_call_groups_by_map_cell_in_label_order():
+    spp, xy, ids = _pop()
+    from geonomics_amd.sim.model import Model
+    mod = types.SimpleNamespace(comm={0: spp})
+    for name in ('_get_spp_num', 'calc_diversity_map'):
+        setattr(mod, name, types.MethodType(getattr(Model, name), mod))
+    res = mod.calc_diversity_map(grid=(5, 4), win=3)
+    lab = _labels(xy, (20, 12), 5, 4)
+    want = sums_numpy(spp._dev.gts, lab, 5, 4, 1)
+    assert (want['n'] == 0).any() and res['grid'] == (5, 4) and res['win'] == 3
+    _assert_result(res, want, 140)
+    call = spp._dev.calls[-1]
+    assert (call['nx'], call['ny'], call['r']) == (5, 4, 1) and call['mask'] is None
+    # grouped by label, ascending id inside a map cell (the stable sort of the id order)
+    got_lab = lab[call['slots']]
+    assert (np.diff(got_lab) >= 0).all()
+    np.testing.assert_array_equal(np.diff(call['cell_start']), np.bincount(lab, minlength=20))
+    for c in range(20):
+        assert (np.diff(ids[call['slots'][got_lab == c]]) > 0).all()
+    # win = 1: the map cells themselves; min_n masks
+    res = mod.calc_diversity_map(grid=(5, 4), win=1, min_n=6)
+    want = sums_numpy(spp._dev.gts, lab, 5, 4, 0)
+    assert (want['n'] < 6).any() and (want['n'] >= 6).any()
+    _assert_result(res, want, 140, min_n=6)
+
+
+def test_individs_loci_and_the_default_grid():
+    spp, xy, ids = _pop()
+    keep = np.random.RandomState(5).permutation(150)[:90]
+    res = spp._calc_diversity_map(grid=(3, 2), win=3, individs=ids[keep])
+    lab = _labels(xy, (20, 12), 3, 2)
+    _assert_result(res, sums_numpy(spp._dev.gts[keep], lab[keep], 3, 2, 1), 140)
+    assert sorted(spp._dev.calls[-1]['slots'].tolist()) == sorted(keep.tolist())
+    loci = np.array([130, 3, 63, 64, 3])
+    res = spp._calc_diversity_map(grid=(3, 2), win=1, loci=loci)
+    _assert_result(res, sums_numpy(spp._dev.gts, lab, 3, 2, 0, np.unique(loci)), 4)
+    mask = spp._dev.calls[-1]['mask']
+    assert [int(w) for w in mask[:3]] == [(1 << 3) | (1 << 63), 1, 1 << 2] and not mask[3:].any()
+    # grid = None: (min(dim_x, 64), min(dim_y, 64))
+    res = spp._calc_diversity_map()
+    assert res['grid'] == (20, 12) and res['win'] == 3 and res['n'].shape == (12, 20)
+    _assert_result(res, sums_numpy(spp._dev.gts, _labels(xy, (20, 12), 20, 12), 20, 12, 1), 140)
+    wide = _Species(xy * 10, spp._dev.gts, ids, (200, 120))
+    res = wide._calc_diversity_map(win=5)
+    assert res['grid'] == (64, 64) and res['n'].shape == (64, 64)
+    np.testing.assert_array_equal(
+        res['n'], DM.box_sum(np.bincount(_labels(xy * 10, (200, 120), 64, 64),
+                                         minlength=4096).reshape(64, 64), 2))
+
+
+def test_bad_arguments_are_value_errors():
+    spp, xy, ids = _pop()
+    for kw, msg in ((dict(win=2), 'win'), (dict(win=0), 'win'), (dict(win=-3), 'win'),
+                    (dict(win=2.5), 'win'), (dict(min_n=0), 'min_n'), (dict(grid=(0, 3)), 'grid'),
+                    (dict(grid=(3, -1)), 'grid'), (dict(grid=(3,)), 'grid'),
+                    (dict(loci=[140]), 'loci')):
+        with pytest.raises(ValueError, match=msg):
+            spp._calc_diversity_map(**kw)
+    assert spp._dev.calls == []
+    spp.gen_arch = None
+    with pytest.raises(ValueError, match='no genomes'):
+        spp._calc_diversity_map()
+
+
+def test_tiled_species_refuses():
+    from geonomics_amd.structs.tiled import TiledSpecies
+    spp = TiledSpecies.__new__(TiledSpecies)
+    with pytest.raises(NotImplementedError, match='tiled over several GPUs'):
+        spp._calc_diversity_map(grid=(4, 4))
+
+
+def test_exports_and_signatures():
+    import inspect
+    from geonomics_amd import _native
+    from geonomics_amd.sim.model import Model
+    assert 'gnx_divmap_sums' in _native.EXPORTS and 'gnx_divmap_info' in _native.EXPORTS
+    assert list(inspect.signature(_native.Device.divmap_sums).parameters) == [
+        'self', 'slots', 'cell_start', 'nx', 'ny', 'r', 'locus_mask', 'max_counts']
+    assert list(inspect.signature(Model.calc_diversity_map).parameters) == [
+        'self', 'spp', 'grid', 'win', 'min_n', 'loci', 'individs']
