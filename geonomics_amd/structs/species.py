@@ -9,6 +9,11 @@ _do_pop_dynamics, _set_Nt, _set_genomes_and_tables (structs/species.py:567,
 582, 822, 554, 956) - are thin calls into the C-ABI.  Read accessors download
 on demand and return arrays ordered by ascending individual id, like the
 reference's (dict order == id order there).
+
+This module holds the simulation (construction, device upkeep, movement, population
+dynamics, the walk, mutation, introductions, snapshots), the reference's accessors and
+the pedigree's simplification.  The analysis calls (_calc_*, _run_*, the lineages) are
+inherited from SpeciesAnalyses (structs/analyses.py).
 """
 import copy
 import os
@@ -18,6 +23,7 @@ import numpy as np
 
 from .. import _native as nat
 from . import genome as _genome
+from .analyses import SpeciesAnalyses
 from ..sim import burnin as _burnin
 
 
@@ -150,55 +156,7 @@ def _check_introduction_compat(recip, source):
                 % (attr, t))
 
 
-_COST_OPTS = ('lyr', 'kind', 'barrier', 'cost', 'name')
-
-
-def _is_cost_spec(p):
-    return (isinstance(p, (tuple, list)) and len(p) == 2 and isinstance(p[0], str)
-            and p[0] == 'cost' and isinstance(p[1], dict))
-
-
-def _predictor_list(predictors):
-    """the predictors of a Mantel / MMRR request as a list: one name, or one ('cost', opts),
-    stands for itself"""
-    if isinstance(predictors, str) or _is_cost_spec(predictors):
-        return [predictors]
-    return list(predictors)
-
-
-def _split_predictors(spp, who, predictors, env_lyrs, trts):
-    """(names in the caller's order, the device columns of the column predictors in that order
-    (Species._dist_predictors), [(name, opts)] of the cost predictors in that order).  A cost
-    predictor is 'cost' (the defaults of calc_cost_distances) or ('cost', opts) with any of lyr,
-    kind, barrier, cost, name; its name is opts['name'], default 'cost'"""
-    names, col_names, costs = [], [], []
-    for p in _predictor_list(predictors):
-        if isinstance(p, str) and p == 'cost':
-            p = ('cost', {})
-        if _is_cost_spec(p):
-            opts = dict(p[1])
-            extra = sorted(set(opts) - set(_COST_OPTS))
-            if extra:
-                raise ValueError("%s: a 'cost' predictor takes %s, not %s"
-                                 % (who, ', '.join(_COST_OPTS), ', '.join(extra)))
-            name = str(opts.pop('name', 'cost'))
-            costs.append((name, opts))
-            names.append(name)
-        else:
-            col_names.append(p)
-            names.append(p)
-    cols = []
-    if col_names or not costs:
-        _, cols = spp._dist_predictors(who, col_names, env_lyrs, trts)
-    if len(set(names)) != len(names):
-        raise ValueError('%s: a predictor is listed twice' % who)
-    if len(names) > 4:
-        raise ValueError('%s: at most 4 predictors and 8 columns (layers, traits, x, y) '
-                         'together' % who)
-    return names, cols, costs
-
-
-class Species:
+class Species(SpeciesAnalyses):
     def __init__(self, name, idx, land, spp_params, genomic_architecture=None,
                  seed=0, device=0, rng=None):
         self.idx = idx
@@ -910,1151 +868,6 @@ class Species:
         if as_dict:
             return {int(i): g for i, g in zip(out_ids, gts)}
         return gts
-
-    # -- genetic PCA and distances (sim/pca.py; csrc/gnx_geno.hip) -----------------------
-    def _geno_sample(self, individs):
-        """(ids ascending, their slots) of the listed living individuals (all by default)"""
-        all_ids = self._field(nat.F_ID)
-        order = np.argsort(all_ids, kind='stable')
-        srt = all_ids[order]
-        if individs is None:
-            return srt, order.astype(np.int64)
-        ids = np.sort(np.asarray(individs, dtype=np.int64).ravel())
-        if (np.diff(ids) == 0).any():
-            raise ValueError('individs lists an individual more than once')
-        pos = np.searchsorted(srt, ids)
-        alive = pos < srt.size
-        alive[alive] = srt[pos[alive]] == ids[alive]
-        if not alive.all():
-            raise ValueError('individuals not alive: %s' % ids[~alive][:10].tolist())
-        return ids, order[pos].astype(np.int64)
-
-    def _geno_loci(self, loci):
-        """(ascending loci, uint64 [W64] bit mask of them), or (None, None) for all loci"""
-        if loci is None:
-            return None, None
-        L = self._dev.L
-        loci = np.unique(np.asarray(loci, dtype=np.int64).ravel())
-        if loci.size == 0 or loci[0] < 0 or loci[-1] >= L:
-            raise ValueError('loci: a non-empty list of loci in 0..%d' % (L - 1))
-        mask = np.zeros(self._dev.W64, np.uint64)
-        np.bitwise_or.at(mask, loci >> 6, np.uint64(1) << (loci & 63).astype(np.uint64))
-        return loci, mask
-
-    # -- Fst, diversity and the SFS of groups of individuals (sim/fst.py;
-    # csrc/gnx_group_counts.hip) --------------------------------------------------------
-    def _group_counts(self, groups, loci=None):
-        """per-group locus counts taken on the device (gnx_stats_group_counts): groups as
-        sim/fst.make_groups takes them (a dict name -> ids, or integer labels aligned with the
-        living in id order; negative: left out); loci selects columns on the host
-        -> (names, n [G], cnt1 [G][L'], cnt_het [G][L'])"""
-        from ..sim import fst as _fst
-        if self.gen_arch is None or self._dev.L == 0:
-            raise ValueError('the Species has no genomes (no gen_arch)')
-        ids, slots = self._geno_sample(None)
-        names, order, group_start = _fst.make_groups(ids, groups)
-        if len(names) > 1024:
-            raise ValueError('at most 1024 groups per call (got %d)' % len(names))
-        cnt1, cnt_het = self._dev.stats_group_counts(slots[order], group_start)
-        if loci is not None:
-            loci = np.asarray(loci, dtype=np.int64).ravel()
-            if loci.size == 0 or loci.min() < 0 or loci.max() >= self._dev.L:
-                raise ValueError('loci: a non-empty list of loci in 0..%d' % (self._dev.L - 1))
-            cnt1, cnt_het = cnt1[:, loci], cnt_het[:, loci]
-        return names, np.diff(group_start), cnt1, cnt_het
-
-    def _everybody(self, groups):
-        return np.zeros(len(self), np.int64) if groups is None else groups
-
-    def _calc_fst(self, groups, loci=None, method='HsHt', mean=True, est_Hs=False,
-                  include_zeros=False):
-        """Fst between groups of individuals from counts taken on the device.  'HsHt' (the
-        reference's island validation, tests/validation/island/island_test.py:54-115) and
-        'hudson' -> {(name_a, name_b): value}, keyed as calc_Fsts_mod keys its dict; the value
-        is the nanmean over loci as there ('hudson': the ratio of averages), or with mean=False
-        the per-locus array.  'var' -> one array over all groups, or its mean."""
-        from ..sim import fst as _fst
-        if method not in ('HsHt', 'hudson', 'var'):
-            raise ValueError("method: 'HsHt', 'hudson' or 'var', not %r" % (method,))
-        names, n, cnt1, cnt_het = self._group_counts(groups, loci)
-        return _fst.calc_fst(names, n, cnt1, cnt_het, method=method, mean=mean, est_Hs=est_Hs,
-                             include_zeros=include_zeros)
-
-    def _calc_diversity(self, groups=None, loci=None):
-        """per group (None: one group holding everybody): n, S, pi, theta_w, tajima_d, Ho, He,
-        Fis (sim/fst.diversity) -> dict of arrays [G], and 'names'"""
-        from ..sim import fst as _fst
-        names, n, cnt1, cnt_het = self._group_counts(self._everybody(groups), loci)
-        out = _fst.diversity(cnt1, cnt_het, n)
-        out['names'] = names
-        return out
-
-    def _calc_sfs(self, groups=None, loci=None, folded=False):
-        """site-frequency spectrum, one row per group (sim/fst.sfs) -> (names, sfs)"""
-        from ..sim import fst as _fst
-        names, n, cnt1, _ = self._group_counts(self._everybody(groups), loci)
-        return names, _fst.sfs(cnt1, n, folded=folded)
-
-    def _group_by_layer(self, lyr_num, edges):
-        """labels of the living in id order by their environment on a Layer:
-        np.digitize(e, edges) - 1, individuals outside the edges -1"""
-        edges = np.asarray(edges, dtype=np.float64).ravel()
-        if edges.size < 2 or (np.diff(edges) <= 0).any():
-            raise ValueError('edges: at least two ascending values')
-        lab = np.digitize(self._get_e(lyr_num=int(lyr_num)), edges) - 1
-        lab[lab >= edges.size - 1] = -1
-        return lab.astype(np.int64)
-
-    def _group_by_grid(self, nx, ny):
-        """labels of the living in id order by the rectangle of the landscape, cut into
-        nx x ny by coordinate, they stand in: label = iy * nx + ix"""
-        if int(nx) < 1 or int(ny) < 1:
-            raise ValueError('nx, ny: at least 1')
-        dim = self._land_ref.dim
-        xy = self._get_coords()
-        ix = np.clip((xy[:, 0] * (int(nx) / dim[0])).astype(np.int64), 0, int(nx) - 1)
-        iy = np.clip((xy[:, 1] * (int(ny) / dim[1])).astype(np.int64), 0, int(ny) - 1)
-        return iy * int(nx) + ix
-
-    # -- moving-window diversity rasters (sim/divmap.py; csrc/gnx_divmap.hip) ----------------
-    def _calc_diversity_map(self, grid=None, win=3, min_n=2, loci=None, individs=None):
-        """rasters of n, S, pi, theta_w, tajima_d, Ho, He and Fis over overlapping windows of
-        win x win map cells (sim/divmap.py holds the definition): grid (nx, ny) cuts the
-        landscape as _group_by_grid does (None: (min(dim_x, 64), min(dim_y, 64))), win is odd,
-        windows of fewer than min_n individuals are NaN; loci and individs restrict what is
-        counted.  The four integers per window are taken on the device (gnx_divmap_sums)
-        -> dict of [ny][nx] rasters, and 'grid', 'win', 'n_loci'"""
-        from ..sim import divmap as _divmap
-        if self.gen_arch is None or self._dev.L == 0:
-            raise ValueError('the Species has no genomes (no gen_arch)')
-        if int(win) != win or int(win) < 1 or int(win) % 2 == 0:
-            raise ValueError('win: an odd number of map cells, at least 1 (got %r)' % (win,))
-        if int(min_n) != min_n or int(min_n) < 1:
-            raise ValueError('min_n: at least 1 (got %r)' % (min_n,))
-        dim = self._land_ref.dim
-        if grid is None:
-            grid = (min(int(dim[0]), 64), min(int(dim[1]), 64))
-        if len(grid) != 2 or int(grid[0]) < 1 or int(grid[1]) < 1:
-            raise ValueError('grid: (nx, ny), each at least 1 (got %r)' % (grid,))
-        nx, ny = int(grid[0]), int(grid[1])
-        lab = self._group_by_grid(nx, ny)                 # the living in id order
-        ids, slots = self._geno_sample(individs)
-        if individs is not None:
-            all_ids, _ = self._geno_sample(None)
-            lab = lab[np.searchsorted(all_ids, ids)]
-        loci, mask = self._geno_loci(loci)
-        order = np.argsort(lab, kind='stable')
-        cell_start = np.concatenate([[0], np.cumsum(np.bincount(lab, minlength=nx * ny))])
-        got = self._dev.divmap_sums(slots[order], cell_start.astype(np.int64), nx, ny,
-                                    (int(win) - 1) // 2, locus_mask=mask)
-        n_loci = int(self._dev.L if loci is None else loci.size)
-        out = {'n': got['n'], 'S': got['S']}
-        out.update(_divmap.window_stats(got['n'], got['S'], got['sum_het'], got['sum_cc'],
-                                        n_loci, min_n=int(min_n)))
-        out.update(grid=(nx, ny), win=int(win), n_loci=n_loci)
-        return out
-
-    def _calc_genetic_PCA(self, n_pcs=3, individs=None, loci=None, method='auto', n_iter=8,
-                          oversample=10, seed=0):
-        """PCA of the mean genotypes of the living individuals asked for (reference
-        Model.plot_genetic_PCA, sim/model.py:2031-2041: sklearn PCA of the speciome, ids
-        ascending), on the device.  method 'exact': the Gram matrix (gnx_geno_gram, up to
-        8192 individuals) and eigh in fp64; 'randomized': subspace iteration over
-        gnx_geno_matmul / gnx_geno_rmatmul (the whole population); 'auto': exact for
-        n <= 8192.  -> (ids, scores [n][n_pcs], explained_variance_ratio [n_pcs])"""
-        from ..sim import pca as _pca
-        if method not in ('auto', 'exact', 'randomized'):
-            raise ValueError("method: 'auto', 'exact' or 'randomized', not %r" % (method,))
-        ids, slots = self._geno_sample(individs)
-        if self._dev.L == 0:
-            self._dev.geno_gram(slots[:1])            # the library's error: no genomes
-        loci, mask = self._geno_loci(loci)
-        n = ids.size
-        n_pcs = _pca.check_n_pcs(n_pcs, n, self._dev.L if loci is None else loci.size,
-                                 oversample)
-        if method == 'auto':
-            method = 'exact' if n <= 8192 else 'randomized'
-        if method == 'randomized':
-            if n != len(self):
-                raise NotImplementedError(
-                    'randomized genetic PCA of a subset of the individuals (its total variance '
-                    'needs per-sample locus counts); use the exact method (up to 8192)')
-            scores, ratio = _pca.device_randomized_pca(self._dev, n_pcs, loci=loci,
-                                                       oversample=oversample, n_iter=n_iter,
-                                                       seed=seed)
-            return ids, scores[slots], ratio
-        if n > 8192:
-            raise ValueError('the exact genetic PCA takes at most 8192 individuals (got %d)' % n)
-        import torch
-        G = self._dev.geno_gram(slots, mask)
-        tdev = torch.device('cuda', int(self._dev.cfg.device))
-
-        def rmatmul(U):
-            Z = self._dev.geno_rmatmul(torch.as_tensor(U, dtype=torch.float32, device=tdev),
-                                       slots)
-            return Z if loci is None else Z[torch.as_tensor(loci, device=tdev)]
-
-        scores, ratio = _pca.pca_from_gram(G, n_pcs, rmatmul=rmatmul)
-        return ids, scores, ratio
-
-    def _calc_genetic_distances(self, individs=None, loci=None):
-        """Euclidean distances between the mean genotypes of the living individuals asked for
-        (reference demos/_IBD_IBE.py calc_dists, dist_type='gen', biallelic=False,
-        return_flat=False): 0.5 sqrt(G_ii + G_jj - 2 G_ij) from the exact Gram matrix (up to
-        8192 individuals).  -> (ids ascending, dist [n][n])"""
-        ids, slots = self._geno_sample(individs)
-        if ids.size > 8192:
-            raise ValueError('genetic distances of at most 8192 individuals per call (got %d)'
-                             % ids.size)
-        if self._dev.L == 0:
-            self._dev.geno_gram(slots[:1])            # the library's error: no genomes
-        loci, mask = self._geno_loci(loci)
-        G = self._dev.geno_gram(slots, mask)
-        g = np.diag(G)
-        return ids, 0.5 * np.sqrt((g[:, None] + g[None, :] - 2 * G).astype(np.float64))
-
-    # -- genotype-environment association (sim/gea.py; csrc/gnx_gea.hip) -----------------
-    def _gea_products(self, slots, loci, lyr_num):
-        """what sim/gea.cca_from_cross_products takes, from the device: C, s (gnx_geno_locus_gram),
-        DtZ, ZtZ, Zt1 (gnx_geno_locus_cross; Z = [e[:, lyr_num], x, y]) of the individuals in
-        `slots` at `loci`, and matmul(M [n_loci][3]) -> D M [n][3] (gnx_geno_matmul, fp32)"""
-        import torch
-        dev = self._dev
-        Cm, cs = dev.geno_locus_gram(loci, slots)
-        DtZ, ZtZ, Zt1 = dev.geno_locus_cross(loci, lyr_num, slots)
-        tdev = torch.device('cuda', int(dev.cfg.device))
-        loci_t = torch.as_tensor(loci, device=tdev)
-
-        def matmul(M):
-            full = torch.zeros((dev.L, M.shape[1]), dtype=torch.float32, device=tdev)
-            full[loci_t] = torch.as_tensor(M, dtype=torch.float32, device=tdev)
-            return dev.geno_matmul(full, slots).cpu().numpy().astype(np.float64)
-
-        return Cm, cs, DtZ, ZtZ, Zt1, matmul
-
-    def _run_cca(self, trt_num=0, individs=None, loci=None):
-        """Canonical correlation analysis genotype ~ env + lat + long for one Trait (reference
-        structs/species.py:2269-2355: sklearn's CCA(n_components=3) on the table of
-        _make_gea_df, :2218-2266; env = e of the Trait's Layer, lat = x, long = y), from
-        cross-products taken on the device (sim/gea.py): no N x L table leaves the GPU.
-        individs and loci (extensions) restrict the rows and the columns; at most 8192 loci.
-        -> dict(ind_df [n][3] (rows in ascending-id order), loci_df [n_loci][3], var_df [3][3],
-        trait_loci, ids)"""
-        from ..sim import gea as _gea
-        if self.gen_arch is None or self._dev.L == 0:
-            raise ValueError('run_gea: the Species has no genomes (no gen_arch)')
-        traits = self.gen_arch.traits
-        if not traits:
-            raise ValueError('run_gea: the Species has no Traits')
-        if isinstance(trt_num, bool) or trt_num not in traits:
-            raise ValueError('run_gea: no Trait %r (Traits: %s)' % (trt_num, sorted(traits)))
-        if not self.__dict__.get('_genomes_assigned', False):
-            raise ValueError('run_gea: genomes are assigned at the end of the burn-in; '
-                             'burn the model in first')
-        trt = traits[trt_num]
-        loci_u, _ = self._geno_loci(loci)
-        if loci_u is None:
-            loci_u = np.arange(self._dev.L, dtype=np.int64)
-        if loci_u.size > 8192:
-            raise ValueError('run_gea: at most 8192 loci per analysis (the cross-product matrix '
-                             'is n_loci x n_loci), got %d: choose them with loci=...' % loci_u.size)
-        ids, slots = self._geno_sample(individs)
-        prods = self._gea_products(slots, loci_u, int(trt.lyr_num))
-        res = _gea.cca_from_cross_products(*prods[:5], ids.size, prods[5])
-        return dict(ind_df=res['ind_df'], loci_df=res['loci_df'], var_df=res['var_df'],
-                    trait_loci=np.asarray(trt.loci), ids=ids)
-
-    # -- Mantel tests and MMRR (sim/mmrr.py; csrc/gnx_mantel.hip) --------------------------
-    def _dist_predictors(self, who, predictors, env_lyrs, trts):
-        """the device columns [(field, index), ...] of each named predictor: 'geo' = (x, y),
-        'env' = the layers env_lyrs (default: the layers the Traits are tied to, or every layer
-        of a Species without Traits), 'phn' = the Traits trts (default: all)"""
-        if isinstance(predictors, str):
-            predictors = (predictors,)
-        predictors = list(predictors)
-        if not predictors:
-            raise ValueError('%s: no predictors' % who)
-        traits = self.gen_arch.traits or {}
-        n_layers = int(self._dev.cfg.n_layers)
-        cols = []
-        for name in predictors:
-            if name == 'geo':
-                cols.append([(nat.F_X, 0), (nat.F_Y, 0)])
-            elif name == 'env':
-                lyrs = env_lyrs
-                if lyrs is None:
-                    lyrs = sorted({int(t.lyr_num) for t in traits.values()}) or range(n_layers)
-                lyrs = [int(l) for l in np.atleast_1d(lyrs)]
-                if not lyrs or min(lyrs) < 0 or max(lyrs) >= n_layers:
-                    raise ValueError('%s: env_lyrs: layers in 0..%d' % (who, n_layers - 1))
-                cols.append([(nat.F_E, l) for l in lyrs])
-            elif name == 'phn':
-                nums = sorted(traits) if trts is None else [int(t) for t in np.atleast_1d(trts)]
-                if not nums or any(t not in traits for t in nums):
-                    raise ValueError('%s: trts: Traits among %s' % (who, sorted(traits)))
-                cols.append([(nat.F_Z, t) for t in nums])
-            else:
-                raise ValueError("%s: unknown predictor %r ('geo', 'env', 'phn' or 'cost')"
-                                 % (who, name))
-        if len(set(predictors)) != len(predictors):
-            raise ValueError('%s: a predictor is listed twice' % who)
-        if len(cols) > 4 or sum(len(c) for c in cols) > 8:
-            raise ValueError('%s: at most 4 predictors and 8 columns (layers, traits, x, y) '
-                             'together' % who)
-        return predictors, cols
-
-    # -- least-cost distances (sim/cost.py; csrc/gnx_cost.hip) ------------------------------
-    def _cost_raster(self, who, lyr=None, kind='conductance', barrier=None, cost=None):
-        """the resistance raster R [H][W] of a request (sim/cost.resistance_raster): an explicit
-        cost raster, or the values of Layer lyr (default: the Layer of the move_surf) read as
-        kind"""
-        from ..sim import cost as _cost
-        W, H = self._land_dim
-        if cost is not None:
-            return _cost.resistance_raster(cost=cost, shape=(H, W))
-        land = self._land_ref
-        if lyr is None:
-            if not self._move_surf:
-                raise ValueError('%s: the Species has no move_surf to take the conductance '
-                                 'from: pass lyr=... or cost=...' % who)
-            lyr = self._spp_params.movement.move_surf['layer']
-        if isinstance(lyr, str):
-            nums = [k for k, l in land.items() if l.name == lyr]
-            if len(nums) != 1:
-                raise ValueError('%s: lyr: no single Layer is named %r' % (who, lyr))
-            lyr = nums[0]
-        if isinstance(lyr, bool) or int(lyr) != lyr or int(lyr) not in land:
-            raise ValueError('%s: lyr: a Layer among %s (got %r)' % (who, sorted(land), lyr))
-        return _cost.resistance_raster(land[int(lyr)].rast, kind=kind, barrier=barrier,
-                                       shape=(H, W))
-
-    def _cost_res(self):
-        return abs(float(self._land_res[0])), abs(float(self._land_res[1]))
-
-    def _cost_matrix_of_cells(self, R, cells):
-        """least-cost distances [n][n] of individuals standing on cells [n][2] = (x, y): the
-        distinct cells' matrix from the device, expanded (two individuals on one cell: 0)"""
-        from ..sim import cost as _cost
-        cells = np.asarray(cells, np.int64).reshape(-1, 2)
-        lin = cells[:, 1] * int(self._land_dim[0]) + cells[:, 0]
-        uniq, inverse = np.unique(lin, return_inverse=True)
-        return _cost.expand(self._dev.cost_matrix(R, self._cost_res(), uniq), inverse)
-
-    def _calc_cost_distances(self, lyr=None, kind='conductance', barrier=None, cost=None,
-                             individs=None):
-        """pairwise least-cost distances between the cells of the living individuals asked for
-        (all by default; at most 8192) over the resistance raster of the request, solved on the
-        device -> dict(ids ascending, cells [n][2], dist float64 [n][n])"""
-        who = 'calc_cost_distances'
-        ids, _ = self._geno_sample(individs)
-        if ids.size > 8192:
-            raise ValueError('%s: at most 8192 individuals per call (the distance matrix is '
-                             'n x n), got %d: sample them with n=... or individs=...'
-                             % (who, ids.size))
-        if ids.size < 1:
-            raise ValueError('%s: no individuals' % who)
-        R = self._cost_raster(who, lyr=lyr, kind=kind, barrier=barrier, cost=cost)
-        cells = self._get_cells(individs=ids)
-        return dict(ids=ids, cells=cells, dist=self._cost_matrix_of_cells(R, cells))
-
-    def _calc_cost_surface(self, x, y, lyr=None, kind='conductance', barrier=None, cost=None):
-        """the accumulated-cost raster float64 [k][H][W] of k points (x, y) in landscape
-        coordinates, floored to cells as _get_cells does"""
-        who = 'calc_cost_surface'
-        x = np.atleast_1d(np.asarray(x, np.float64)).ravel()
-        y = np.atleast_1d(np.asarray(y, np.float64)).ravel()
-        if x.size != y.size or x.size < 1:
-            raise ValueError('%s: as many x as y, at least one point' % who)
-        W, H = self._land_dim
-        if not (np.isfinite(x).all() and np.isfinite(y).all()):
-            raise ValueError('%s: a point is not finite' % who)
-        cx, cy = np.floor(x).astype(np.int64), np.floor(y).astype(np.int64)
-        if (cx < 0).any() or (cx >= W).any() or (cy < 0).any() or (cy >= H).any():
-            raise ValueError('%s: a point lies outside the landscape (0 <= x < %d, 0 <= y < %d)'
-                             % (who, W, H))
-        R = self._cost_raster(who, lyr=lyr, kind=kind, barrier=barrier, cost=cost)
-        return self._dev.cost_surfaces(R, self._cost_res(), cy * int(W) + cx)
-
-    def _dist_perm_sums(self, who, predictors, env_lyrs, trts, individs, loci, nperm, seed,
-                        min_n):
-        """(names, permuted cross-sums [nperm][K], moments) of a Mantel / MMRR request:
-        the reference's row shuffles drawn from `seed` (or the Species' rng), inverted for the
-        library, and gnx_dist_perm_sums on the device columns"""
-        from ..sim import mmrr as _mmrr
-        if self.gen_arch is None or self._dev.L == 0:
-            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
-        if not self.__dict__.get('_genomes_assigned', False):
-            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
-                             'model in first' % who)
-        if isinstance(nperm, bool) or int(nperm) != nperm or nperm < 1:
-            raise ValueError('%s: nperm: at least 1 permutation (got %r)' % (who, nperm))
-        names, cols, costs = _split_predictors(self, who, predictors, env_lyrs, trts)
-        ids, slots = self._geno_sample(individs)
-        if ids.size > 8192:
-            raise ValueError('%s: at most 8192 individuals per test (the distance matrix is '
-                             'n x n), got %d: sample them with n=... or individs=...'
-                             % (who, ids.size))
-        if ids.size < min_n:
-            raise ValueError('%s: %d individuals leave the test no degrees of freedom (at least '
-                             '%d)' % (who, ids.size, min_n))
-        _, mask = self._geno_loci(loci)
-        if not costs:
-            rows = _mmrr.draw_row_shuffles(ids.size, int(nperm), seed=seed, rng=self._rng)
-            sums, mom = self._dev.dist_perm_sums(cols, _mmrr.invert_rows(rows), slots, mask)
-            return names, sums, mom
-        # the cost matrices of the sample (rows in id order, as slots), built beside the columns
-        cells = self._get_cells(individs=ids)
-        mats = []
-        for name, opts in costs:
-            D = self._cost_matrix_of_cells(self._cost_raster(who, **opts), cells)
-            n_inf = int(np.isinf(D[np.tril_indices(ids.size, -1)]).sum())
-            if n_inf:
-                raise ValueError('%s: predictor %r: %d pairs of the sampled individuals are at '
-                                 'infinite cost (no path joins them): sample individuals that '
-                                 'can reach each other' % (who, name, n_inf))
-            mats.append(D)
-        rows = _mmrr.draw_row_shuffles(ids.size, int(nperm), seed=seed, rng=self._rng)
-        sums, mom = self._dev.dist_perm_sums_mat(cols, np.stack(mats), _mmrr.invert_rows(rows),
-                                                 slots, mask)
-        # the library's order (columns, then matrices) back to the caller's
-        lib = [n for n in names if n not in dict(costs)] + [n for n, _ in costs]
-        o = [lib.index(n) for n in names]
-        mom = dict(mom, sx=np.asarray(mom['sx'])[o], sxy=np.asarray(mom['sxy'])[o],
-                   sxx=np.asarray(mom['sxx'])[np.ix_(o, o)])
-        return names, np.ascontiguousarray(np.asarray(sums)[:, o]), mom
-
-    def _run_mmrr(self, predictors=('geo', 'env'), env_lyrs=None, trts=None, individs=None,
-                  loci=None, nperm=999, seed=None):
-        """multiple matrix regression with randomization of the genetic distances on the
-        predictors' distances (reference data/IBD_IBE_demo/MMRR.py, as demos/_IBD_IBE.py calls
-        it), every permutation's fit from cross-sums taken on the device
-        -> the reference's OrderedDict (sim/mmrr.mmrr)"""
-        from ..sim import mmrr as _mmrr
-        K = len(_predictor_list(predictors))
-        # n (n - 1) / 2 pairs must exceed the K + 1 coefficients
-        min_n = 3
-        while min_n * (min_n - 1) // 2 < K + 2:
-            min_n += 1
-        names, sums, mom = self._dist_perm_sums('run_mmrr', predictors, env_lyrs, trts,
-                                                individs, loci, nperm, seed, min_n)
-        return _mmrr.mmrr(sums, mom, names)
-
-    def _run_mantel(self, x='geo', given=None, env_lyrs=None, trts=None, individs=None,
-                    loci=None, nperm=999, seed=None):
-        """Mantel test of the genetic distances against predictor x, partial given another
-        (reference data/IBD_IBE_demo/run_mantel.R: vegan's mantel.partial with the genetic
-        matrix permuted) -> dict(r, p, nperm, perm_r [nperm])"""
-        from ..sim import mmrr as _mmrr
-        preds = (x,) if given is None else (x, given)
-        _, sums, mom = self._dist_perm_sums('run_mantel', preds, env_lyrs, trts, individs,
-                                            loci, nperm, seed, 3 if given is None else 4)
-        return _mmrr.mantel(sums, mom, 0, None if given is None else 1)
-
-    # -- fine-scale spatial genetic structure (sim/sgs.py; csrc/gnx_sgs.hip) ----------------
-    # pair-words (candidate pairs x genome words) one call may take: about ten seconds at the
-    # measured rate of the call with cells that fill their tiles (DESIGN section 15)
-    _SGS_MAX_WORK = 1 << 43
-
-    def _calc_spatial_structure(self, edges=None, n_classes=10, max_dist=None, individs=None,
-                                loci=None, nperm=0, seed=None, fit_range=None, max_work=None):
-        """kinship by distance class over the pairs of the living individuals asked for (all by
-        default; no n x n matrix, so the whole population can be analysed): Loiselle's kinship
-        per class, its slope on ln(distance), Sp and Wright's neighbourhood size
-        (sim/sgs.spatial_structure), from per-class sums taken on the device (gnx_sgs_sums).
-        edges: the classes' bounds, ascending (1..32 classes); default n_classes classes of equal
-        width in ln r from the landscape's cell size to max_dist (default: a quarter of the
-        shorter landscape side).  nperm > 0: the genomes are permuted over the positions, drawn
-        as run_mantel draws its permutations, one device call each.  fit_range: (first class,
-        one past the last) of the classes the slope is fitted over.  max_work: the pair-words
-        (candidate pairs x genome words) one call may take
-        -> dict of arrays and scalars: edges, pairs, mean_r, mean_lnr, F, dist2, slope, F1, Sp,
-        Nb, n, n_zero (pairs at distance 0: in no class), work, ids; with nperm: nperm,
-        perm_slope, p_slope, perm_F, p_F"""
-        from ..sim import mmrr as _mmrr
-        from ..sim import sgs as _sgs
-        who = 'calc_spatial_structure'
-        if self.gen_arch is None or self._dev.L == 0:
-            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
-        if not self.__dict__.get('_genomes_assigned', False):
-            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
-                             'model in first' % who)
-        if isinstance(nperm, bool) or int(nperm) != nperm or nperm < 0:
-            raise ValueError('%s: nperm: a number of permutations >= 0 (got %r)' % (who, nperm))
-        if edges is None:
-            dim = self._land_ref.dim
-            hi = min(dim) / 4.0 if max_dist is None else float(max_dist)
-            edges = _sgs.default_edges(1.0, hi, n_classes)
-        elif max_dist is not None:
-            raise ValueError('%s: give edges or max_dist, not both' % who)
-        edges = _sgs.check_edges(edges)
-        _sgs._fit_slice(fit_range, edges.size - 1)
-        if max_work is None:
-            max_work = self._SGS_MAX_WORK
-        if isinstance(max_work, bool) or int(max_work) != max_work or max_work < 1:
-            raise ValueError('%s: max_work: a positive number of pair-words (got %r)'
-                             % (who, max_work))
-        ids, slots = self._geno_sample(individs)
-        n = ids.size
-        if n < 2:
-            raise ValueError('%s: at least 2 individuals (got %d)' % (who, n))
-        if n > 2 ** 24:
-            raise ValueError('%s: at most 2^24 individuals per call (got %d): sample them with '
-                             'n=... or individs=...' % (who, n))
-        loci_u, mask = self._geno_loci(loci)
-        dev = self._dev
-        work = dev.sgs_sums(edges, slots, mask)['work']
-        if work > max_work:
-            raise ValueError('%s: %d pair-words of work (candidate pairs x genome words) exceed '
-                             'max_work = %d: analyse a sample (n=...), fewer loci (loci=...) or a '
-                             'smaller max_dist, or raise max_work' % (who, work, max_work))
-        cnt1, _ = dev.stats_group_counts(slots, np.array([0, n], np.int64))
-        s_l = cnt1[0].astype(np.int64)
-        weight = np.zeros(dev.L, np.float64)
-        if loci_u is None:
-            weight[:] = _sgs.locus_terms(s_l, n)[0]
-        else:
-            s_l = s_l[loci_u]
-            weight[loci_u] = _sgs.locus_terms(s_l, n)[0]
-        obs = dev.sgs_sums(edges, slots, mask, weight, None, max_work)
-        pI = pS = None
-        if nperm:
-            rows = _mmrr.draw_row_shuffles(n, int(nperm), seed=seed, rng=self._rng)
-            pI = np.empty((int(nperm),) + obs['isums'].shape, np.int64)
-            pS = np.empty((int(nperm),) + obs['fsums'].shape, np.float64)
-            for p, r in enumerate(rows):                  # position i takes the genome of r[i]
-                got = dev.sgs_sums(edges, slots, mask, weight, r.astype(np.int32), max_work)
-                pI[p], pS[p] = got['isums'], got['fsums']
-        out = _sgs.spatial_structure(obs['isums'], obs['fsums'], s_l, n, fit_range, pI, pS)
-        out.update(edges=edges, n_zero=obs['n_zero'], work=work, ids=ids)
-        return out
-
-    # -- genome-wide linkage disequilibrium (sim/ld.py; csrc/gnx_ld.hip) ---------------------
-    # tile-words (64 x 64-locus tiles x chromosome words) one call may take; a tile-word is 4096
-    # pair-words of the popcount tile, so this is four times _SGS_MAX_WORK (DESIGN section 16)
-    _LD_MAX_WORK = 1 << 33
-
-    def _ld_request(self, who, individs, loci, unit, min_maf):
-        """(ids, slots, loci ascending, their coordinates for the device, min_minor) of an LD
-        request"""
-        from ..sim import ld as _ld
-        if self.gen_arch is None or self._dev.L == 0:
-            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
-        if not self.__dict__.get('_genomes_assigned', False):
-            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
-                             'model in first' % who)
-        if unit not in ('c', 'morgans', 'loci'):
-            raise ValueError("%s: unit: 'c', 'morgans' or 'loci', not %r" % (who, unit))
-        ids, slots = self._geno_sample(individs)
-        if ids.size < 1 or ids.size > 2 ** 25:
-            raise ValueError('%s: 1..2^25 individuals per call (got %d): sample them with n=... '
-                             'or individs=...' % (who, ids.size))
-        loci_u, _ = self._geno_loci(loci)
-        if loci_u is None:
-            loci_u = np.arange(self._dev.L, dtype=np.int64)
-        if unit == 'loci':
-            pos = loci_u.astype(np.float64)
-        else:
-            rec = self.gen_arch.recombinations
-            rates = np.zeros(self._dev.L)
-            rates[rec._positions] = rec._rates
-            pos = _ld.map_positions(rates)[loci_u]
-        return ids, slots, loci_u, pos, _ld.min_minor(min_maf, 2 * ids.size)
-
-    def _ld_call(self, who, loci, pos, edges, slots, min_minor, morgans, max_work):
-        """one gnx_ld_bins call; the library's refusal of a request above max_work (it comes
-        before anything is launched) becomes a ValueError with advice"""
-        try:
-            return self._dev.ld_bins(loci, pos, edges, slots, min_minor, morgans, max_work)
-        except nat.GnxError as err:
-            if 'exceed max_work' not in str(err):
-                raise
-            raise ValueError('%s: %s: analyse a sample (n=...), fewer loci (loci=...) or a '
-                             'smaller max_dist, or raise max_work' % (who, err)) from None
-
-    def _calc_ld_decay(self, edges=None, n_bins=20, unit='c', max_dist=None, individs=None,
-                       loci=None, min_maf=0.05, max_work=None):
-        """the decay of linkage disequilibrium with distance: mean r^2 over the pairs of loci in
-        each distance bin, for all loci of the living individuals asked for (all by default), on
-        the device (gnx_ld_bins: no L x L matrix, any number of loci).  unit: 'c', the
-        recombination fraction between the two loci under the architecture's rates (sim/ld.py;
-        edges in c, an upper edge >= 0.5 taking in every looser pair); 'morgans', their map
-        distance; 'loci', the difference of their locus numbers.  edges: the bins' bounds
-        (default sim/ld.default_edges(unit, n_bins, max_dist)).  Loci whose minor-allele
-        frequency in the sample is below min_maf are left out.  max_work: the tile-words (tiles
-        of 64 x 64 loci x words of 64 chromosomes) the call may take
-        -> dict: edges, pairs, mean_r2, sd_r2, mean_dist (Morgans for 'c'), mean_c (c at the mean
-        map distance; NaN for 'loci'), expected_w (the mean of Weir & Hill's w(c), so that
-        E[mean_r2] ~ expected_w / N_e + 1 / n_chrom; inf in a bin holding a pair at distance 0;
-        NaN for 'loci'), n_chrom, n_loci_kept, c1 (1-alleles per locus), loci, ids, work"""
-        from ..sim import ld as _ld
-        who = 'calc_ld_decay'
-        ids, slots, loci_u, pos, mm = self._ld_request(who, individs, loci, unit, min_maf)
-        if edges is None:
-            edges = _ld.default_edges(unit, n_bins, max_dist, loci_u.size)
-        elif max_dist is not None:
-            raise ValueError('%s: give edges or max_dist, not both' % who)
-        edges = _ld.check_edges(edges)
-        dev_edges = _ld.c_to_morgans(edges) if unit == 'c' else edges
-        if unit == 'c' and ((edges < 0).any() or (edges[:-1] >= 0.5).any()):
-            raise ValueError('%s: edges in c lie in 0..0.5, at most the last at or above 0.5 '
-                             '(got %r)' % (who, edges.tolist()))
-        if max_work is None:
-            max_work = self._LD_MAX_WORK
-        if isinstance(max_work, bool) or int(max_work) != max_work or max_work < 1:
-            raise ValueError('%s: max_work: a positive number of tile-words (got %r)'
-                             % (who, max_work))
-        morgans = unit != 'loci'
-        got = self._ld_call(who, loci_u, pos, dev_edges, slots, mm, morgans, max_work)
-        work = got['work']
-        out = _ld.decay_stats(got['pairs'], got['sum_r2'], got['sum_r4'], got['sum_d'],
-                              got['sum_w'], morgans)
-        n_chrom = 2 * ids.size
-        c1 = got['c1']
-        out.update(edges=edges, pairs=got['pairs'], n_chrom=n_chrom,
-                   n_loci_kept=int((np.minimum(c1, n_chrom - c1) >= mm).sum()), c1=c1,
-                   loci=loci_u, ids=ids, work=work)
-        return out
-
-    def _calc_ne(self, method='ld', min_c=0.05, min_maf=0.05, individs=None, loci=None):
-        """the linkage-disequilibrium estimate of the effective population size (Waples 2006;
-        Weir & Hill 1980) from every pair of loci with recombination fraction >= min_c under the
-        architecture's rates (0.5: unlinked pairs only), in one device call:
-        N_e = mean w(c) / (mean r^2 - 1 / n_chrom) (sim/ld.ld_ne), for phase-known gametes under
-        random mating.  inf when the sample's own 1 / n_chrom explains all the r^2 there is, NaN
-        without pairs.  Confidence intervals are out of scope.  The call takes every tile of loci
-        at or beyond min_c, up to _LD_MAX_WORK tile-words (above it: ValueError; pass individs
-        or loci).
-        -> dict: Ne, mean_r2, r2_drift (mean_r2 - 1 / n_chrom), pairs, n_chrom, n_loci_kept,
-        min_c"""
-        from ..sim import ld as _ld
-        who = 'calc_ne'
-        if method != 'ld':
-            raise ValueError("%s: method: 'ld' (got %r)" % (who, method))
-        if not 0.0 <= float(min_c) <= 0.5:
-            raise ValueError('%s: min_c: a recombination fraction in 0..0.5 (got %r)'
-                             % (who, min_c))
-        ids, slots, loci_u, pos, mm = self._ld_request(who, individs, loci, 'c', min_maf)
-        # across a break the map puts BREAK_MORGANS: half of it already gives c = 0.5 exactly
-        lo = min(float(_ld.c_to_morgans(float(min_c))), _ld.BREAK_MORGANS / 2)
-        got = self._ld_call(who, loci_u, pos, np.array([lo, np.inf]), slots, mm, True,
-                            self._LD_MAX_WORK)
-        n_chrom = 2 * ids.size
-        m = int(got['pairs'][0])
-        mean = float(got['sum_r2'][0]) / m if m else float('nan')
-        c1 = got['c1']
-        return dict(Ne=_ld.ld_ne(m, got['sum_r2'][0], got['sum_w'][0], n_chrom), mean_r2=mean,
-                    r2_drift=mean - 1.0 / n_chrom, pairs=m, n_chrom=n_chrom,
-                    n_loci_kept=int((np.minimum(c1, n_chrom - c1) >= mm).sum()),
-                    min_c=float(min_c))
-
-    # -- model-based ancestry (sim/ancestry.py; csrc/gnx_admix.hip) ---------------------------
-    def _calc_ancestry(self, K, individs=None, loci=None, init='pca', seed=None, accelerate=True,
-                       tol=1e-4, max_sweeps=2000, fixed_F=None, budget=None):
-        """the admixture model of STRUCTURE / ADMIXTURE fitted by (accelerated) EM to the living
-        individuals asked for (all by default) at `loci` (all by default; 'neutral': the loci
-        under no selection), every sweep taken on the device from the packed genomes
-        (gnx_admix_sweep; sim/ancestry.fit describes the driver, its initialisations and what it
-        returns).  fixed_F [K][the loci used]: projection onto held frequencies.  seed None
-        with init='random': drawn from the Species' generator.  budget: bytes of partial sums
-        per chunk of individuals of one sweep (None: the library's default)
-        -> sim/ancestry.fit's dict; individs = the ids (ascending, the rows of Q), loci = the
-        loci used (ascending, the columns of F)"""
-        import torch
-        from ..sim import ancestry as _an
-        who = 'calc_ancestry'
-        K = _an.check_K(K)
-        if self.gen_arch is None or self._dev.L == 0:
-            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
-        if not self.__dict__.get('_genomes_assigned', False):
-            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
-                             'model in first' % who)
-        ids, slots = self._geno_sample(individs)
-        if ids.size < 1:
-            raise ValueError('%s: at least one individual' % who)
-        if isinstance(loci, str):
-            if loci != 'neutral':
-                raise ValueError("%s: loci: a list of loci, None or 'neutral' (got %r)"
-                                 % (who, loci))
-            loci = self.gen_arch.neut_loci
-        loci_u, mask = self._geno_loci(loci)
-        L_u = self._dev.L if loci_u is None else int(loci_u.size)
-        pcs = None
-        if isinstance(init, str) and init == 'pca' and K > 1:
-            _, pcs, _ = self._calc_genetic_PCA(n_pcs=K - 1, individs=ids, loci=loci_u)
-        if seed is None and isinstance(init, str) and init == 'random':
-            seed = int(self._rng.randint(0, 2 ** 31 - 1))
-        tdev = torch.device('cuda', int(self._dev.cfg.device))
-        sweep = _an.device_sweep(self._dev, slots, loci_u, mask, budget)
-        return _an.fit(sweep, ids.size, L_u, K, init=init, seed=seed, accelerate=accelerate,
-                       tol=tol, max_sweeps=max_sweeps, fixed_F=fixed_F, pcs=pcs,
-                       put=lambda a: torch.as_tensor(np.asarray(a, np.float64), device=tdev),
-                       loci=np.arange(L_u, dtype=np.int64) if loci_u is None else loci_u,
-                       individs=ids)
-
-    # -- identity tracts of the phased genomes (sim/tracts.py; csrc/gnx_tracts.hip) -----------
-    # word steps (haplotype pairs x genome words) one pair scan may take: 4096 individuals at
-    # 10^5 loci are 5.2e10
-    _TRACT_MAX_WORK = 1 << 37
-
-    def _tract_request(self, who, individs, unit, min_len, min_loci, n_max, advice):
-        """(ids, slots, pos, packed breaks, genome_len, min_len in units, min_loci) of a tract
-        request"""
-        from ..sim import tracts as _tr
-        if self.gen_arch is None or self._dev.L == 0:
-            raise ValueError('%s: the Species has no genomes (no gen_arch)' % who)
-        if not self.__dict__.get('_genomes_assigned', False):
-            raise ValueError('%s: genomes are assigned at the end of the burn-in; burn the '
-                             'model in first' % who)
-        if unit not in ('morgans', 'loci'):
-            raise ValueError("%s: unit: 'morgans' or 'loci', not %r" % (who, unit))
-        if isinstance(min_loci, bool) or int(min_loci) != min_loci or min_loci < 1:
-            raise ValueError('%s: min_loci: a number of loci >= 1 (got %r)' % (who, min_loci))
-        if isinstance(min_len, bool) or not 0 <= float(min_len) < np.inf:
-            raise ValueError('%s: min_len: a finite length >= 0 in %s (got %r)'
-                             % (who, unit, min_len))
-        ids, slots = self._geno_sample(individs)
-        if ids.size < 1 or ids.size > n_max:
-            raise ValueError('%s: 1..%d individuals per call (got %d)%s'
-                             % (who, n_max, ids.size, advice))
-        rec = self.gen_arch.recombinations
-        rates = np.zeros(self._dev.L)
-        rates[rec._positions] = rec._rates
-        pos, brk, genome_len = _tr.tract_map(rates, unit)
-        return (ids, slots, pos, _tr.pack_breaks(brk, self._dev.W64), genome_len,
-                _tr.to_units(min_len, unit), int(min_loci))
-
-    def _tract_edges(self, who, edges, unit):
-        from ..sim import tracts as _tr
-        if edges is None:
-            return None
-        e = np.asarray(edges, dtype=np.float64).ravel()
-        if not 2 <= e.size <= 65 or np.isnan(e).any() or (e < 0).any() or \
-                (np.diff(e) <= 0).any():
-            raise ValueError('%s: tract length edges: 2..65 ascending lengths >= 0 (got %r)'
-                             % (who, edges))
-        return _tr.check_tract_edges([_tr.to_units(v, unit) for v in e])
-
-    def _calc_roh(self, min_len=0.01, min_loci=50, unit='morgans', individs=None, edges=None,
-                  cover=False):
-        """runs of homozygosity: the tracts over which an individual's two homologues are
-        identical, no shorter than min_len (in the unit: Morgans on the architecture's map, or
-        loci) and min_loci loci, for the living individuals asked for (all by default), scanned
-        on the device (gnx_tracts_self).  A recombination rate of 0.5 or more is a chromosome
-        boundary that no tract crosses: under the template's free recombination every locus is
-        a break, so every tract is one locus long.  edges: bounds of a histogram of tract
-        lengths (in the unit; the last may be inf).  cover: per locus, the individuals with a
-        run over it (ROH islands)
-        -> dict: ids, n_roh, roh_loci, roh_len, longest (per individual; lengths in the unit),
-        f_roh (roh_len / genome_len; for 'loci' roh_loci / L), mean_f_roh, genome_len, hist
-        (dict(edges, tracts, sum_len) if edges), cover (if asked), unit"""
-        from ..sim import tracts as _tr
-        who = 'calc_roh'
-        ids, slots, pos, brk, genome_len, ml, mloci = self._tract_request(
-            who, individs, unit, min_len, min_loci, 2 ** 25,
-            ': sample them with n=... or individs=...')
-        e = self._tract_edges(who, edges, unit)
-        got = self._dev.tracts_self(pos, brk, mloci, ml, e, slots, bool(cover))
-        per = got['per']
-        f, mean_f = _tr.roh_stats(per[:, 1], per[:, 2], genome_len, self._dev.L, unit)
-        out = dict(ids=ids, n_roh=per[:, 0].copy(), roh_loci=per[:, 1].copy(),
-                   roh_len=_tr.from_units(per[:, 2], unit),
-                   longest=_tr.from_units(per[:, 3], unit), f_roh=f, mean_f_roh=mean_f,
-                   genome_len=float(_tr.from_units(genome_len, unit)), unit=unit)
-        if e is not None:
-            out['hist'] = dict(edges=np.asarray(edges, dtype=np.float64).ravel(),
-                               tracts=got['hist'][:, 0].copy(),
-                               sum_len=_tr.from_units(got['hist'][:, 1], unit))
-        if cover:
-            out['cover'] = got['cover']
-        return out
-
-    def _calc_ibs_sharing(self, min_len=0.02, min_loci=50, unit='morgans', individs=None,
-                          edges=None, n_classes=10, max_dist=None, tract_edges=None, cover=False,
-                          max_work=None):
-        """long tracts shared identical-by-state between individuals as a function of their
-        geographic distance (the recent-dispersal signal of Ringbauer et al. 2017): for every
-        two of the individuals asked for (at most 4096) the tracts, no shorter than min_len (in
-        the unit) and min_loci loci, over which one haplotype of the one equals one haplotype of
-        the other (four haplotype pairs), scanned on the device (gnx_tracts_pairs).  Under the
-        template's free recombination every locus is a break, so every tract is one locus long.
-        edges: the distance classes' bounds (default n_classes classes of equal width in ln r
-        from one landscape cell to max_dist; default a quarter of the shorter side).
-        tract_edges: bounds of a histogram of tract lengths (in the unit).  cover: per locus, the
-        haplotype pairs with a tract over it.  max_work: the word steps (haplotype pairs x
-        genome words) the call may take
-        -> dict: ids, n_tracts, shared_len, longest ([n][n], the diagonal the individual's own
-        runs of homozygosity; lengths in the unit), by_dist (dict: edges, pairs, mean_tracts,
-        mean_len, share_with_tract, mean_dist per class), hist (or None), cover (or None), work,
-        unit"""
-        from ..sim import sgs as _sgs
-        from ..sim import tracts as _tr
-        who = 'calc_ibs_sharing'
-        ids, slots, pos, brk, _, ml, mloci = self._tract_request(
-            who, individs, unit, min_len, min_loci, 4096,
-            ' (the matrices are n x n): sample them with n=... or individs=...')
-        if edges is None:
-            dim = self._land_ref.dim
-            hi = min(dim) / 4.0 if max_dist is None else float(max_dist)
-            edges = _sgs.default_edges(1.0, hi, n_classes)
-        elif max_dist is not None:
-            raise ValueError('%s: give edges or max_dist, not both' % who)
-        edges = _sgs.check_edges(edges)
-        te = self._tract_edges(who, tract_edges, unit)
-        if max_work is None:
-            max_work = self._TRACT_MAX_WORK
-        if isinstance(max_work, bool) or int(max_work) != max_work or max_work < 1:
-            raise ValueError('%s: max_work: a positive number of word steps (got %r)'
-                             % (who, max_work))
-        try:
-            got = self._dev.tracts_pairs(pos, brk, mloci, ml, te, slots, bool(cover),
-                                         int(max_work))
-        except nat.GnxError as err:
-            if 'exceed max_work' not in str(err):
-                raise
-            raise ValueError('%s: %s: analyse a sample (n=... or individs=...), or raise '
-                             'max_work' % (who, err)) from None
-        x = self._field(nat.F_X)[slots]
-        y = self._field(nat.F_Y)[slots]
-        by = _tr.sharing_stats(x, y, got['cnt'], got['len'], edges)
-        by['mean_len'] = _tr.from_units(by['mean_len'], unit)
-        by['edges'] = edges
-        hist = None
-        if te is not None:
-            hist = dict(edges=np.asarray(tract_edges, dtype=np.float64).ravel(),
-                        tracts=got['hist'][:, 0].copy(),
-                        sum_len=_tr.from_units(got['hist'][:, 1], unit))
-        return dict(ids=ids, n_tracts=got['cnt'], shared_len=_tr.from_units(got['len'], unit),
-                    longest=_tr.from_units(got['longest'], unit), by_dist=by, hist=hist,
-                    cover=got['cover'], work=got['work'], unit=unit)
-
-    # -- haplotype sweep scans (sim/sweeps.py; csrc/gnx_sweeps.hip) ----------------------------
-    # word steps (scanned cores x 4 scans x chromosome words x kept loci) one call may take: the
-    # bound no scan reaches, since a scan ends at its cutoff (DESIGN section 20)
-    _SWEEP_MAX_WORK = 1 << 42
-
-    def _sweep_request(self, who, individs, loci, unit, min_maf, cutoff, max_gap, max_extent,
-                       max_work):
-        """what the sweep calls share: the request checks of _ld_request, the integer map of the
-        unit (for 'sites' after a probe call that only counts c1), the thresholds as integers
-        -> dict(ids, slots, loci, pos, brk, scale, min_minor, kw), kw the keyword arguments of
-        Device.sweeps_scan"""
-        from ..sim import sweeps as _sw
-        if unit not in ('morgans', 'loci', 'sites'):
-            raise ValueError("%s: unit: 'morgans', 'loci' or 'sites', not %r" % (who, unit))
-        num, den = _sw.cutoff_fraction(cutoff)
-        lim = {}
-        for name, v in (('max_gap', max_gap), ('max_extent', max_extent)):
-            if v is not None and (isinstance(v, bool) or not 0 < float(v) < np.inf):
-                raise ValueError('%s: %s: a positive length in %s, or None (got %r)'
-                                 % (who, name, unit, v))
-            lim[name] = v
-        if max_work is None:
-            max_work = self._SWEEP_MAX_WORK
-        if isinstance(max_work, bool) or int(max_work) != max_work or max_work < 1:
-            raise ValueError('%s: max_work: a positive number of word steps (got %r)'
-                             % (who, max_work))
-        ids, slots, loci_u, _, mm = self._ld_request(who, individs, loci, 'loci', min_maf)
-        if ids.size > _sw.MAX_N:
-            raise ValueError('%s: 1..%d individuals per call (got %d): sample them with n=... or '
-                             'individs=...' % (who, _sw.MAX_N, ids.size))
-        mm = max(2, mm)
-        rec = self.gen_arch.recombinations
-        rates = np.zeros(self._dev.L)
-        rates[rec._positions] = rec._rates
-        kept = None
-        if unit == 'sites':
-            probe = self._dev.sweeps_scan(loci_u, loci_u, slots=slots, min_minor=mm, max_work=0)
-            kept = np.zeros(self._dev.L, bool)
-            kept[loci_u] = _sw.kept_loci(probe['c1'], 2 * ids.size, mm)
-        pos, brk, scale = _sw.sweep_map(rates, unit, kept)
-        nb = np.cumsum(brk)
-        b = np.zeros(loci_u.size, np.uint8)
-        b[1:] = nb[loci_u[1:]] > nb[loci_u[:-1]]
-        kw = dict(min_minor=mm, cut_num=num, cut_den=den, max_work=int(max_work))
-        for name, v in lim.items():
-            kw[name] = 0 if v is None else max(1, int(np.floor(float(v) * scale)))
-        return dict(ids=ids, slots=slots, loci=loci_u, pos=pos[loci_u], brk=b, scale=scale,
-                    min_minor=mm, kw=kw)
-
-    def _sweep_call(self, who, rq, cls=None, cores=None, curve=False):
-        """one gnx_sweeps_scan call; the library's refusal of a request above max_work becomes a
-        ValueError with advice"""
-        try:
-            return self._dev.sweeps_scan(rq['loci'], rq['pos'], rq['brk'], cls, cores,
-                                         rq['slots'], curve=curve, **rq['kw'])
-        except nat.GnxError as err:
-            if 'exceed max_work' not in str(err):
-                raise
-            raise ValueError('%s: %s: analyse a sample (n=...) or fewer loci (loci=...), or '
-                             'raise max_work' % (who, err)) from None
-
-    def _calc_ihs(self, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None, max_extent=None,
-                  individs=None, loci=None, n_freq_bins=20, keep_edge=False, max_work=None):
-        """the integrated haplotype score of every locus (Voight et al. 2006) from the phased
-        genomes of the living individuals asked for (at most 2048), scanned on the device
-        (gnx_sweeps_scan): around each core locus the haplotypes carrying the derived allele (1)
-        and those carrying the ancestral one (0) are followed outwards in both directions until
-        their EHH - the share of pairs still identical - falls below cutoff, and the area under
-        each curve is iHH.  unit: 'morgans' on the map of the architecture's recombination rates,
-        'loci' (locus numbers) or 'sites' (the rank among the loci kept: nSL).  Loci whose
-        minor-allele frequency in the sample is below min_maf (or whose minor count is below 2)
-        are neither cores nor steps.  A recombination rate of 0.5 or more is a chromosome
-        boundary no scan crosses: under the template's free recombination every scan ends at
-        once.  max_gap, max_extent (in the unit): a scan stops before a step longer than max_gap
-        and before leaving max_extent around the core.  A locus one of whose scans reached an
-        edge, a break or a gap before the cutoff has no score unless keep_edge.  ihs is ihs_unstd
-        standardised within n_freq_bins bins of the derived-allele frequency.  max_work: the
-        word steps (cores x 4 scans x words of 64 chromosomes x kept loci) the call may take
-        -> dict: loci, pos (in the unit), freq (of allele 1), ihh1, ihh0 (in the unit),
-        ihs_unstd = ln(ihh1 / ihh0), ihs, status [n_loci][2][2] ([direction: left, right]
-        [class]; 0 cutoff, 1 edge or break, 2 gap, 3 extent, 4 class below two chromosomes, 5 not
-        scanned), steps, kept, c1, n_chrom, work, ids, unit"""
-        from ..sim import sweeps as _sw
-        who = 'calc_ihs'
-        rq = self._sweep_request(who, individs, loci, unit, min_maf, cutoff, max_gap, max_extent,
-                                 max_work)
-        got = self._sweep_call(who, rq)
-        n_chrom = 2 * rq['ids'].size
-        c1 = got['c1']
-        unstd, h1, h0 = _sw.ihs_unstandardized(got['area'], got['status'], c1, n_chrom,
-                                               keep_edge=bool(keep_edge))
-        freq = c1 / float(n_chrom)
-        return dict(loci=rq['loci'], pos=rq['pos'] / float(rq['scale']), freq=freq,
-                    ihh1=h1 / rq['scale'], ihh0=h0 / rq['scale'], ihs_unstd=unstd,
-                    ihs=_sw.standardize_by_frequency(unstd, freq, n_freq_bins),
-                    status=got['status'], steps=got['steps'],
-                    kept=_sw.kept_loci(c1, n_chrom, rq['min_minor']), c1=c1, n_chrom=n_chrom,
-                    work=got['work'], ids=rq['ids'], unit=unit)
-
-    def _calc_xpehh(self, groups, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None,
-                    max_extent=None, individs=None, loci=None, keep_edge=False, max_work=None):
-        """the cross-population extended haplotype homozygosity of every locus (Sabeti et al.
-        2007) between two groups of individuals (groups as calc_fst takes them; exactly two
-        groups; individs restricts both), scanned on the device: around each core locus the
-        haplotypes of group a and those of group b are followed outwards, whatever allele they
-        carry at the core, and xpehh_unstd = ln(iHH_a / iHH_b); positive where group a carries
-        the longer haplotypes.  Loci are kept by their frequency in the two groups pooled.  One
-        departure from selscan: each population is scanned to its own cutoff, not until the
-        pooled EHH falls below it.  The other arguments as calc_ihs
-        -> dict: loci, pos, ihh_a, ihh_b, xpehh_unstd, xpehh (standardised over all defined
-        loci), status, steps, kept, c1, names, n_a, n_b, work, ids, unit"""
-        from ..sim import fst as _fst
-        from ..sim import sweeps as _sw
-        who = 'calc_xpehh'
-        # (the request checks come first: every living individual, as the groups see them)
-        all_ids = self._ld_request(who, None, None, 'loci', min_maf)[0]
-        names, order, start = _fst.make_groups(all_ids, groups)
-        if len(names) != 2:
-            raise ValueError('%s: exactly two groups (got %d)' % (who, len(names)))
-        member = np.full(all_ids.size, -1, np.int64)
-        member[order[:start[1]]] = 0
-        member[order[start[1]:]] = 1
-        if individs is not None:
-            ids_in = np.asarray(individs, dtype=np.int64).ravel()
-            member[~np.isin(all_ids, ids_in)] = -1
-        sample = all_ids[member >= 0]
-        rq = self._sweep_request(who, sample, loci, unit, min_maf, cutoff, max_gap, max_extent,
-                                 max_work)
-        grp = member[np.searchsorted(all_ids, rq['ids'])]
-        n_a, n_b = int((grp == 0).sum()), int((grp == 1).sum())
-        got = self._sweep_call(who, rq, cls=np.repeat(grp, 2).astype(np.uint8))
-        ha, hb = _sw.ihh_both(got['area'], got['status'], _sw.class_pairs(2 * n_a),
-                              _sw.class_pairs(2 * n_b), keep_edge=bool(keep_edge))
-        unstd = _sw.log_ratio(ha, hb)
-        n_chrom = 2 * rq['ids'].size
-        return dict(loci=rq['loci'], pos=rq['pos'] / float(rq['scale']), ihh_a=ha / rq['scale'],
-                    ihh_b=hb / rq['scale'], xpehh_unstd=unstd, xpehh=_sw.standardize(unstd),
-                    status=got['status'], steps=got['steps'],
-                    kept=_sw.kept_loci(got['c1'], n_chrom, rq['min_minor']), c1=got['c1'],
-                    names=names, n_a=n_a, n_b=n_b, work=got['work'], ids=rq['ids'], unit=unit)
-
-    def _calc_ehh(self, locus, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None,
-                  max_extent=None, individs=None, loci=None, max_work=None):
-        """the decay of extended haplotype homozygosity around one core locus (Sabeti et al.
-        2002), scanned on the device: per kept locus the scan reached, the share of pairs of
-        haplotypes carrying the derived (ehh1) or the ancestral allele (ehh0) at the core that
-        are still identical from the core to there; 1 at the core, NaN at loci that are not kept
-        and past the scan's end (the first value below the cutoff is included).  The arguments
-        as calc_ihs; the core must be a kept locus
-        -> dict: locus, loci, pos, ehh1, ehh0, status [2][2], steps [2][2], c1 (of the core),
-        n_chrom, ids, unit"""
-        from ..sim import sweeps as _sw
-        who = 'calc_ehh'
-        if isinstance(locus, bool) or int(locus) != locus:
-            raise ValueError('%s: locus: one locus number (got %r)' % (who, locus))
-        rq = self._sweep_request(who, individs, loci, unit, min_maf, cutoff, max_gap, max_extent,
-                                 max_work)
-        core = int(np.searchsorted(rq['loci'], int(locus)))
-        if core >= rq['loci'].size or rq['loci'][core] != int(locus):
-            raise ValueError('%s: locus %d is not among the loci of the request'
-                             % (who, int(locus)))
-        got = self._sweep_call(who, rq, cores=[core], curve=True)
-        n_chrom = 2 * rq['ids'].size
-        c1 = got['c1']
-        kept = _sw.kept_loci(c1, n_chrom, rq['min_minor'])
-        if not kept[core]:
-            raise ValueError('%s: locus %d is not kept: %d of %d chromosomes carry allele 1, the '
-                             'minor count is below %d (min_maf)'
-                             % (who, int(locus), c1[core], n_chrom, rq['min_minor']))
-        T = (_sw.class_pairs(n_chrom - c1[core]), _sw.class_pairs(c1[core]))
-        e0, e1 = _sw.ehh_curve(got['curve'], kept, core, T, rq['loci'].size)
-        return dict(locus=int(locus), loci=rq['loci'], pos=rq['pos'] / float(rq['scale']),
-                    ehh1=e1, ehh0=e0, status=got['status'][core], steps=got['steps'][core],
-                    c1=int(c1[core]), n_chrom=n_chrom, ids=rq['ids'], unit=unit)
-
-    # -- lineages through the recorded pedigree (structs/pedigree.py; csrc/gnx_lineage.hip) ----
-    # The reference simplifies its tables with tskit's default, which drops unary nodes: its
-    # lineage at a locus lists only the ancestors that survive simplification for the current
-    # sample.  The simplification here (_sort_and_simplify_table_collection) drops only the rows
-    # no lineage of the living passes through and keeps unary nodes, so a lineage lists EVERY
-    # ancestor.  _check_coalescence is the same either way (two lineages share
-    # their oldest in-simulation node exactly when they coalesce inside the simulation); the
-    # statistics are taken to the oldest in-simulation ancestor of the full pedigree, and no
-    # parity with tskit's simplification is claimed (DESIGN section 12).
-    _LINEAGE_DICT_MAX = 2000000          # chain entries _get_lineage_dicts turns into dicts
-
-    def _lineage_request(self, individs, nodes, loci, who):
-        """(the TreeTables, sample node ids int64, loci int64) of a lineage request"""
-        if self._tt is None:
-            raise ValueError("%s: no pedigree was recorded for this Species ('use_tskit' False, "
-                             "or the genomes were not assigned yet)" % who)
-        tt = self._tt
-        if nodes is None:
-            if individs is None:
-                ids, order = self._ids_sorted()
-                ids = ids[order]
-            else:
-                ids = np.asarray(individs, dtype=np.int64).ravel()
-            rows = np.searchsorted(tt.ids, ids)
-            if ids.size and not (tt.ids[np.minimum(rows, tt.ids.size - 1)] == ids).all():
-                raise ValueError('%s: individs holds ids the pedigree does not know' % who)
-            nodes = (2 * rows[:, None] + np.arange(2)[None, :]).ravel()
-        nodes = np.asarray(nodes, dtype=np.int64).ravel()
-        if nodes.size == 0:
-            raise ValueError('%s: no sample nodes' % who)
-        if nodes.min() < 0 or nodes.max() >= 2 * tt.ids.size:
-            raise ValueError('%s: nodes are node ids of the pedigree tables, 0..%d'
-                             % (who, 2 * tt.ids.size - 1))
-        L = self.gen_arch.L
-        loci = np.arange(L, dtype=np.int64) if loci is None else \
-            np.asarray(loci, dtype=np.int64).ravel()
-        if loci.size == 0 or loci.min() < 0 or loci.max() >= L:
-            raise ValueError('%s: loci: a non-empty list of loci in 0..%d' % (who, L - 1))
-        return tt, nodes, loci
-
-    def _lineage_curr_xy(self, tt, nodes):
-        """current x, y [n][2] of the sample nodes' individuals, read from the device columns
-        (as _get_coords); NaN rows for individuals that are not alive"""
-        ids, order = self._ids_sorted()
-        ids = ids[order]
-        xy = np.stack([self._field(nat.F_X)[order].astype(np.float64),
-                       self._field(nat.F_Y)[order].astype(np.float64)], axis=1)
-        want = tt.ids[nodes >> 1]
-        pos = np.minimum(np.searchsorted(ids, want), max(ids.size - 1, 0))
-        out = np.full((nodes.size, 2), np.nan)
-        alive = ids[pos] == want if ids.size else np.zeros(nodes.size, bool)
-        out[alive] = xy[pos[alive]]
-        return out
-
-    def _get_lineage_dicts(self, loci, nodes=None, drop_before_sim=True,
-                           time_before_present=True, use_individs_curr_pos=True,
-                           max_time_ago=None, min_time_ago=None):
-        """{locus: {sample node: {lineage node: (birth time, array([x, y]))}}}, youngest node
-        first (reference structs/species.py:1242-1276, structs/genome.py:1638-1760), the chains
-        walked on the device (gnx_lineage_chains).  Node ids are those of this Species'
-        pedigree tables (2 * row + homologue); `nodes` defaults to both nodes of every living
-        individual in ascending id order.  Times are time + t if time_before_present, and the
-        window min_time_ago..max_time_ago applies to the times as returned, as there.
-        use_individs_curr_pos puts the individual's current x, y (device columns) in the
-        sample node's own entry when that entry is among the kept nodes; the reference raises
-        KeyError when it is not, here the dict is left as it is.  The lineages list every
-        ancestor: a simplification keeps unary nodes (see the comment above).  Meant for
-        plotting-sized requests: above _LINEAGE_DICT_MAX chain entries it raises ValueError - use
-        _calc_lineage_stats(as_arrays=True) or _check_coalescence."""
-        who = '_get_lineage_dicts'
-        tt, nodes, loci = self._lineage_request(None, nodes, loci, who)
-        lo, hi = min_time_ago, max_time_ago
-        if not time_before_present:           # the window is on the raw table times then
-            lo = None if lo is None else lo + self.t
-            hi = None if hi is None else hi + self.t
-        tab, bt = tt.node_table()
-        kw = dict(drop_before_sim=drop_before_sim, min_time_ago=lo, max_time_ago=hi)
-        n_kept = self._dev.lineage_trace(tab, bt, nodes, loci, self.t, want=('n_kept',),
-                                         locus_range=False, **kw)['n_kept']
-        total = int(n_kept.sum(dtype=np.int64))
-        if total > self._LINEAGE_DICT_MAX:
-            raise ValueError('%s: %d lineage entries (more than %d): nested dicts are for '
-                             'plotting-sized requests; use _calc_lineage_stats(as_arrays=True) '
-                             'or _check_coalescence' % (who, total, self._LINEAGE_DICT_MAX))
-        off, chain = self._dev.lineage_chains(tab, bt, nodes, loci, self.t, n_kept=n_kept, **kw)
-        times = bt[chain >> 1].astype(np.float64) + (self.t if time_before_present else 0)
-        xy = tt._ind_xy[0][chain >> 1]
-        curr = self._lineage_curr_xy(tt, nodes) if use_individs_curr_pos else None
-        out = {}
-        n = nodes.size
-        for i, locus in enumerate(loci.tolist()):
-            d_loc = out[locus] = {}
-            for j, node in enumerate(nodes.tolist()):
-                a, b = off[i * n + j], off[i * n + j + 1]
-                d = {int(c): (float(tm), np.array(p)) for c, tm, p in
-                     zip(chain[a:b].tolist(), times[a:b], xy[a:b])}
-                if curr is not None and node in d:
-                    if np.isnan(curr[j, 0]):
-                        raise ValueError('%s: use_individs_curr_pos: the individual of node %d '
-                                         'is not alive' % (who, node))
-                    d[node] = (d[node][0], curr[j].copy())
-                d_loc[node] = d
-        return out
-
-    def _calc_lineage_stats(self, individs=None, nodes=None, loci=None,
-                            stats=['dir', 'dist', 'time', 'speed'], use_individs_curr_pos=True,
-                            max_time_ago=None, min_time_ago=None, as_arrays=False):
-        """Gene-flow statistics of the lineages of the sample nodes at the loci (reference
-        structs/species.py:1309-1343, structs/genome.py:1786-1871): 'dir' the compass
-        direction in degrees from the oldest kept node's birth location to the youngest's,
-        'dist' and 'time' oldest minus youngest, 'speed' = dist / time.  The youngest and
-        oldest kept node of every (locus, node) come from the device (gnx_lineage_trace); the
-        floats are computed here in fp64 with the reference's formulas.  -> {stat: {locus:
-        [value per node]}} with None where a lineage has fewer than two kept nodes; with
-        as_arrays (an extension) {stat: float64 [n_loci][n_nodes] (NaN there), 'nodes', 'loci'}.
-        individs are Geonomics ids (default: all living, ascending, two nodes each); nodes are
-        node ids of this Species' pedigree tables.  use_individs_curr_pos as in
-        _get_lineage_dicts.  The statistics reach back to the oldest in-simulation ancestor of
-        the FULL pedigree: the reference's simplified tables list fewer ancestors (see the
-        comment above _lineage_request)."""
-        from . import pedigree as _ped
-        who = '_calc_lineage_stats'
-        for st in stats:
-            if st not in _ped.LINEAGE_STATS:
-                raise ValueError("%s: the only valid statistics are 'dir', 'dist', 'time' and "
-                                 "'speed', not %r" % (who, st))
-        tt, nodes, loci = self._lineage_request(individs, nodes, loci, who)
-        tab, bt = tt.node_table()
-        tr = self._dev.lineage_trace(tab, bt, nodes, loci, self.t, drop_before_sim=True,
-                                     min_time_ago=min_time_ago, max_time_ago=max_time_ago,
-                                     want=('first', 'last', 'n_kept'), locus_range=False)
-        curr = self._lineage_curr_xy(tt, nodes) if use_individs_curr_pos else None
-        vals = _ped.lineage_stats(tt, nodes, tr['first'], tr['last'], tr['n_kept'], self.t,
-                                  stats, curr_xy=curr)
-        if as_arrays:
-            return dict(vals, nodes=nodes, loci=loci)
-        return {st: {locus: [None if v != v else v for v in vals[st][i].tolist()]
-                     for i, locus in enumerate(loci.tolist())} for st in stats}
-
-    def _check_coalescence(self, individs=None, loci=None, all_loci=False):
-        """whether the lineages of the individuals' nodes (default: all living) have coalesced
-        inside the simulation at each locus (default: all) -> {locus: bool}, or one bool for
-        all of them if all_loci (reference structs/species.py:1282-1306): the oldest
-        in-simulation node is the same for every sample node.  Reduced on the device to a min
-        and a max per locus (gnx_lineage_trace): nothing n_loci x n_nodes comes back.  A locus
-        at which some sample node has no in-simulation node at all is not coalesced."""
-        tt, nodes, loci = self._lineage_request(individs, None, loci, '_check_coalescence')
-        tab, bt = tt.node_table()
-        tr = self._dev.lineage_trace(tab, bt, nodes, loci, self.t, want=(), locus_range=True)
-        co = (tr['locus_lo'] == tr['locus_hi']) & (tr['locus_lo'] >= 0)
-        if all_loci:
-            return bool(co.all())
-        return {locus: bool(c) for locus, c in zip(loci.tolist(), co)}
 
     def _sort_and_simplify_table_collection(self, verbose=False):
         """Drop from the recorded pedigree every row that no lineage of a living individual

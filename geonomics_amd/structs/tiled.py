@@ -34,125 +34,91 @@ from . import genome as _genome
 from ..sim import burnin as _burnin
 
 
+# What is not done over tiles yet: method -> its refusal.  TiledSpecies gets one method per line
+# (below the class), so a call says what is missing before it reaches a device call that would
+# see one tile only.
+_NOT_TILED = {
+    # genetic PCA and distances (each tile's products are row-local, but they would need an
+    # all-reduce of L x k and k x k, and the Gram matrix a gather of the sample)
+    '_calc_genetic_PCA': 'genetic PCA of a Species tiled over several GPUs is not '
+                         'implemented; run the model on one GPU',
+    '_calc_genetic_distances': 'genetic distances of a Species tiled over several GPUs are '
+                               'not implemented; run the model on one GPU',
+    # GEA (the cross-products add over tiles: one all-reduce of n_loci x n_loci, then the scores
+    # tile by tile)
+    '_run_cca': 'run_gea with a Species tiled over several GPUs is not '
+                'implemented; run the model on one GPU',
+    # Mantel tests and MMRR (the distance matrix pairs individuals of different tiles: a gather
+    # of the sample)
+    '_run_mmrr': 'run_mmrr with a Species tiled over several GPUs is not '
+                 'implemented; run the model on one GPU',
+    '_run_mantel': 'run_mantel with a Species tiled over several GPUs is not '
+                   'implemented; run the model on one GPU',
+    # least-cost distances (a path crosses the tiles' borders; the raster would be solved on one
+    # rank anyway).  A 'cost' predictor reaches the refusals above
+    '_calc_cost_distances': 'calc_cost_distances with a Species tiled over several GPUs '
+                            'is not implemented; run the model on one GPU',
+    '_calc_cost_surface': 'calc_cost_surface with a Species tiled over several GPUs is '
+                          'not implemented; run the model on one GPU',
+    # spatial genetic structure (pairs across a tile border: the border cells of the neighbours'
+    # samples would have to be exchanged)
+    '_calc_spatial_structure': 'calc_spatial_structure with a Species tiled over several '
+                               'GPUs is not implemented; run the model on one GPU',
+    '_calc_ld_decay': 'calc_ld_decay with a Species tiled over several GPUs is not '
+                      'implemented; run the model on one GPU',
+    '_calc_ne': 'calc_ne with a Species tiled over several GPUs is not '
+                'implemented; run the model on one GPU',
+    '_calc_ancestry': 'calc_ancestry with a Species tiled over several GPUs is not '
+                      'implemented; run the model on one GPU',
+    # identity tracts (a pair of individuals of different tiles: a gather of the sample)
+    '_calc_roh': 'calc_roh with a Species tiled over several GPUs is not '
+                 'implemented; run the model on one GPU',
+    '_calc_ibs_sharing': 'calc_ibs_sharing with a Species tiled over several GPUs is '
+                         'not implemented; run the model on one GPU',
+    # haplotype sweep scans (one bit row holds the whole sample: a gather)
+    '_calc_ihs': 'calc_ihs with a Species tiled over several GPUs is not '
+                 'implemented; run the model on one GPU',
+    '_calc_xpehh': 'calc_xpehh with a Species tiled over several GPUs is not '
+                   'implemented; run the model on one GPU',
+    '_calc_ehh': 'calc_ehh with a Species tiled over several GPUs is not '
+                 'implemented; run the model on one GPU',
+    # lineages (each rank records its own births: the pedigree of a tiled Species is in pieces,
+    # and a lineage crosses them)
+    '_get_lineage_dicts': 'lineages of a Species tiled over several GPUs are not '
+                          'implemented; run the model on one GPU',
+    '_calc_lineage_stats': 'lineage statistics of a Species tiled over several GPUs are '
+                           'not implemented; run the model on one GPU',
+    '_check_coalescence': 'the coalescence check of a Species tiled over several GPUs '
+                          'is not implemented; run the model on one GPU',
+    '_sort_and_simplify_table_collection':
+        'simplifying the pedigree of a Species tiled over several '
+        'GPUs is not implemented; run the model on one GPU',
+    # Fst, diversity and the SFS of groups (the per-group counts add over tiles: one all-reduce
+    # of G x L, with the groups agreed between the ranks)
+    '_group_counts': 'group counts (Fst, diversity, SFS) of a Species tiled over '
+                     'several GPUs are not implemented; run the model on one GPU',
+    # moving-window diversity rasters (a window reaches over a tile's edge: the four integers
+    # add over tiles, one all-reduce of O(map))
+    '_calc_diversity_map': 'calc_diversity_map with a Species tiled over several GPUs is '
+                           'not implemented; run the model on one GPU',
+    # introductions (the newcomers would have to be routed to their tiles)
+    '_add_individuals': 'add_individuals with a Species tiled over several GPUs is '
+                        'not implemented; run the model on one GPU',
+}
+
+
+def _refusal(message):
+    def refuse(*args, **kw):
+        raise NotImplementedError(message)
+    return refuse
+
+
 class TiledSpecies(Species):
     def __init__(self, *args, comm=None, **kw):
         super().__init__(*args, **kw)
         self._comm = comm
         self._stepper = None
         self._glob_N = 0
-
-    # -- genetic PCA and distances: not over tiles --------------------------------------
-    # (each tile's products are row-local, but they would need an all-reduce of L x k and
-    # k x k, and the Gram matrix a gather of the sample)
-    def _calc_genetic_PCA(self, *args, **kw):
-        raise NotImplementedError('genetic PCA of a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    def _calc_genetic_distances(self, *args, **kw):
-        raise NotImplementedError('genetic distances of a Species tiled over several GPUs are '
-                                  'not implemented; run the model on one GPU')
-
-    # -- GEA: not over tiles (the cross-products add over tiles: one all-reduce of
-    # n_loci x n_loci, then the scores tile by tile)
-    def _run_cca(self, *args, **kw):
-        raise NotImplementedError('run_gea with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    # -- Mantel tests and MMRR: not over tiles (the distance matrix pairs individuals of
-    # different tiles: a gather of the sample)
-    def _run_mmrr(self, *args, **kw):
-        raise NotImplementedError('run_mmrr with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    def _run_mantel(self, *args, **kw):
-        raise NotImplementedError('run_mantel with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    # -- least-cost distances: not over tiles (a path crosses the tiles' borders; the raster
-    # would be solved on one rank anyway).  A 'cost' predictor reaches the refusals above
-    def _calc_cost_distances(self, *args, **kw):
-        raise NotImplementedError('calc_cost_distances with a Species tiled over several GPUs '
-                                  'is not implemented; run the model on one GPU')
-
-    def _calc_cost_surface(self, *args, **kw):
-        raise NotImplementedError('calc_cost_surface with a Species tiled over several GPUs is '
-                                  'not implemented; run the model on one GPU')
-
-    # -- spatial genetic structure: not over tiles (pairs across a tile border: the border
-    # cells of the neighbours' samples would have to be exchanged)
-    def _calc_spatial_structure(self, *args, **kw):
-        raise NotImplementedError('calc_spatial_structure with a Species tiled over several '
-                                  'GPUs is not implemented; run the model on one GPU')
-
-    def _calc_ld_decay(self, *args, **kw):
-        raise NotImplementedError('calc_ld_decay with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    def _calc_ne(self, *args, **kw):
-        raise NotImplementedError('calc_ne with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    def _calc_ancestry(self, *args, **kw):
-        raise NotImplementedError('calc_ancestry with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    # -- identity tracts: not over tiles (a pair of individuals of different tiles: a gather of
-    # the sample)
-    def _calc_roh(self, *args, **kw):
-        raise NotImplementedError('calc_roh with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    def _calc_ibs_sharing(self, *args, **kw):
-        raise NotImplementedError('calc_ibs_sharing with a Species tiled over several GPUs is '
-                                  'not implemented; run the model on one GPU')
-
-    # -- haplotype sweep scans: not over tiles (one bit row holds the whole sample: a gather)
-    def _calc_ihs(self, *args, **kw):
-        raise NotImplementedError('calc_ihs with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    def _calc_xpehh(self, *args, **kw):
-        raise NotImplementedError('calc_xpehh with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    def _calc_ehh(self, *args, **kw):
-        raise NotImplementedError('calc_ehh with a Species tiled over several GPUs is not '
-                                  'implemented; run the model on one GPU')
-
-    # -- lineages: not over tiles (each rank records its own births: the pedigree of a tiled
-    # Species is in pieces, and a lineage crosses them)
-    def _get_lineage_dicts(self, *args, **kw):
-        raise NotImplementedError('lineages of a Species tiled over several GPUs are not '
-                                  'implemented; run the model on one GPU')
-
-    def _calc_lineage_stats(self, *args, **kw):
-        raise NotImplementedError('lineage statistics of a Species tiled over several GPUs are '
-                                  'not implemented; run the model on one GPU')
-
-    def _check_coalescence(self, *args, **kw):
-        raise NotImplementedError('the coalescence check of a Species tiled over several GPUs '
-                                  'is not implemented; run the model on one GPU')
-
-    def _sort_and_simplify_table_collection(self, *args, **kw):
-        raise NotImplementedError('simplifying the pedigree of a Species tiled over several '
-                                  'GPUs is not implemented; run the model on one GPU')
-
-    # -- Fst, diversity and the SFS of groups: not over tiles (the per-group counts add over
-    # tiles: one all-reduce of G x L, with the groups agreed between the ranks)
-    def _group_counts(self, *args, **kw):
-        raise NotImplementedError('group counts (Fst, diversity, SFS) of a Species tiled over '
-                                  'several GPUs are not implemented; run the model on one GPU')
-
-    # -- moving-window diversity rasters: not over tiles (a window reaches over a tile's edge:
-    # the four integers add over tiles, one all-reduce of O(map))
-    def _calc_diversity_map(self, *args, **kw):
-        raise NotImplementedError('calc_diversity_map with a Species tiled over several GPUs is '
-                                  'not implemented; run the model on one GPU')
-
-    # -- introductions: not over tiles (the newcomers would have to be routed to their tiles)
-    def _add_individuals(self, *args, **kw):
-        raise NotImplementedError('add_individuals with a Species tiled over several GPUs is '
-                                  'not implemented; run the model on one GPU')
 
     # -- construction -----------------------------------------------------------------
     def _capacities(self, cap, N0):
@@ -418,3 +384,7 @@ class TiledSpecies(Species):
         its own device - an observer's call, not part of a step (the step's own density comes
         from the all-reduced bins)"""
         return Species._calc_density(self, normalize=normalize, as_layer=as_layer, set_N=set_N)
+
+
+for _name, _message in _NOT_TILED.items():
+    setattr(TiledSpecies, _name, _refusal(_message))

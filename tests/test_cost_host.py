@@ -16,7 +16,7 @@ import pytest
 
 from geonomics_amd.sim import cost as K
 from geonomics_amd.sim import mmrr as M
-from geonomics_amd.structs import species as S
+from geonomics_amd.structs.analyses import SpeciesAnalyses
 from geonomics_amd.structs.landscape import Landscape, Layer
 from test_mmrr_host import BAR, GAP, lstsq_fit, small_sample, smallest_gap
 
@@ -222,13 +222,8 @@ class _Dev:
         return K.numpy_cost_surfaces(R, res, src)
 
 
-class _Species:
+class _Species(SpeciesAnalyses):
     """a Species stand-in: the real methods over the numpy device"""
-    for _name in ('_run_mmrr', '_run_mantel', '_dist_perm_sums', '_dist_predictors', '_geno_loci',
-                  '_cost_raster', '_cost_res', '_cost_matrix_of_cells', '_calc_cost_distances',
-                  '_calc_cost_surface'):
-        locals()[_name] = getattr(S.Species, _name)
-    del _name
 
     def __init__(self, D, x, y, e, z, ids, land, move_surf=1):
         self._dev = _Dev(D, x, y, e, z)

@@ -12,7 +12,7 @@ import pytest
 
 from geonomics_amd.sim import divmap as DM
 from geonomics_amd.sim import fst as F
-from geonomics_amd.structs import species as S
+from geonomics_amd.structs.analyses import SpeciesAnalyses
 
 U53 = 2.0 ** -53
 
@@ -164,12 +164,9 @@ class _Dev:
         return out
 
 
-class _Species:
+class _Species(SpeciesAnalyses):
     """a Species stand-in: the real _calc_diversity_map and _group_by_grid over the numpy
     device, columns kept in slot order"""
-    _calc_diversity_map = S.Species._calc_diversity_map
-    _group_by_grid = S.Species._group_by_grid
-    _geno_loci = S.Species._geno_loci
 
     def __init__(self, xy, gts, ids, dim):
         self._dev = _Dev(gts)

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from geonomics_amd.sim import gea as G
-from geonomics_amd.structs import species as S
+from geonomics_amd.structs.analyses import SpeciesAnalyses
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g18_gea.npz')
 BAR = 1e-9
@@ -133,10 +133,8 @@ class _Dev:
         self.L, self.W64 = L, (L + 1023) // 1024 * 16
 
 
-class _Species:
+class _Species(SpeciesAnalyses):
     """a Species stand-in: the real _run_cca / _geno_loci over numpy products"""
-    _run_cca = S.Species._run_cca
-    _geno_loci = S.Species._geno_loci
 
     def __init__(self, D, Z2, ids, L=None):
         self.D, self.e, self.ids = D, Z2, np.asarray(ids)

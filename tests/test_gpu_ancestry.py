@@ -48,6 +48,7 @@ from test_ancestry_host import PLANTED, RECOVERY
 from test_gpu_mmrr import _handle
 from test_gpu_parity import native
 from geonomics_amd.sim import ancestry as AN
+from geonomics_amd.structs.analyses import SpeciesAnalyses
 
 pytestmark = pytest.mark.gpu
 
@@ -329,7 +330,7 @@ class _Arch:
     neut_loci = np.arange(0, PLANTED['L'], 3)
 
 
-class _Spp:
+class _Spp(SpeciesAnalyses):
     """a Species' analysis methods over a Device that holds an uploaded sample"""
     gen_arch = _Arch()
 
@@ -354,8 +355,7 @@ class _Mod:
 def _model_over(dev):
     from geonomics_amd.sim.model import Model
     from geonomics_amd.structs.species import Species
-    for name in ('_calc_ancestry', '_geno_sample', '_geno_loci', '_calc_genetic_PCA', '_field'):
-        setattr(_Spp, name, getattr(Species, name))
+    _Spp._field = Species._field
     for name in ('calc_ancestry', '_test_sample'):
         setattr(_Mod, name, getattr(Model, name))
     return _Mod(_Spp(dev))

@@ -9,6 +9,7 @@ import pytest
 
 import _ld as T
 from geonomics_amd.sim import ld as LD
+from geonomics_amd.structs.analyses import SpeciesAnalyses
 
 
 def test_map_positions_constant_rate_gives_the_product_formula():
@@ -174,7 +175,7 @@ class _Dev:
         return out
 
 
-class _Species:
+class _Species(SpeciesAnalyses):
     """a Species stand-in: the real _calc_ld_decay and _calc_ne over the numpy device"""
 
     def __init__(self, gts, ids, rates):
@@ -194,10 +195,6 @@ class _Species:
 
 
 def _stand_in():
-    from geonomics_amd.structs import species as S
-    for name in ('_calc_ld_decay', '_calc_ne', '_ld_request', '_ld_call', '_geno_loci',
-                 '_LD_MAX_WORK'):
-        setattr(_Species, name, getattr(S.Species, name))
     bits = T.wright_fisher(60, 90, 0.02, 30, 4)
     gts = bits.reshape(60, 2, 90).transpose(0, 2, 1).copy()
     ids = np.random.RandomState(2).permutation(60) * 3 + 5

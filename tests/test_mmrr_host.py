@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from geonomics_amd.sim import mmrr as M
-from geonomics_amd.structs import species as S
+from geonomics_amd.structs.analyses import SpeciesAnalyses
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g20_mmrr.npz')
 BAR = 1e-9
@@ -247,13 +247,8 @@ class _Dev:
         return sums, M.numpy_moments(Y, Xs)
 
 
-class _Species:
+class _Species(SpeciesAnalyses):
     """a Species stand-in: the real _run_mmrr / _run_mantel over numpy cross-sums"""
-    _run_mmrr = S.Species._run_mmrr
-    _run_mantel = S.Species._run_mantel
-    _dist_perm_sums = S.Species._dist_perm_sums
-    _dist_predictors = S.Species._dist_predictors
-    _geno_loci = S.Species._geno_loci
 
     def __init__(self, D, x, y, e, z, ids, L=None):
         self._dev = _Dev(D, x, y, e, z, L)

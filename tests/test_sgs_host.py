@@ -16,6 +16,7 @@ import _sgs as O
 from geonomics_amd.sim import mmrr as M
 from geonomics_amd.sim import sgs as G
 from geonomics_amd.structs import species as S
+from geonomics_amd.structs.analyses import SpeciesAnalyses
 
 BAR = 1e-9
 GAP = 1e-8
@@ -196,11 +197,8 @@ class _Dev:
         return dict(work=work, isums=isums, fsums=fsums, n_zero=nz)
 
 
-class _Species:
+class _Species(SpeciesAnalyses):
     """a Species stand-in: the real _calc_spatial_structure over the numpy device"""
-    _calc_spatial_structure = S.Species._calc_spatial_structure
-    _geno_loci = S.Species._geno_loci
-    _SGS_MAX_WORK = S.Species._SGS_MAX_WORK
 
     def __init__(self, x, y, D, ids, dim=(12, 12)):
         self._dev = _Dev(x, y, D)

@@ -9,6 +9,7 @@ import pytest
 
 import _sweeps as W
 from geonomics_amd.sim import sweeps as SW
+from geonomics_amd.structs.analyses import SpeciesAnalyses
 
 
 def _same(got, ref, label=''):
@@ -247,7 +248,7 @@ class _Dev:
         return got
 
 
-class _Species:
+class _Species(SpeciesAnalyses):
     """a Species stand-in: the real _calc_ihs, _calc_xpehh and _calc_ehh over the numpy device"""
 
     def __init__(self, haps, ids, rates):
@@ -266,10 +267,6 @@ class _Species:
 
 
 def _stand_in():
-    from geonomics_amd.structs import species as S
-    for name in ('_calc_ihs', '_calc_xpehh', '_calc_ehh', '_sweep_request', '_sweep_call',
-                 '_SWEEP_MAX_WORK', '_ld_request', '_geno_loci'):
-        setattr(_Species, name, getattr(S.Species, name))
     rng = np.random.RandomState(3)
     n, L = 40, 300
     haps = W.mosaic(rng, n, L, n_founders=6, mean_seg=50, mu=1 / 200)

@@ -9,6 +9,7 @@ import pytest
 
 import _tracts as T
 from geonomics_amd.sim import tracts as TR
+from geonomics_amd.structs.analyses import SpeciesAnalyses
 
 
 @pytest.fixture(scope='module')
@@ -261,7 +262,7 @@ class _Dev:
         return TR.brute_pairs(h, pos, self._brk(brk), min_loci, min_len, edges, cover)
 
 
-class _Species:
+class _Species(SpeciesAnalyses):
     """a Species stand-in: the real _calc_roh and _calc_ibs_sharing over the numpy device"""
 
     def __init__(self, haps, ids, rates, xy):
@@ -286,10 +287,6 @@ class _Species:
 
 
 def _stand_in():
-    from geonomics_amd.structs import species as S
-    for name in ('_calc_roh', '_calc_ibs_sharing', '_tract_request', '_tract_edges',
-                 '_TRACT_MAX_WORK'):
-        setattr(_Species, name, getattr(S.Species, name))
     rng = np.random.RandomState(3)
     n, L = 30, 500
     haps = T.mosaic(rng, n, L, mean_seg=120)

@@ -29,6 +29,7 @@ sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402
 from geonomics_amd.sim import gea as G  # noqa: E402
+from geonomics_amd.structs.analyses import SpeciesAnalyses  # noqa: E402
 from geonomics_amd.structs.species import Species  # noqa: E402
 
 # 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz 32-bit VALU operations per second; one AND + popcount
@@ -52,13 +53,16 @@ def timed(fn, reps, warm=1):
     return t
 
 
+class _StandIn(SpeciesAnalyses):
+    _field = Species._field
+
+
 def stand_in_species(dev, lyr_num):
     """the real Species methods of the analysis around a bare handle"""
     trt = types.SimpleNamespace(lyr_num=lyr_num, loci=np.zeros(0, np.int64))
-    spp = types.SimpleNamespace(_dev=dev, gen_arch=types.SimpleNamespace(traits={0: trt}),
-                                _genomes_assigned=True)
-    for name in ('_field', '_geno_sample', '_geno_loci', '_gea_products', '_run_cca'):
-        setattr(spp, name, types.MethodType(getattr(Species, name), spp))
+    spp = _StandIn()
+    spp._dev, spp.gen_arch = dev, types.SimpleNamespace(traits={0: trt})
+    spp._genomes_assigned = True
     return spp
 
 
