@@ -74,6 +74,8 @@ EXPORTS = [
     'gnx_admix_sweep', 'gnx_admix_info',
     'gnx_sweeps_scan', 'gnx_sweeps_info',
     'gnx_divmap_sums', 'gnx_divmap_info',
+    'gnx_circuit_matrix', 'gnx_circuit_current', 'gnx_circuit_potentials', 'gnx_circuit_budget',
+    'gnx_circuit_info',
 ]
 
 
@@ -1222,6 +1224,65 @@ class Device:
                                          C.byref(b)))
         return dict(kernel_ms=ms.value, launches=int(n.value), rounds=int(r.value),
                     batches=int(b.value))
+
+    # -- circuit-theory resistances and current maps (csrc/gnx_circuit.hip) ----------------
+    def _circuit_args(self, R, res, cells, tol, max_iter):
+        R = self._cost_raster(R)
+        cells = _arr(cells, np.int32).ravel()
+        return R, cells, (
+            self.h, _ptr(R, C.c_double), C.c_double(float(res[0])), C.c_double(float(res[1])),
+            C.c_int32(int(cells.size)), _ptr(cells if cells.size else None, C.c_int32),
+            C.c_double(1e-10 if tol is None else float(tol)),
+            C.c_int64(0 if max_iter is None else int(max_iter)))
+
+    def circuit_matrix(self, R, res, cells, tol=None, max_iter=None):
+        """the pairwise effective resistances of distinct cells (y * W + x) over the resistance
+        raster R float64 [H][W] (inf: impassable), exactly symmetric; tol: the relative residual
+        every system is solved to (default 1e-10), max_iter: the CG iterations a batch may take
+        (default: twice the cells of the largest component)
+        (include/gnx_hip.h, gnx_circuit_matrix) -> float64 [n][n]"""
+        R, cells, args = self._circuit_args(R, res, cells, tol, max_iter)
+        n = int(cells.size) if 1 <= cells.size <= 8192 else 0     # the library refuses the rest
+        D = np.zeros((n, n), np.float64)
+        self._chk(self.lib.gnx_circuit_matrix(*args, _ptr(D if D.size else None, C.c_double)))
+        return D
+
+    def circuit_current(self, R, res, cells, tol=None, max_iter=None):
+        """the cumulative node-current map of all pairs of at most 128 distinct cells
+        (include/gnx_hip.h, gnx_circuit_current)
+        -> (float64 [H][W], pairs used, pairs skipped)"""
+        R, cells, args = self._circuit_args(R, res, cells, tol, max_iter)
+        out = np.zeros((self.cfg.H, self.cfg.W), np.float64)
+        counts = np.zeros(2, np.int64)
+        self._chk(self.lib.gnx_circuit_current(*args, _ptr(out, C.c_double),
+                                               _ptr(counts, C.c_int64)))
+        return out, int(counts[0]), int(counts[1])
+
+    def circuit_potentials(self, R, res, cells, tol=None, max_iter=None):
+        """the potentials x_i of L x_i = e_i - e_anchor of at most 128 distinct cells as the
+        solver left them (include/gnx_hip.h, gnx_circuit_potentials)
+        -> (float64 [n][H][W], anchor int32 [n])"""
+        R, cells, args = self._circuit_args(R, res, cells, tol, max_iter)
+        n = int(cells.size) if 1 <= cells.size <= 128 else 0      # the library refuses the rest
+        out = np.zeros((n, self.cfg.H, self.cfg.W), np.float64)
+        anchor = np.full(n, -1, np.int32)
+        self._chk(self.lib.gnx_circuit_potentials(
+            *args, _ptr(anchor if n else None, C.c_int32),
+            _ptr(out if out.size else None, C.c_double)))
+        return out, anchor
+
+    def circuit_budget(self, n_bytes):
+        """bytes of solver rasters one batch of systems may take (0: the default, 4 GiB)"""
+        self._chk(self.lib.gnx_circuit_budget(self.h, C.c_int64(int(n_bytes))))
+
+    def circuit_info(self):
+        """of the last circuit_matrix / circuit_current / circuit_potentials:
+        dict(kernel_ms, launches, iterations, restarts, worst_residual)"""
+        ms, n, it, rs, w = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        self._chk(self.lib.gnx_circuit_info(self.h, C.byref(ms), C.byref(n), C.byref(it),
+                                            C.byref(rs), C.byref(w)))
+        return dict(kernel_ms=ms.value, launches=int(n.value), iterations=int(it.value),
+                    restarts=int(rs.value), worst_residual=w.value)
 
     # -- fine-scale spatial genetic structure (csrc/gnx_sgs.hip) ---------------------------
     def sgs_sums(self, edges, slots=None, locus_mask=None, locus_weight=None, perm=None,

@@ -377,6 +377,14 @@ struct gnx_state {
   double cost_ms = 0.0;
   int64_t cost_launches = 0, cost_rounds = 0, cost_batches = 0;
 
+  // circuit-theory resistances (gnx_circuit.hip): bytes of solver rasters one batch of systems
+  // may take (0: the default), and the kernel time, launches, CG iterations (summed over the
+  // batches), restarts and worst true residual of the last call
+  int64_t circ_budget = 0;
+  double circ_ms = 0.0;
+  int64_t circ_launches = 0, circ_iters = 0, circ_restarts = 0;
+  double circ_worst = 0.0;
+
   // admixture sweeps (gnx_admix.hip): the kernel time and launches of the last call, its chunks
   // over the individuals and the template instance (K) that ran
   double admix_ms = 0.0;

@@ -888,9 +888,11 @@ class Model:
         data/IBD_IBE_demo/MMRR.py, the last step of demos/_IBD_IBE.py): the genetic distances
         between the individuals (get_genetic_distances) regressed on the distances of the
         predictors - 'geo' (x, y), 'env' (the layers env_lyrs; default: the layers the Traits
-        are tied to, or all), 'phn' (the Traits trts; default: all) and 'cost' (least-cost
+        are tied to, or all), 'phn' (the Traits trts; default: all), 'cost' (least-cost
         distances as calc_cost_distances, or ('cost', dict(lyr=, kind=, barrier=, cost=, name=));
-        the key is the name, default 'cost') - with nperm row-and-column
+        the key is the name, default 'cost') and 'circuit' (resistance distances as
+        calc_resistance_distances, or ('circuit', dict(...)) with the options of 'cost' and tol=,
+        max_iter=; default name 'circuit') - with nperm row-and-column
         permutations of the genetic matrix, computed on the device.  individs, or a random
         sample of n, and loci restrict the analysis; at most 8192 individuals.  seed: the
         permutations of np.random.seed(seed) followed by the reference's shuffles (default: the
@@ -905,7 +907,7 @@ class Model:
     def run_mantel(self, x='geo', given=None, spp=0, env_lyrs=None, trts=None, individs=None,
                    n=None, loci=None, nperm=999, seed=None):
         """Mantel test of the genetic distances against the distances of predictor x ('geo',
-        'env', 'phn' or 'cost', as run_mmrr), or the partial test given another predictor (reference
+        'env', 'phn', 'cost' or 'circuit', as run_mmrr), or the partial test given another predictor (reference
         data/IBD_IBE_demo/run_mantel.R: vegan's mantel.partial(gen, env, geo), the genetic
         matrix permuted), computed on the device.
         -> dict(r, p = (1 + #{r_perm >= r}) / (nperm + 1), nperm, perm_r [nperm])"""
@@ -938,6 +940,44 @@ class Model:
         calc_cost_distances describes -> float64 [k][H][W] (inf: not reachable)"""
         spp = self.comm[self._get_spp_num(spp)]
         return spp._calc_cost_surface(x, y, lyr=lyr, kind=kind, barrier=barrier, cost=cost)
+
+    def calc_resistance_distances(self, spp=0, lyr=None, kind='conductance', barrier=None,
+                                  cost=None, individs=None, n=None, tol=None, max_iter=None):
+        """circuit-theory resistance distances between the living individuals (an extension:
+        isolation by resistance in McRae's sense; sim/circuit.py states the definition): the
+        effective resistance between the individuals' cells when the raster is read as a
+        resistor network - the graph, R and lyr / kind / barrier / cost of calc_cost_distances,
+        an edge between cells u, v being a resistor of 0.5 (R[u] + R[v]) times its length - so
+        that every additional route lowers the distance.  One linear system per distinct cell,
+        solved on the device by conjugate gradients to the relative residual tol (default
+        1e-10) within max_iter iterations (default: twice the cells of the largest connected
+        component).  individs, or a random sample of n, as run_mmrr; at most 8192 individuals.
+        Two on one cell are at 0; inf: different components, or an impassable cell
+        -> dict(ids, cells [n][2], dist float64 [n][n], info: the solver's kernel_ms, launches,
+        iterations, restarts, worst_residual)"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_resistance_distances(lyr=lyr, kind=kind, barrier=barrier, cost=cost,
+                                              individs=self._test_sample(spp, individs, n),
+                                              tol=tol, max_iter=max_iter)
+
+    def calc_current_map(self, x=None, y=None, spp=0, individs=None, n=None, lyr=None,
+                         kind='conductance', barrier=None, cost=None, tol=None, max_iter=None):
+        """the cumulative current map of circuit theory (corridors and pinch points): one
+        ampere is sent between every unordered pair of the distinct cells of the points (x, y)
+        - or of the individuals individs, or of a random sample of n, or of everyone - over the
+        resistor network calc_resistance_distances describes, and the currents through every
+        cell are added up (Circuitscape's node current: the two ends of a pair carry 1).  At
+        most 128 distinct cells per call: the work is pairs x cells x 8 edges.  Pairs in
+        different components or with an impassable cell are skipped and counted
+        -> dict(current float64 [H][W] (0 on impassable cells), cells (y * W + x), n_pairs,
+        n_skipped)"""
+        spp = self.comm[self._get_spp_num(spp)]
+        if x is None and y is None:
+            individs = self._test_sample(spp, individs, n)
+        elif n is not None:
+            raise ValueError('calc_current_map: points (x, y) or a sample of n, not both')
+        return spp._calc_current_map(x=x, y=y, individs=individs, lyr=lyr, kind=kind,
+                                     barrier=barrier, cost=cost, tol=tol, max_iter=max_iter)
 
     def calc_spatial_structure(self, spp=0, edges=None, n_classes=10, max_dist=None,
                                individs=None, n=None, loci=None, nperm=0, seed=None,

@@ -11,16 +11,19 @@ from .. import _native as nat
 
 
 _COST_OPTS = ('lyr', 'kind', 'barrier', 'cost', 'name')
+# the matrix predictors (solved over the landscape's raster, not device columns) and their options
+_MATRIX_OPTS = {'cost': _COST_OPTS,
+                'circuit': ('lyr', 'kind', 'barrier', 'cost', 'tol', 'max_iter', 'name')}
 
 
 def _is_cost_spec(p):
     return (isinstance(p, (tuple, list)) and len(p) == 2 and isinstance(p[0], str)
-            and p[0] == 'cost' and isinstance(p[1], dict))
+            and p[0] in _MATRIX_OPTS and isinstance(p[1], dict))
 
 
 def _predictor_list(predictors):
-    """the predictors of a Mantel / MMRR request as a list: one name, or one ('cost', opts),
-    stands for itself"""
+    """the predictors of a Mantel / MMRR request as a list: one name, or one ('cost', opts) or
+    ('circuit', opts), stands for itself"""
     if isinstance(predictors, str) or _is_cost_spec(predictors):
         return [predictors]
     return list(predictors)
@@ -28,21 +31,23 @@ def _predictor_list(predictors):
 
 def _split_predictors(spp, who, predictors, env_lyrs, trts):
     """(names in the caller's order, the device columns of the column predictors in that order
-    (Species._dist_predictors), [(name, opts)] of the cost predictors in that order).  A cost
-    predictor is 'cost' (the defaults of calc_cost_distances) or ('cost', opts) with any of lyr,
-    kind, barrier, cost, name; its name is opts['name'], default 'cost'"""
+    (Species._dist_predictors), [(name, kind, opts)] of the matrix predictors in that order).  A
+    matrix predictor is 'cost' (the defaults of calc_cost_distances) or ('cost', opts) with any
+    of lyr, kind, barrier, cost, name, or 'circuit' (the defaults of calc_resistance_distances)
+    or ('circuit', opts) with those and tol, max_iter; its name is opts['name'], default its
+    kind"""
     names, col_names, costs = [], [], []
     for p in _predictor_list(predictors):
-        if isinstance(p, str) and p == 'cost':
-            p = ('cost', {})
+        if isinstance(p, str) and p in _MATRIX_OPTS:
+            p = (p, {})
         if _is_cost_spec(p):
-            opts = dict(p[1])
-            extra = sorted(set(opts) - set(_COST_OPTS))
+            what, opts = p[0], dict(p[1])
+            extra = sorted(set(opts) - set(_MATRIX_OPTS[what]))
             if extra:
-                raise ValueError("%s: a 'cost' predictor takes %s, not %s"
-                                 % (who, ', '.join(_COST_OPTS), ', '.join(extra)))
-            name = str(opts.pop('name', 'cost'))
-            costs.append((name, opts))
+                raise ValueError("%s: a '%s' predictor takes %s, not %s"
+                                 % (who, what, ', '.join(_MATRIX_OPTS[what]), ', '.join(extra)))
+            name = str(opts.pop('name', what))
+            costs.append((name, what, opts))
             names.append(name)
         else:
             col_names.append(p)
@@ -56,6 +61,15 @@ def _split_predictors(spp, who, predictors, env_lyrs, trts):
         raise ValueError('%s: at most 4 predictors and 8 columns (layers, traits, x, y) '
                          'together' % who)
     return names, cols, costs
+
+
+def _solver_opts(who, tol, max_iter):
+    """refuse a tolerance or an iteration limit the circuit solver cannot take"""
+    if tol is not None and not (np.isfinite(tol) and tol > 0):
+        raise ValueError('%s: tol: a positive relative residual (got %r)' % (who, tol))
+    if max_iter is not None and (isinstance(max_iter, bool) or int(max_iter) != max_iter
+                                 or max_iter < 1):
+        raise ValueError('%s: max_iter: at least 1 iteration (got %r)' % (who, max_iter))
 
 
 # -- the request checks the analyses share: functions of the Species like _split_predictors, not
@@ -405,7 +419,8 @@ class SpeciesAnalyses:
                     raise ValueError('%s: trts: Traits among %s' % (who, sorted(traits)))
                 cols.append([(nat.F_Z, t) for t in nums])
             else:
-                raise ValueError("%s: unknown predictor %r ('geo', 'env', 'phn' or 'cost')"
+                raise ValueError("%s: unknown predictor %r ('geo', 'env', 'phn', 'cost' or "
+                                 "'circuit')"
                                  % (who, name))
         if len(set(predictors)) != len(predictors):
             raise ValueError('%s: a predictor is listed twice' % who)
@@ -486,6 +501,78 @@ class SpeciesAnalyses:
         R = self._cost_raster(who, lyr=lyr, kind=kind, barrier=barrier, cost=cost)
         return self._dev.cost_surfaces(R, self._cost_res(), cy * int(W) + cx)
 
+    # -- circuit-theory resistances (sim/circuit.py; csrc/gnx_circuit.hip) -------------------
+    def _resistance_matrix_of_cells(self, R, cells, tol=None, max_iter=None):
+        """effective resistances [n][n] of individuals standing on cells [n][2] = (x, y): the
+        distinct cells' matrix from the device, expanded (two individuals on one cell: 0)"""
+        from ..sim import circuit as _circuit
+        cells = np.asarray(cells, np.int64).reshape(-1, 2)
+        lin = cells[:, 1] * int(self._land_dim[0]) + cells[:, 0]
+        uniq, inverse = np.unique(lin, return_inverse=True)
+        return _circuit.expand(self._dev.circuit_matrix(R, self._cost_res(), uniq, tol, max_iter),
+                               inverse)
+
+    def _calc_resistance_distances(self, lyr=None, kind='conductance', barrier=None, cost=None,
+                                   individs=None, tol=None, max_iter=None):
+        """pairwise effective resistances (circuit theory) between the cells of the living
+        individuals asked for (all by default; at most 8192) over the resistance raster of the
+        request, solved on the device
+        -> dict(ids ascending, cells [n][2], dist float64 [n][n], info: the solver's
+        kernel_ms, launches, iterations, restarts, worst_residual)"""
+        who = 'calc_resistance_distances'
+        ids, _ = self._geno_sample(individs)
+        if ids.size > 8192:
+            raise ValueError('%s: at most 8192 individuals per call (the distance matrix is '
+                             'n x n), got %d: sample them with n=... or individs=...'
+                             % (who, ids.size))
+        if ids.size < 1:
+            raise ValueError('%s: no individuals' % who)
+        _solver_opts(who, tol, max_iter)
+        R = self._cost_raster(who, lyr=lyr, kind=kind, barrier=barrier, cost=cost)
+        cells = self._get_cells(individs=ids)
+        dist = self._resistance_matrix_of_cells(R, cells, tol, max_iter)
+        return dict(ids=ids, cells=cells, dist=dist, info=self._dev.circuit_info())
+
+    def _calc_current_map(self, x=None, y=None, individs=None, lyr=None, kind='conductance',
+                          barrier=None, cost=None, tol=None, max_iter=None):
+        """the cumulative current map float64 [H][W] of all pairs of the distinct cells of k
+        points (x, y) in landscape coordinates, floored to cells as _calc_cost_surface does, or
+        of the cells of the living individuals asked for (all when neither is given).  At most
+        128 distinct cells: the work is pairs x cells x 8 edges
+        -> dict(current [H][W], cells [m] (y * W + x, ascending), n_pairs, n_skipped)"""
+        who = 'calc_current_map'
+        W, H = self._land_dim
+        if (x is None) != (y is None):
+            raise ValueError('%s: x and y, or neither' % who)
+        if x is not None:
+            if individs is not None:
+                raise ValueError('%s: points (x, y) or individs, not both' % who)
+            x = np.atleast_1d(np.asarray(x, np.float64)).ravel()
+            y = np.atleast_1d(np.asarray(y, np.float64)).ravel()
+            if x.size != y.size or x.size < 1:
+                raise ValueError('%s: as many x as y, at least one point' % who)
+            if not (np.isfinite(x).all() and np.isfinite(y).all()):
+                raise ValueError('%s: a point is not finite' % who)
+            cx, cy = np.floor(x).astype(np.int64), np.floor(y).astype(np.int64)
+            if (cx < 0).any() or (cx >= W).any() or (cy < 0).any() or (cy >= H).any():
+                raise ValueError('%s: a point lies outside the landscape (0 <= x < %d, '
+                                 '0 <= y < %d)' % (who, W, H))
+        else:
+            ids, _ = self._geno_sample(individs)
+            if ids.size < 1:
+                raise ValueError('%s: no individuals' % who)
+            cells = np.asarray(self._get_cells(individs=ids), np.int64).reshape(-1, 2)
+            cx, cy = cells[:, 0], cells[:, 1]
+        uniq = np.unique(cy * int(W) + cx)
+        if uniq.size > 128:
+            raise ValueError('%s: at most 128 distinct cells per call (the work is pairs x cells '
+                             'x 8 edges), got %d: sample them with n=... or individs=...'
+                             % (who, uniq.size))
+        _solver_opts(who, tol, max_iter)
+        R = self._cost_raster(who, lyr=lyr, kind=kind, barrier=barrier, cost=cost)
+        cur, used, skipped = self._dev.circuit_current(R, self._cost_res(), uniq, tol, max_iter)
+        return dict(current=cur, cells=uniq, n_pairs=used, n_skipped=skipped)
+
     def _dist_perm_sums(self, who, predictors, env_lyrs, trts, individs, loci, nperm, seed,
                         min_n):
         """(names, permuted cross-sums [nperm][K], moments) of a Mantel / MMRR request:
@@ -512,8 +599,14 @@ class SpeciesAnalyses:
         # the cost matrices of the sample (rows in id order, as slots), built beside the columns
         cells = self._get_cells(individs=ids)
         mats = []
-        for name, opts in costs:
-            D = self._cost_matrix_of_cells(self._cost_raster(who, **opts), cells)
+        for name, what, opts in costs:
+            if what == 'circuit':
+                opts = dict(opts)
+                tol, max_iter = opts.pop('tol', None), opts.pop('max_iter', None)
+                D = self._resistance_matrix_of_cells(self._cost_raster(who, **opts), cells, tol,
+                                                     max_iter)
+            else:
+                D = self._cost_matrix_of_cells(self._cost_raster(who, **opts), cells)
             n_inf = int(np.isinf(D[np.tril_indices(ids.size, -1)]).sum())
             if n_inf:
                 raise ValueError('%s: predictor %r: %d pairs of the sampled individuals are at '
@@ -524,7 +617,8 @@ class SpeciesAnalyses:
         sums, mom = self._dev.dist_perm_sums_mat(cols, np.stack(mats), _mmrr.invert_rows(rows),
                                                  slots, mask)
         # the library's order (columns, then matrices) back to the caller's
-        lib = [n for n in names if n not in dict(costs)] + [n for n, _ in costs]
+        mat_names = [c[0] for c in costs]
+        lib = [n for n in names if n not in mat_names] + mat_names
         o = [lib.index(n) for n in names]
         mom = dict(mom, sx=np.asarray(mom['sx'])[o], sxy=np.asarray(mom['sxy'])[o],
                    sxx=np.asarray(mom['sxx'])[np.ix_(o, o)])

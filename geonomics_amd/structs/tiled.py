@@ -60,6 +60,10 @@ _NOT_TILED = {
                             'is not implemented; run the model on one GPU',
     '_calc_cost_surface': 'calc_cost_surface with a Species tiled over several GPUs is '
                           'not implemented; run the model on one GPU',
+    '_calc_resistance_distances': 'calc_resistance_distances with a Species tiled over several '
+                                  'GPUs is not implemented; run the model on one GPU',
+    '_calc_current_map': 'calc_current_map with a Species tiled over several GPUs is '
+                         'not implemented; run the model on one GPU',
     # spatial genetic structure (pairs across a tile border: the border cells of the neighbours'
     # samples would have to be exchanged)
     '_calc_spatial_structure': 'calc_spatial_structure with a Species tiled over several '

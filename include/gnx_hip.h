@@ -784,6 +784,62 @@ int gnx_cost_budget(gnx_state* h, int64_t bytes);
 int gnx_cost_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* rounds,
                   int64_t* batches);
 
+/* ---- circuit-theory resistance distances and current maps (csrc/gnx_circuit.hip; the reference
+ *      has no such analysis) --------------------------------------------------------------------
+ * The graph is the one of the least-cost distances above (geonomics_amd/sim/circuit.py restates
+ * what follows with scipy's splu): R, res_x, res_y and cell = y * W + x as there; the edge between
+ * passable cells u, v is a resistor of w ohms, g = 1.0 / w its conductance in fp64, and
+ * L = diag(sum g) - G the Laplacian, component by component.
+ *   reff(s, t) = (e_s - e_t)' L+ (e_s - e_t)  for two passable cells of one connected component;
+ *   reff(s, s) = 0, also on an impassable cell; reff = +inf between components and from or to an
+ *   impassable cell.
+ * The first listed cell of every component is its anchor a; every other passable listed cell i
+ * is one system L x_i = e_i - e_a, solved from x = 0 by Jacobi-preconditioned conjugate gradients
+ * in fp64 (x_a = 0; only differences of x_i inside the component mean anything).  A system stops
+ * when the recurrence residual is at most tol sqrt(2) (sqrt(2) = the norm of the right-hand side;
+ * tol > 0, finite); then the true residual b - L x is recomputed, and a system above the
+ * threshold restarts from it, at most 3 times.  max_iter: the iterations one batch of systems may
+ * take in all (0: twice the passable cells of the largest component).  Running out of iterations
+ * or restarts is an error that names the system and its residual.  No floating-point atomics: a
+ * call repeated, or made under another gnx_circuit_budget, is bit-equal.
+ * Refused (return 1) by all five entry points, before any other check: ghost records (a tile).
+ * Refused before anything is launched: n outside 1..8192 (gnx_circuit_matrix) or 1..128 (the other
+ * two), a bad R entry, res or tol, max_iter < 0, a cell outside 0..H W - 1, a cell listed twice, a
+ * budget below one system's rasters.  Nothing of the handle changes.
+ * gnx_circuit_matrix: out double [n][n] (HOST), exactly symmetric with a zero diagonal,
+ *   reff(i, j) = (x_i[c_i] - x_j[c_i]) - (x_i[c_j] - x_j[c_j]) evaluated once for i < j.  The
+ *   systems are solved batch by batch under the budget; of a batch only x at the listed cells is
+ *   kept.                                                                                       */
+int gnx_circuit_matrix(gnx_state* h, const double* R /*[H][W]*/, double res_x, double res_y,
+                       int32_t n, const int32_t* cells /*distinct*/, double tol,
+                       int64_t max_iter, double* out /*[n][n]*/);
+/* gnx_circuit_current: out double [H][W] (HOST) = the sum over all unordered pairs (s, t) of
+ *   listed cells that share a component of the node current
+ *   c(u) = 0.5 (sum_k g_uk |v_u - v_k| + |b_u|), v = x_s - x_t, b = +1 at s, -1 at t, 0 elsewhere
+ *   (the source and the sink carry 1; a cell of a 1-wide corridor between them carries 1);
+ *   impassable cells hold 0.  counts[0] = the pairs used, counts[1] = the pairs skipped (across
+ *   components, or with an impassable cell).  The work is pairs x cells x 8 edges, hence at most
+ *   128 cells.  The potentials of all systems must be resident (H W 8 bytes each, beside the
+ *   4 H W 8 of one system's work): above the budget the call is refused with the bytes needed. */
+int gnx_circuit_current(gnx_state* h, const double* R /*[H][W]*/, double res_x, double res_y,
+                        int32_t n, const int32_t* cells /*distinct*/, double tol,
+                        int64_t max_iter, double* out /*[H][W]*/, int64_t* counts /*[2]*/);
+/* gnx_circuit_potentials: out double [n][H][W] (HOST) = x_i as the solver left it (all 0 for an
+ *   anchor and for an impassable cell); anchor int32 [n] = the index in cells of cell i's anchor
+ *   (i itself for an anchor, -1 for an impassable cell).  Resident as gnx_circuit_current.       */
+int gnx_circuit_potentials(gnx_state* h, const double* R /*[H][W]*/, double res_x, double res_y,
+                           int32_t n, const int32_t* cells /*distinct*/, double tol,
+                           int64_t max_iter, int32_t* anchor /*[n]*/, double* out /*[n][H][W]*/);
+/* bytes of solver rasters one batch of systems may take (5 rasters of H W 8 bytes per system:
+ * x, r, two p, L p); more systems are worked off batch by batch (0: the default, 4 GiB).
+ * Negative, or positive and below one system's rasters: an error                                */
+int gnx_circuit_budget(gnx_state* h, int64_t bytes);
+/* of the last gnx_circuit_matrix / current / potentials: its kernels' HIP-event time (ms), their
+ * number, the CG iterations summed over the batches, the restarts, and the worst true residual
+ * norm of a system; each may be NULL                                                            */
+int gnx_circuit_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* iterations,
+                     int64_t* restarts, double* worst_residual);
+
 /* ---- fine-scale spatial genetic structure (csrc/gnx_sgs.hip; the reference has no such
  *      analysis: its IBD demo, demos/_IBD_IBE.py, ends at MMRR on a sample) ----------------
  * The sums over the pairs of individuals closer than the largest distance class, from which mean
