@@ -538,7 +538,7 @@ extern "C" void gnx_destroy(gnx_state* h) {
                   h->off_parent, h->off_keys, h->off_start, h->keep_in, h->inj_a, h->inj_b,
                   h->mid_x, h->mid_y, h->p_death, h->d_cell, h->dead_in, h->nmax_bits, h->red,
                   h->sel_loci, h->path_sel, h->lat.areas, h->lat.cprime, h->spl_N.c, h->spl_P.c, h->bin_partials, h->nodes,
-                  h->K_over, h->blk_cnt, h->blk_off, h->cnt_dev, h->tickets, h->nmax2, h->fb[0], h->gp_rec, h->gp_z, h->gp_slots, h->tile_counts, h->rq_sorted, h->rq_k, h->gam_out, h->gam_slot, h->chk,
+                  h->K_over, h->blk_cnt, h->blk_off, h->cnt_dev, h->tickets, h->nmax2, h->fb[0], h->gp_rec, h->gp_z, h->gp_slots, h->rq_sorted, h->rq_k, h->gam_out, h->gam_slot, h->chk,
                   h->lin_tab, h->lin_bt};
   for (void* p : ptrs) (void)hipFree(p);
   for (int t = 0; t < GNX_MAX_TRAITS; ++t) {

@@ -506,19 +506,18 @@ struct gnx_state {
   bool st_has_geno = false;
   int64_t birth_first_slot = 0;
   int64_t n_req = 0;
-  // device-resident transport: the staged selection grouped by destination rank
+  // tile2 routing (gnx_tile2_route_finish): this step's emigrants grouped by destination rank
   gnx_ind_rec* gp_rec = nullptr;
   float* gp_z = nullptr;
   int64_t* gp_slots = nullptr;
-  int64_t gp_n = 0, gp_cap = 0;
-  int32_t* tile_counts = nullptr;    // [GNX_MAX_TILES] per-destination counts
-  void* rq_sorted = nullptr;         // gnx_gamete_req [n_req] grouped by owner rank
+  int64_t gp_cap = 0;
+  void* rq_sorted = nullptr;         // gnx_gamete_req2 [n_req] grouped by owner rank
   int32_t* rq_k = nullptr;           // child index of each grouped request
   int64_t rq_cap = 0;
   uint64_t* gam_out = nullptr;       // gametes cut for other tiles
   int32_t* gam_slot = nullptr;
   int64_t gam_cap = 0;
-  int64_t* chk = nullptr;            // [2] device-side record check: bad count, max id
+  int64_t* chk = nullptr;            // [2] deferred checks: records off the landscape, bad gamete requests
   // tile2 protocol (gnx_tile.hip, "device-driven"): emigrants stay in their slots until the
   // cell sort, which gives them a key behind every cell (tile_evict individuals) and the
   // population shrinks by that many; gamete requests are counted with the pairs, so the
@@ -534,7 +533,6 @@ struct gnx_state {
   int32_t* h_route_pin = nullptr;    // pinned host words of the tile2 read-backs
   int32_t* h_route_pin_dev = nullptr;
   std::vector<int64_t> req_by_rank;  // gamete requests per owning rank (gnx_tile2_pairs)
-  bool rq_is2 = false;               // rq_sorted holds 24-byte gnx_gamete_req2 records
   bool tile_req_on_device = false;   // gnx_tile2_pairs leaves the request counts in route_cnt (no wait)
   bool tile2_mode = false;           // the handle steps through the tile2 protocol (set by its entry points)
   bool req_cnt_zeroed = false;       // the request counters were cleared by k_tile2_zero

@@ -224,52 +224,6 @@ class Comm:
         self.dist.all_gather(out, buf)
         return [o[:k].cpu().numpy() for o, k in zip(out, ns)]
 
-    # -- device-resident transport (backend nccl = RCCL) -----------------------------
-    def count_matrix(self, counts):
-        """every rank's per-destination counts -> int64 [src][dst] on the host"""
-        import torch
-        c = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).to(self.device)
-        out = [torch.zeros_like(c) for _ in range(self.world)]
-        self.dist.all_gather(out, c)
-        return torch.stack(out).cpu().numpy()
-
-    def exchange_dev(self, parts, mat):
-        """parts: [(uint8 device tensor grouped by destination rank, bytes per
-        element)]; mat[src][dst] = element counts.  One batch of isend/irecv for
-        all parts; returns the received tensors, grouped by source rank."""
-        import torch
-        me = self.rank
-        soff = np.concatenate([[0], np.cumsum(mat[me])])
-        roff = np.concatenate([[0], np.cumsum(mat[:, me])])
-        ops, recv = [], []
-        for t, unit in parts:
-            r = torch.empty(int(roff[-1]) * unit, dtype=torch.uint8, device=t.device)
-            recv.append(r)
-            for peer in range(self.world):
-                if peer == me:
-                    if mat[me, me]:
-                        r[roff[me] * unit:roff[me + 1] * unit] = \
-                            t[soff[me] * unit:soff[me + 1] * unit]
-                    continue
-                if mat[me, peer]:
-                    ops.append(self.dist.P2POp(
-                        self.dist.isend, t[soff[peer] * unit:soff[peer + 1] * unit], peer))
-                if mat[peer, me]:
-                    ops.append(self.dist.P2POp(
-                        self.dist.irecv, r[roff[peer] * unit:roff[peer + 1] * unit], peer))
-        if ops:
-            for req in self.dist.batch_isend_irecv(ops):
-                req.wait()
-        # the library reads these buffers from its own stream
-        torch.cuda.current_stream().synchronize()
-        return recv
-
-    def allreduce_dev_(self, t):
-        import torch
-        self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
-        torch.cuda.current_stream().synchronize()
-        return t
-
     # -- tile2: nothing here blocks the host except the count all-gathers -----------------
     def host_allgather(self, a):
         """every rank's int64 vector (same length everywhere) -> int64 [world][len] on the
@@ -294,9 +248,11 @@ class Comm:
         return getattr(self, '_hgrp', None)
 
     def exchange_multi(self, groups):
-        """groups: [(parts, mat)] as for exchange_dev, all in ONE batch of isend / irecv and
-        without a host synchronisation: the received tensors are valid for work enqueued on
-        the current stream (req.wait() orders the stream behind RCCL, it does not block)."""
+        """groups: [(parts, mat)]; parts: [(uint8 device tensor grouped by destination rank,
+        bytes per element)], mat[src][dst] = element counts.  All in ONE batch of isend / irecv
+        and without a host synchronisation; returns per group the received tensors, grouped by
+        source rank: they are valid for work enqueued on the current stream (req.wait() orders
+        the stream behind RCCL, it does not block)."""
         import torch
         me = self.rank
         ops, out = [], []
@@ -491,8 +447,8 @@ class TiledStepper:
         self._t0 = 0.0
         # the device-driven protocol (tile2, include/gnx_hip.h): the HIP shard with a
         # transport that moves device memory, or a single tile
-        self.v2 = (hasattr(shard, 'dev') and os.environ.get('GNX_TILE_V2', '1') != '0' and
-                   (comm.world == 1 or self.dev_transport) and not self.panmixia)
+        self.v2 = (hasattr(shard, 'dev') and (comm.world == 1 or self.dev_transport) and
+                   not self.panmixia)
         # One C call per step, the exchanges issued by the library itself on its own stream
         # (gnx_tile_step, csrc/gnx_comm.hip: grouped ncclSend / ncclRecv, KB-sized collectives,
         # no torch.distributed call and no Python between the phases of a step); with a per-step
@@ -513,7 +469,6 @@ class TiledStepper:
         if self.v2 and use_library:
             self.v3 = self._join_library_comm()
         self._ext = None           # the library's stream as a torch stream
-        self._evcache = os.environ.get('GNX_TILE_EVCACHE', '1') != '0'
         self._keep = []            # tensors the library reads until the end of the step
         self._n_start = None       # global population at the start of the coming step
         self._pre = None           # global population before the last step's deaths
@@ -607,101 +562,7 @@ class TiledStepper:
                 _cat(zs, np.float32, (nt,)) if nt else None,
                 _cat(gs, np.uint64, (2, W64)) if geno is not None else None)
 
-    # -- device-resident exchanges (see csrc/gnx_tile.hip, "Device-resident transport")
-    def _migrate_dev(self):
-        dev = self.shard.dev
-        geno = self.shard.has_genomes
-        nt, W64 = self.shard.n_traits, self.shard.W64
-        counts, (p_rec, p_z, p_g) = dev.tile_export_migrants_dev()
-        self._tick('  mig export')
-        assert counts[self.comm.rank] == 0
-        mat = self.comm.count_matrix(counts)
-        self._tick('  mig counts')
-        n = int(counts.sum())
-        parts = [(dev_bytes(p_rec, n * 32), 32)]
-        if nt:
-            parts.append((dev_bytes(p_z, n * 4 * nt), 4 * nt))
-        if geno:
-            parts.append((dev_bytes(p_g, n * 16 * W64), 16 * W64))
-        self.bytes_sent += sum(t.numel() for t, _ in parts)
-        got = self.comm.exchange_dev(parts, mat)
-        self._tick('  mig exchange')
-        m = int(mat[:, self.comm.rank].sum())
-        if m:
-            dev.tile_import_dev(m, got[0].data_ptr(), got[1].data_ptr() if nt else 0,
-                                got[-1].data_ptr() if geno else 0)
-        self._tick('  mig import')
-
-    def _halo_dev(self):
-        dev = self.shard.dev
-        counts, p_rec = dev.tile_export_halo_dev()
-        self._tick('  halo export')
-        mat = self.comm.count_matrix(counts)
-        n = int(counts.sum())
-        self.bytes_sent += n * 32
-        got = self.comm.exchange_dev([(dev_bytes(p_rec, n * 32), 32)], mat)
-        self._tick('  halo exchange')
-        m = int(mat[:, self.comm.rank].sum())
-        if m:
-            dev.tile_import_ghosts_dev(m, got[0].data_ptr())
-        self._tick('  halo import')
-
-    def _offspring_dev(self, burn):
-        """pair order on the device: all-gather the pairs' order keys (hash cell << 40 |
-        focal id, ascending on every tile), searchsorted, and hand the offsets to the
-        library without leaving GPU memory"""
-        import torch
-        dev = self.shard.dev
-        P, p_ids, p_nb = dev.tile_pair_ptrs()
-        mine = dev_bytes(p_ids, P * 8).view(torch.int64)
-        all_ids = self.comm.allgather_var(mine)
-        fixed = self.fixed_births
-        all_nb = None
-        if not fixed:
-            nb = dev_bytes(p_nb, P * 4).view(torch.int32).to(torch.int64) if P else mine
-            all_nb = self.comm.allgather_var(nb)
-        goff = torch.zeros(P, dtype=torch.int64, device=mine.device)
-        total_births = total_pairs = 0
-        for r in range(self.comm.world):
-            li = all_ids[r]
-            if fixed:
-                if P:
-                    goff += torch.searchsorted(li, mine) * int(fixed)
-                total_births += int(fixed) * li.numel()
-            else:
-                cum = torch.zeros(li.numel() + 1, dtype=torch.int64, device=mine.device)
-                if li.numel():
-                    cum[1:] = torch.cumsum(all_nb[r], 0)
-                if P:
-                    goff += cum[torch.searchsorted(li, mine)]
-                total_births += int(cum[-1].item())
-            total_pairs += li.numel()
-        torch.cuda.current_stream().synchronize()
-        n_req = dev.tile_offspring_dev(burn, self.max_id + 1, goff.data_ptr() if P else 0)
-        return n_req, total_births, total_pairs
-
-    def _gametes_dev(self):
-        dev = self.shard.dev
-        W64 = self.shard.W64
-        counts, p_req = dev.tile_group_requests()
-        mat = self.comm.count_matrix(counts)
-        n = int(counts.sum())
-        got = self.comm.exchange_dev([(dev_bytes(p_req, n * 16), 16)], mat)
-        m = int(mat[:, self.comm.rank].sum())
-        p_out = dev.tile_serve_gametes_dev(m, got[0].data_ptr() if m else 0)
-        self.bytes_sent += m * 8 * W64
-        back = self.comm.exchange_dev([(dev_bytes(p_out, m * 8 * W64), 8 * W64)], mat.T.copy())
-        if n:
-            dev.tile_put_gametes_dev(n, back[0].data_ptr())
-
-    def _bins_dev(self):
-        import torch
-        ptr, n = self.shard.dev.tile_bins_ptr()
-        self.comm.allreduce_dev_(dev_bytes(ptr, n * 4).view(torch.int32))
-
     def _migrate(self):
-        if self.dev_transport:
-            return self._migrate_dev()
         rec, z, geno = self.shard.export_migrants()
         dest = self.rank_of(rec['x'], rec['y']) if rec.size else np.zeros(0, np.int64)
         if self.comm.world == 1:
@@ -715,8 +576,6 @@ class TiledStepper:
     def _halo(self):
         if self.comm.world == 1:
             return
-        if self.dev_transport:
-            return self._halo_dev()
         rec = self.shard.export_halo()
         w = self.comm.world
         send = [np.zeros(0, np.uint8)] * w
@@ -837,6 +696,17 @@ class TiledStepper:
         self._t0 = now
 
     # -- tile2: one time step, three host waits -----------------------------------------
+    def _lib_stream(self):
+        """the library's stream as a torch stream, with one event per direction, recorded again
+        at every hand-over (Stream.wait_stream makes a new event each time, 30 us of host time
+        a call and ten calls a step)"""
+        import torch
+        if self._ext is None:
+            self._ext = torch.cuda.ExternalStream(self.shard.dev.stream_ptr())
+            self._ev_l2t = torch.cuda.Event()
+            self._ev_t2l = torch.cuda.Event()
+        return self._ext
+
     def _lib_to_torch(self):
         """collectives enqueued from here on see what the library has enqueued so far: a
         stream dependency under RCCL; a transport that reads device memory from the host
@@ -845,17 +715,9 @@ class TiledStepper:
         if not getattr(self.comm, 'stream_ordered', True):
             self.shard.dev.synchronize()
             return
-        # (one event per direction, recorded again at every hand-over: Stream.wait_stream makes
-        # a new event each time, 30 us of host time a call and ten calls a step)
-        if self._ext is None:
-            self._ext = torch.cuda.ExternalStream(self.shard.dev.stream_ptr())
-            self._ev_l2t = torch.cuda.Event()
-            self._ev_t2l = torch.cuda.Event()
-        if self._evcache:
-            self._ev_l2t.record(self._ext)
-            torch.cuda.current_stream().wait_event(self._ev_l2t)
-        else:
-            torch.cuda.current_stream().wait_stream(self._ext)
+        ext = self._lib_stream()
+        self._ev_l2t.record(ext)
+        torch.cuda.current_stream().wait_event(self._ev_l2t)
 
     def _torch_to_lib(self):
         """library work enqueued from here on sees what torch / RCCL have enqueued so far"""
@@ -863,15 +725,9 @@ class TiledStepper:
         if not getattr(self.comm, 'stream_ordered', True):
             torch.cuda.current_stream().synchronize()
             return
-        if self._ext is None:
-            self._ext = torch.cuda.ExternalStream(self.shard.dev.stream_ptr())
-            self._ev_l2t = torch.cuda.Event()
-            self._ev_t2l = torch.cuda.Event()
-        if self._evcache:
-            self._ev_t2l.record(torch.cuda.current_stream())
-            self._ext.wait_event(self._ev_t2l)
-        else:
-            self._ext.wait_stream(torch.cuda.current_stream())
+        ext = self._lib_stream()
+        self._ev_t2l.record(torch.cuda.current_stream())
+        ext.wait_event(self._ev_t2l)
 
     def _step_v2(self, burn, with_selection, after_births, exact):
         import torch
@@ -1083,12 +939,7 @@ class TiledStepper:
             total_births, total_pairs = int(vt[:64].sum()), int(vt[64])
             if self.comm.world > 1:
                 sh.dev.tile2_vt_bases(np.concatenate([[0], np.cumsum(vt[:64])[:-1]]))
-            if self.dev_transport:
-                n_req = sh.dev.tile_offspring_dev(burn, self.max_id + 1, 0)
-            else:
-                n_req = sh.offspring(burn, self.max_id + 1, None)
-        elif self.dev_transport:
-            n_req, total_births, total_pairs = self._offspring_dev(burn)
+            n_req = sh.offspring(burn, self.max_id + 1, None)
         else:
             goff, total_births, total_pairs = self._pair_offsets()
             self._tick('pair order')
@@ -1097,22 +948,16 @@ class TiledStepper:
         sh.set_max_id(self.max_id)
         self._tick('offspring+crossover')
         if not burn and sh.has_genomes:
-            if self.dev_transport:
-                self._gametes_dev()
-            else:
-                self._gametes(n_req)
+            self._gametes(n_req)
         self._tick('gametes')
         sh.finish_births(burn)
         if after_births is not None and total_births > 0:
             after_births(self.max_id - total_births + 1, total_births)
         # one all-reduce for both density fields (individuals, pair midpoints)
-        if self.dev_transport:
-            self._bins_dev()
-        else:
-            b0, b1 = sh.get_bins(0), sh.get_bins(1)
-            both = self.comm.allreduce_sum(np.concatenate([b0, b1]))
-            sh.set_bins(0, both[:b0.size])
-            sh.set_bins(1, both[b0.size:])
+        b0, b1 = sh.get_bins(0), sh.get_bins(1)
+        both = self.comm.allreduce_sum(np.concatenate([b0, b1]))
+        sh.set_bins(0, both[:b0.size])
+        sh.set_bins(1, both[b0.size:])
         self._tick('phenotype + bins')
         sh.die(burn, with_selection, total_pairs > 0)
         sh.advance_step()

@@ -403,41 +403,6 @@ int gnx_tile_finish_births(gnx_state* h, int32_t burn);
 int gnx_tile_die(gnx_state* h, int32_t burn, int32_t with_selection, int32_t have_pairs);
 int gnx_set_max_id(gnx_state* h, int64_t max_id);
 
-/* Device-resident transport: RCCL moves GPU memory, so under the "nccl" backend
- * the payloads never visit the host.  The *_dev entry points group the staged
- * selection by destination rank ON the device, return per-rank counts
- * (counts[R*C], the only thing that crosses PCIe) and DEVICE addresses that the
- * host layer wraps in tensors for isend/irecv; imports read the buffers RCCL
- * filled.  Returned addresses belong to the handle and stay valid until the
- * next tile call; every call returns with the handle's stream idle.          */
-typedef struct {
-  int64_t parent_id;
-  int32_t key;      /* recombination path */
-  int32_t start;    /* starting homologue, 0 / 1 */
-} gnx_gamete_req;
-
-int gnx_tile_export_migrants_dev(gnx_state* h, int64_t* counts /*[R*C]*/);
-int gnx_tile_export_halo_dev(gnx_state* h, int64_t* counts /*[R*C]*/);
-/* grouped selection: rec gnx_ind_rec[n], z float[n][n_traits], geno u64[n][2][W64] */
-int gnx_tile_staged_ptrs(gnx_state* h, void** rec, void** z, void** geno);
-int gnx_tile_import_dev(gnx_state* h, int64_t n, const void* rec, const void* z,
-                        const void* geno);
-int gnx_tile_import_ghosts_dev(gnx_state* h, int64_t n, const void* rec);
-/* order keys (cell << 40 | focal id) int64[P] ascending; n_births int32[P] or NULL    */
-int gnx_tile_pair_ptrs(gnx_state* h, int64_t* n_pairs, void** focal_ids, void** n_births);
-/* the same without waiting for the handle's stream (tile2)                             */
-int gnx_tile_pair_ptrs_nosync(gnx_state* h, int64_t* n_pairs, void** focal_ids, void** n_births);
-int gnx_tile_offspring_dev(gnx_state* h, int32_t burn, int64_t id_base,
-                           const void* pair_goff_dev /*int64[P]*/, int64_t* n_requests);
-/* this step's gamete requests grouped by owner rank: gnx_gamete_req[n_requests] */
-int gnx_tile_group_requests(gnx_state* h, int64_t* counts /*[R*C]*/, void** req_dev);
-int gnx_tile_serve_gametes_dev(gnx_state* h, int64_t n, const void* req_dev,
-                               void** out_dev /*u64[n][W64]*/);
-/* answers in the grouped request order                                         */
-int gnx_tile_put_gametes_dev(gnx_state* h, int64_t n, const void* data_dev);
-/* int32 [2][bin_count]: individuals, pair midpoints (all-reduce in place)     */
-int gnx_tile_bins_ptr(gnx_state* h, void** bins, int64_t* n_total);
-
 /* ---- the device-driven tile protocol ("tile2"): the host waits for the device three
  * times per step - for the routing counts, for the pair / request counts and for the
  * survivor count - and every payload stays in device memory.  Entry points marked (no
@@ -504,6 +469,9 @@ int gnx_tile2_import(gnx_state* h, int64_t n_mig, const void* rec, const void* z
  * list, births.  counts[2 + R*C] = pairs, births, gamete requests per owning rank.  One
  * wait (two more with Poisson-distributed births).                                      */
 int gnx_tile2_pairs(gnx_state* h, int32_t burn, int64_t* counts);
+/* the local pair list in device memory: order keys (cell << 40 | focal id) int64[P] ascending;
+ * n_births int32[P], or NULL when every pair has the fixed number of births; (no wait)      */
+int gnx_tile_pair_ptrs_nosync(gnx_state* h, int64_t* n_pairs, void** focal_ids, void** n_births);
 /* offspring; *req_dev = gnx_gamete_req2[] grouped by owning rank as counted by
  * gnx_tile2_pairs; (no wait)                                                             */
 int gnx_tile2_offspring(gnx_state* h, int32_t burn, int64_t id_base,

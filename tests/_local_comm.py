@@ -66,16 +66,13 @@ class LocalComm:
     def allgather_i64(self, a):
         return [x.copy() for x in self._swap(np.ascontiguousarray(a, dtype=np.int64))]
 
-    def count_matrix(self, counts):
-        return np.stack(self._swap(np.asarray(counts, dtype=np.int64).copy()))
-
     # device-side
     def allgather_var(self, t):
         out = [x.clone() for x in self._swap(t)]
         self._done()
         return out
 
-    def allreduce_dev_(self, t):
+    def allreduce_async_(self, t):
         import torch
         posted = self._swap(t)
         total = torch.stack([p.clone() for p in posted]).sum(0).to(t.dtype)
@@ -115,6 +112,3 @@ class LocalComm:
 
     def allgather_known(self, t, ns):
         return self.allgather_var(t)
-
-    def allreduce_async_(self, t):
-        return self.allreduce_dev_(t)

@@ -450,17 +450,20 @@ def test_nccl_backend_world1_wraps_library_memory():
         sh, dev = make_device_shard(config())
         dev.tile_set(1, 1, 0, 0)
         dev.tile_pairs(True)
-        sh.finish_births(True)
-        ptr, n = dev.tile_bins_ptr()
+        # (both bin fields, then the step's four counter words; enqueued, not waited for)
+        ptr, n_words = dev.tile2_finish_births(True)
+        dev.synchronize()
         before = np.concatenate([dev.get_bins(0), dev.get_bins(1)])
-        t = dev_bytes(ptr, n * 4).view(torch.int32)
-        np.testing.assert_array_equal(t.cpu().numpy(), before)
-        comm.allreduce_dev_(t)                       # sum over 1 rank: unchanged, in place
+        n = before.size
+        assert n_words == n + 4
+        t = dev_bytes(ptr, n_words * 4).view(torch.int32)
+        np.testing.assert_array_equal(t[:n].cpu().numpy(), before)
+        comm.allreduce_async_(t)                     # sum over 1 rank: unchanged, in place
+        torch.cuda.current_stream().synchronize()
         np.testing.assert_array_equal(np.concatenate([dev.get_bins(0), dev.get_bins(1)]), before)
         assert before[:n // 2].sum() == dev.N
-        mat = comm.count_matrix(np.array([0]))
-        assert mat.tolist() == [[0]]
-        P, p_ids, _ = dev.tile_pair_ptrs()
+        dev.synchronize()       # (the getter does not wait: the keys are read from an idle stream)
+        P, p_ids, _ = dev.tile_pair_ptrs_nosync()
         ids = comm.allgather_var(dev_bytes(p_ids, P * 8).view(torch.int64))[0]
         np.testing.assert_array_equal(ids.cpu().numpy(), dev.tile_pair_info()[0])
         dev.close()
