@@ -66,6 +66,7 @@ EXPORTS = [
     'gnx_stats_group_counts', 'gnx_sgs_sums',
     'gnx_ld_bins', 'gnx_ld_budget', 'gnx_ld_info',
     'gnx_tracts_self', 'gnx_tracts_pairs', 'gnx_tracts_info',
+    'gnx_kin_matrix', 'gnx_kin_pairs', 'gnx_kin_info',
     'gnx_dist_perm_sums_mat',
     'gnx_cost_surfaces', 'gnx_cost_matrix', 'gnx_cost_budget', 'gnx_cost_info',
     'gnx_admix_sweep', 'gnx_admix_info',
@@ -1423,6 +1424,72 @@ class Device:
         ms, n, nb = C.c_double(), C.c_int64(), C.c_int64()
         self._chk(self.lib.gnx_tracts_info(self.h, C.byref(ms), C.byref(n), C.byref(nb)))
         return dict(kernel_ms=ms.value, launches=int(n.value), bytes_read=int(nb.value))
+
+    # -- close-kin pairs (csrc/gnx_kin.hip) ---------------------------------------------------
+    def kin_matrix(self, slots=None, locus_mask=None):
+        """the integers of KING-robust kinship for every two of `slots` (at most 8192;
+        include/gnx_hip.h, gnx_kin_matrix)
+        -> dict(nhet int32 [n], hh int32 [n][n], ibs0 int32 [n][n])"""
+        s, n = self._geno_slots(slots)
+        m = self._locus_mask_words(locus_mask)
+        # (the library refuses n outside 1..8192 before it writes: no n x n buffer for that)
+        k = n if 1 <= n <= 8192 else 0
+        nhet = np.zeros(max(k, 1), np.int32)
+        hh = np.zeros((k, k), np.int32)
+        ib = np.zeros((k, k), np.int32)
+        self._chk(self.lib.gnx_kin_matrix(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64),
+            _ptr(nhet, C.c_int32), _ptr(hh if k else None, C.c_int32),
+            _ptr(ib if k else None, C.c_int32)))
+        return dict(nhet=nhet[:k], hh=hh, ibs0=ib)
+
+    def kin_pairs(self, T, max_dist=None, slots=None, locus_mask=None, max_pairs=1 << 22,
+                  max_work=0, out=None):
+        """the pairs of `slots` (all living slots by default) closer than max_dist (None: every
+        pair) that the integer rule keeps at threshold T = sim/kin.threshold(min_kinship)
+        (include/gnx_hip.h, gnx_kin_pairs), sorted by (pa, pb).  max_work <= 0: only the work is
+        computed.  out: (pa, pb, hh, ibs0 int32 [max_pairs], nhet int32 [n]) to write into.
+        More kept pairs than max_pairs: GnxError with the attribute n_found
+        -> dict(work, n_candidates, n_found, pa, pb, hh, ibs0 int32 [n_found], nhet int32 [n]);
+        all but work are None when max_work <= 0"""
+        s, n = self._geno_slots(slots)
+        m = self._locus_mask_words(locus_mask)
+        max_pairs = int(max_pairs)
+        run = max_work > 0 and 1 <= n <= 2 ** 24 and 1 <= max_pairs <= 2 ** 26
+        if out is None:
+            k = max_pairs if run else 1
+            out = tuple(np.empty(k, np.int32) for _ in range(4)) + \
+                (np.zeros(n if run else 1, np.int32),)
+        pa, pb, hh, ib, nhet = out
+        for a, size in ((pa, max_pairs), (pb, max_pairs), (hh, max_pairs), (ib, max_pairs),
+                        (nhet, n)):
+            if run and (a.dtype != np.int32 or a.size < size or not a.flags.c_contiguous):
+                raise ValueError('out: contiguous int32 arrays of max_pairs (nhet: n) entries')
+        work, nc, nf = (np.zeros(1, np.int64) for _ in range(3))
+        try:
+            self._chk(self.lib.gnx_kin_pairs(
+                self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64),
+                C.c_double(0.0 if max_dist is None else float(max_dist)), C.c_int64(int(T)),
+                C.c_int64(max_pairs), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
+                _ptr(nc, C.c_int64), _ptr(nf, C.c_int64), _ptr(pa, C.c_int32),
+                _ptr(pb, C.c_int32), _ptr(hh, C.c_int32), _ptr(ib, C.c_int32),
+                _ptr(nhet, C.c_int32)))
+        except GnxError as err:
+            if 'exceed max_pairs' in str(err):
+                err.n_found = int(nf[0])
+            raise
+        if max_work <= 0:
+            return dict(work=int(work[0]), n_candidates=None, n_found=None, pa=None, pb=None,
+                        hh=None, ibs0=None, nhet=None)
+        k = int(nf[0])
+        return dict(work=int(work[0]), n_candidates=int(nc[0]), n_found=k, pa=pa[:k].copy(),
+                    pb=pb[:k].copy(), hh=hh[:k].copy(), ibs0=ib[:k].copy(), nhet=nhet[:n])
+
+    def kin_info(self):
+        """of the last kin_matrix / kin_pairs: dict(kernel_ms, launches, tasks)"""
+        ms, n, nt = C.c_double(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.gnx_kin_info(self.h, C.byref(ms), C.byref(n), C.byref(nt)))
+        return dict(kernel_ms=ms.value, launches=int(n.value), tasks=int(nt.value))
 
     # -- haplotype sweep scans (csrc/gnx_sweeps.hip) -------------------------------------------
     def sweeps_scan(self, loci, pos, brk=None, cls=None, cores=None, slots=None, min_minor=2,

@@ -366,6 +366,11 @@ struct gnx_state {
   double tr_ms = 0.0;
   int64_t tr_launches = 0, tr_bytes = 0;
 
+  // close-kin pairs (gnx_kin.hip): the kernel time and launches of the last call and its
+  // 64 x 64 tiles
+  double kin_ms = 0.0;
+  int64_t kin_launches = 0, kin_tasks = 0;
+
   // haplotype sweep scans (gnx_sweeps.hip): the kernel time and launches of the last call and
   // the completed steps summed over its scans
   double sw_ms = 0.0;

@@ -26,20 +26,12 @@
 // leaves one partial (its four waves added in wave order); k_sgs_total adds the partials in
 // workgroup order.  No atomics: every sum is taken in an order fixed by (n, cells, n_bins), so
 // the fp64 sums of a call repeated are bit-equal too.
-#include <cmath>
-#include "gnx_geno.h"
+#include "gnx_sgs.h"
 
 #define SGS_NB 32            // distance classes at most
 #define SGS_NI 3             // integer sums per class
 #define SGS_NF 7             // fp64 sums per class
 #define SGS_BLOCKS 1024      // workgroups of the pair kernel at most (one partial each)
-#define SGS_MAX_CELLS (1 << 22)
-
-// a 64 x 64 tile of pairs: rows a0 .. a0 + na - 1 against rows b0 .. b0 + nb - 1 of the sorted
-// sample (na, nb <= 64); a0 == b0 only for a diagonal tile of a cell with itself
-struct SgsTask {
-  int32_t a0, na, b0, nb;
-};
 
 // key[i] = the cell of sample index i, val[i] = i
 __global__ void k_sgs_cells(int64_t n, const int64_t* __restrict__ slots,
@@ -341,71 +333,20 @@ extern "C" int gnx_sgs_sums(gnx_state* h, int64_t n, const int64_t* slots,
   std::vector<u64> wmask;
   geno_words(h, locus_mask, widx, wmask);
   const int nw = (int)widx.size();
-  // the grid: a side a little above the largest edge (so that rounding in r or in the cell
-  // number cannot part two individuals closer than it by more than one cell), larger where
-  // the landscape would have more than SGS_MAX_CELLS cells
-  const double Wd = std::max(1, h->cfg.W), Hd = std::max(1, h->cfg.H);
-  double side = edges[n_bins] * (1.0 + 1e-6);
-  int64_t ncx, ncy;
-  for (;;) {
-    const double fx = std::ceil(Wd / side), fy = std::ceil(Hd / side);
-    if (fx * fy <= (double)SGS_MAX_CELLS) {
-      ncx = std::max<int64_t>(1, (int64_t)fx);
-      ncy = std::max<int64_t>(1, (int64_t)fy);
-      break;
-    }
-    side = std::max(side * 1.25, std::sqrt(Wd * Hd / (double)SGS_MAX_CELLS));
-  }
-  const int n_cells = (int)(ncx * ncy);
-  int bits = 1;
-  while ((1ll << bits) < n_cells) ++bits;
+  // the grid: its side is just above the largest edge
+  const SgsGrid grid = sgs_grid(h, edges[n_bins]);
 
   GnxScratch s(who);
   int32_t* d_rows = nullptr;
   int64_t* d_slots = nullptr;
   GNXCHK(geno_rows(h, who, n, slots, s, &d_rows, &d_slots));
   const GnxSoA a = h->soa[h->cur];
-  uint32_t *d_key = nullptr, *d_key2 = nullptr;
-  int32_t *d_val = nullptr, *d_order = nullptr, *d_start = nullptr, *d_perm = nullptr;
-  char* d_tmp = nullptr;
-  size_t tmp_bytes = 0;
-  GNXCHK(gnx_prim_sort_bytes((size_t)n, bits, &tmp_bytes));
-  GNXCHK(s.get(&d_key, (size_t)n));
-  GNXCHK(s.get(&d_key2, (size_t)n));
-  GNXCHK(s.get(&d_val, (size_t)n));
-  GNXCHK(s.get(&d_order, (size_t)n));
-  GNXCHK(s.get(&d_start, (size_t)n_cells + 1));
-  GNXCHK(s.get(&d_tmp, tmp_bytes));
-  hipLaunchKernelGGL(k_sgs_cells, dim3(gnx_grid(n, 256)), dim3(256), 0, h->stream, n, d_slots,
-                     a.x, a.y, side, (int)ncx, (int)ncy, d_key, d_val);
-  GNXCHK(gnx_prim_sort(d_tmp, tmp_bytes, d_key, d_key2, d_val, d_order, (size_t)n, bits,
-                       h->stream));
-  hipLaunchKernelGGL(k_sgs_cell_start, dim3(gnx_grid(n_cells + 1, 256)), dim3(256), 0, h->stream,
-                     n, n_cells, d_key2, d_start);
-  HIPCHK(hipGetLastError());
-  std::vector<int32_t> start((size_t)n_cells + 1);
-  GNXCHK(gnx_d2h(h, start.data(), d_start, start.size() * sizeof(int32_t)));
+  int32_t *d_order = nullptr, *d_perm = nullptr;
+  std::vector<int32_t> start;
+  GNXCHK(sgs_sort_cells(h, s, grid, n, d_slots, &d_order, start));
   // the candidate pairs: a cell with itself and with its four forward neighbours
-  static const int FWD[4][2] = {{1, 0}, {-1, 1}, {0, 1}, {1, 1}};
-  auto count_of = [&](int64_t cxi, int64_t cyi) -> int64_t {
-    if (cxi < 0 || cxi >= ncx || cyi >= ncy) return 0;
-    const int64_t c = cyi * ncx + cxi;
-    return start[c + 1] - start[c];
-  };
   int64_t cand = 0, n_tasks = 0;
-  for (int64_t cyi = 0; cyi < ncy; ++cyi)
-    for (int64_t cxi = 0; cxi < ncx; ++cxi) {
-      const int64_t m = count_of(cxi, cyi);
-      if (!m) continue;
-      const int64_t ta = (m + 63) / 64;
-      cand += m * (m - 1) / 2;
-      n_tasks += ta * (ta + 1) / 2;
-      for (const auto& f : FWD) {
-        const int64_t m2 = count_of(cxi + f[0], cyi + f[1]);
-        cand += m * m2;
-        n_tasks += ta * ((m2 + 63) / 64);
-      }
-    }
+  sgs_count_pairs(grid, start, &cand, &n_tasks);
   *work = cand * (int64_t)nw;
   if (max_work <= 0) return 0;
   if (*work > max_work) {
@@ -415,26 +356,7 @@ extern "C" int gnx_sgs_sums(gnx_state* h, int64_t n, const int64_t* slots,
     return 1;
   }
   std::vector<SgsTask> tasks;
-  tasks.reserve((size_t)n_tasks);
-  for (int64_t cyi = 0; cyi < ncy; ++cyi)
-    for (int64_t cxi = 0; cxi < ncx; ++cxi) {
-      const int64_t m = count_of(cxi, cyi);
-      if (!m) continue;
-      const int32_t a0 = start[cyi * ncx + cxi];
-      for (int64_t i = 0; i < m; i += 64)
-        for (int64_t j = i; j < m; j += 64)
-          tasks.push_back(SgsTask{(int32_t)(a0 + i), (int32_t)std::min<int64_t>(64, m - i),
-                                  (int32_t)(a0 + j), (int32_t)std::min<int64_t>(64, m - j)});
-      for (const auto& f : FWD) {
-        const int64_t m2 = count_of(cxi + f[0], cyi + f[1]);
-        if (!m2) continue;
-        const int32_t b0 = start[(cyi + f[1]) * ncx + cxi + f[0]];
-        for (int64_t i = 0; i < m; i += 64)
-          for (int64_t j = 0; j < m2; j += 64)
-            tasks.push_back(SgsTask{(int32_t)(a0 + i), (int32_t)std::min<int64_t>(64, m - i),
-                                    (int32_t)(b0 + j), (int32_t)std::min<int64_t>(64, m2 - j)});
-      }
-    }
+  sgs_list_tasks(grid, start, n_tasks, tasks);
   n_tasks = (int64_t)tasks.size();
   const int blocks = (int)std::min<int64_t>(std::max<int64_t>(n_tasks, 1), SGS_BLOCKS);
   const int mi = (SGS_NB + 1) * SGS_NI, mf = SGS_NB * SGS_NF;

@@ -1001,6 +1001,51 @@ class Model:
             individs=self._test_sample(spp, individs, n), loci=loci, nperm=nperm, seed=seed,
             fit_range=fit_range, max_work=max_work)
 
+    def calc_relatedness(self, spp=0, individs=None, n=None, loci=None):
+        """KING-robust kinship between every two of at most 8192 individuals (an extension: the
+        reference has no relatedness analysis), from integer counts taken on the device:
+        kinship = (hh - 2 ibs0) / (nhet_a + nhet_b) with hh the loci at which both are
+        heterozygous, ibs0 those at which they are opposite homozygotes and nhet each one's
+        heterozygous loci (Manichaikul et al. 2010).  It uses no allele frequencies: about 1/4
+        for first-degree relatives, 1/8 for second-degree ones, 0 for unrelated individuals of
+        one population and negative across population structure.  individs, or a random sample
+        of n, and loci restrict the analysis
+        -> dict: ids, kinship [n][n] (0.5 on the diagonal; NaN where neither individual has a
+        heterozygous locus), ibs0, hh [n][n], nhet [n]"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_relatedness(individs=self._test_sample(spp, individs, n), loci=loci)
+
+    def find_kin(self, spp=0, max_dist=None, min_kinship=2 ** -3.5, individs=None, n=None,
+                 loci=None, max_pairs=1 << 22, max_work=None, po_max_ibs0=0):
+        """the pairs of close relatives in the population (an extension: the reference has no
+        such analysis): every two individuals closer than max_dist (None: every pair) whose
+        KING-robust kinship (calc_relatedness) is at least min_kinship, found on the device
+        without an n x n matrix, so the whole population can be searched - the parent-offspring
+        pairs whose distances are the dispersal kernel, the parent-offspring and half-sib
+        counts of close-kin mark-recapture, and the relatives to prune from a sample.  Each
+        pair is named by KING's cutoffs: 'dup', 'PO', 'FS', '2nd', '3rd' or 'un'; a first-degree
+        pair is 'PO' iff its ibs0 <= po_max_ibs0 (a parent and its child are never opposite
+        homozygotes).  With a recorded pedigree ('use_tskit': True) the truth stands beside it.
+        individs, or a random sample of n, and loci restrict the search.  max_pairs bounds the
+        list and max_work the pair-words of the device call; a request above either raises
+        ValueError
+        -> dict: ids_a, ids_b, kinship, ibs0, hh, dist, relationship (per pair, sorted by ids_a,
+        ids_b), n_candidates, work, ids, nhet; with a pedigree also true_relationship ('PO',
+        'FS', 'HS' or '')"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_kin_pairs(max_dist=max_dist, min_kinship=min_kinship,
+                                   individs=self._test_sample(spp, individs, n), loci=loci,
+                                   max_pairs=max_pairs, max_work=max_work,
+                                   po_max_ibs0=po_max_ibs0)
+
+    def get_pedigree_parents(self, spp=0, individs=None):
+        """the recorded parents of the living individuals asked for (all by default), from the
+        spatial pedigree of a 'use_tskit': True Species
+        -> (ids ascending, int64 [n][2]: the ids of the parents that gave homologues 0 and 1;
+        -1 for the founders)"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._get_pedigree_parents(individs=individs)
+
     def calc_ld_decay(self, spp=0, edges=None, n_bins=20, unit='c', max_dist=None,
                       individs=None, n=None, loci=None, min_maf=0.05, max_work=None):
         """the decay of linkage disequilibrium with distance, genome-wide (an extension: the

@@ -715,6 +715,100 @@ class SpeciesAnalyses:
         out.update(edges=edges, n_zero=obs['n_zero'], work=work, ids=ids)
         return out
 
+    # -- close-kin pairs (sim/kin.py; csrc/gnx_kin.hip) ----------------------------------------
+    def _calc_relatedness(self, individs=None, loci=None):
+        """KING-robust kinship (Manichaikul et al. 2010) between every two of the living
+        individuals asked for (all by default; at most 8192: the matrices are n x n), from the
+        integers the device counts (gnx_kin_matrix): the loci at which both are heterozygous
+        (hh), those at which they are opposite homozygotes (ibs0) and each one's heterozygous
+        loci (nhet); kinship = (hh - 2 ibs0) / (nhet_a + nhet_b), 0.5 on the diagonal, NaN where
+        neither has a heterozygous locus
+        -> dict: ids, kinship float64 [n][n], ibs0, hh int32 [n][n], nhet int32 [n]"""
+        from ..sim import kin as _kin
+        who = 'calc_relatedness'
+        _need_genomes(self, who)
+        ids, slots = self._geno_sample(individs)
+        if ids.size > 8192:
+            raise ValueError('relatedness of at most 8192 individuals per call (got %d): '
+                             'sample them with n=... or individs=..., or list the close pairs '
+                             'with find_kin' % ids.size)
+        _, mask = self._geno_loci(loci)
+        got = self._dev.kin_matrix(slots, mask)
+        nh = got['nhet']
+        return dict(ids=ids, kinship=_kin.king(got['hh'], got['ibs0'], nh[:, None], nh[None, :]),
+                    ibs0=got['ibs0'], hh=got['hh'], nhet=nh)
+
+    def _calc_kin_pairs(self, max_dist=None, min_kinship=2 ** -3.5, individs=None, loci=None,
+                        max_pairs=1 << 22, max_work=None, po_max_ibs0=0):
+        """the pairs of close relatives among the living individuals asked for (all by default;
+        no n x n matrix, so the whole population can be searched): every pair closer than
+        max_dist (None: every pair) whose KING-robust kinship is at least min_kinship (default
+        2^-3.5: second degree and closer), found on the device (gnx_kin_pairs), with the
+        relationship KING's cutoffs name ('dup', 'PO', 'FS', '2nd', '3rd', 'un'; a first-degree
+        pair is 'PO' iff ibs0 <= po_max_ibs0).  max_pairs: the pairs the list may hold;
+        max_work: the pair-words (pairs of individuals in the same or adjacent cells of side
+        max_dist x genome words) the call may take
+        -> dict: ids_a, ids_b (ids_a < ids_b, sorted by both), kinship, ibs0, hh, dist,
+        relationship (per pair), n_candidates (pairs closer than max_dist), work, ids, nhet;
+        with a recorded pedigree also true_relationship ('PO', 'FS', 'HS' or '')"""
+        from ..sim import kin as _kin
+        who = 'find_kin'
+        _need_genomes(self, who)
+        try:
+            T = _kin.threshold(min_kinship)
+        except (TypeError, ValueError):
+            raise ValueError('%s: min_kinship: a finite number in [-1, 0.5] (got %r)'
+                             % (who, min_kinship)) from None
+        if max_dist is not None and (isinstance(max_dist, bool)
+                                     or not 0 < float(max_dist) < np.inf):
+            raise ValueError('%s: max_dist: None or a positive finite distance (got %r)'
+                             % (who, max_dist))
+        if isinstance(max_pairs, bool) or int(max_pairs) != max_pairs or \
+                not 1 <= max_pairs <= 1 << 26:
+            raise ValueError('%s: max_pairs: a positive integer, at most 2^26 (got %r)'
+                             % (who, max_pairs))
+        max_work = _work_limit(who, max_work, self._SGS_MAX_WORK, 'pair-words')
+        ids, slots = self._geno_sample(individs)
+        n = ids.size
+        if n < 1 or n > 2 ** 24:
+            raise ValueError('%s: 1..2^24 individuals per call (got %d): sample them with '
+                             'n=... or individs=...' % (who, n))
+        _, mask = self._geno_loci(loci)
+        try:
+            got = _within_max_work(
+                who, lambda: self._dev.kin_pairs(T, max_dist, slots, mask, int(max_pairs),
+                                                 max_work),
+                'search a sample (n=... or individs=...), fewer loci (loci=...) or a smaller '
+                'max_dist, or raise max_work')
+        except nat.GnxError as err:
+            if 'exceed max_pairs' not in str(err):
+                raise
+            raise ValueError('%s: n_found = %d kept pairs exceed max_pairs = %d: ask for a '
+                             'higher min_kinship, a smaller max_dist, or a larger max_pairs'
+                             % (who, getattr(err, 'n_found', -1), max_pairs)) from None
+        pa, pb, nh = got['pa'], got['pb'], got['nhet']
+        x = self._field(nat.F_X)[slots].astype(np.float64)
+        y = self._field(nat.F_Y)[slots].astype(np.float64)
+        dx, dy = x[pa] - x[pb], y[pa] - y[pb]
+        kinship = _kin.king(got['hh'], got['ibs0'], nh[pa], nh[pb])
+        out = dict(ids_a=ids[pa], ids_b=ids[pb], kinship=kinship, ibs0=got['ibs0'],
+                   hh=got['hh'], dist=np.sqrt(dx * dx + dy * dy),
+                   relationship=_kin.relationship(kinship, got['ibs0'], po_max_ibs0),
+                   n_candidates=got['n_candidates'], work=got['work'], ids=ids, nhet=nh)
+        if self.__dict__.get('_tt') is not None:
+            par = self._tt.parents_of(ids)
+            out['true_relationship'] = _kin.pair_truth(ids[pa], ids[pb], par[pa], par[pb])
+        return out
+
+    def _get_pedigree_parents(self, individs=None):
+        """(ids ascending, int64 [n][2] their recorded parents' ids, -1 for founders) of the
+        living individuals asked for (all by default)"""
+        if self.__dict__.get('_tt') is None:
+            raise ValueError("get_pedigree_parents: no pedigree was recorded for this Species "
+                             "('use_tskit' False, or the genomes were not assigned yet)")
+        ids, _ = self._geno_sample(individs)
+        return ids, self._tt.parents_of(ids)
+
     # -- genome-wide linkage disequilibrium (sim/ld.py; csrc/gnx_ld.hip) ---------------------
     # tile-words (64 x 64-locus tiles x chromosome words) one call may take; a tile-word is 4096
     # pair-words of the popcount tile, so this is four times _SGS_MAX_WORK (DESIGN section 16)

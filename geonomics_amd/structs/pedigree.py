@@ -201,6 +201,24 @@ class TreeTables:
         self._flush()
         return self._nt[0], self._bt[0]
 
+    def parents_of(self, ids):
+        """int64 [n][2]: the ids of the two parents of each listed individual, column h the
+        parent that gave homologue h; -1 for founders and for ids that are not in the table
+        (never recorded, or dropped by simplify)"""
+        ids = np.asarray(ids, dtype=np.int64).ravel()
+        known = self.ids
+        nt, _ = self.node_table()
+        out = np.full((ids.size, 2), -1, np.int64)
+        if known.size == 0 or ids.size == 0:
+            return out
+        row = np.minimum(np.searchsorted(known, ids), known.size - 1)
+        there = known[row] == ids
+        for hom in range(2):
+            prow = nt[2 * row + hom, 0].astype(np.int64)
+            has = there & (prow >= 0)
+            out[has, hom] = known[prow[has]]
+        return out
+
     def _switches_upto(self, key, locus):
         """number of switch points <= locus of path `key` (arrays of one shape)"""
         if self._bp_loci.size == 0:

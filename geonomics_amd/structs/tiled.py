@@ -68,6 +68,11 @@ _NOT_TILED = {
     # samples would have to be exchanged)
     '_calc_spatial_structure': 'calc_spatial_structure with a Species tiled over several '
                                'GPUs is not implemented; run the model on one GPU',
+    # close-kin pairs (relatives on both sides of a tile border: the same exchange)
+    '_calc_relatedness': 'calc_relatedness with a Species tiled over several GPUs is not '
+                         'implemented; run the model on one GPU',
+    '_calc_kin_pairs': 'find_kin with a Species tiled over several GPUs is not '
+                       'implemented; run the model on one GPU',
     '_calc_ld_decay': 'calc_ld_decay with a Species tiled over several GPUs is not '
                       'implemented; run the model on one GPU',
     '_calc_ne': 'calc_ne with a Species tiled over several GPUs is not '

@@ -934,6 +934,51 @@ int gnx_tracts_pairs(gnx_state* h, int64_t n, const int64_t* slots, const int64_
  * not read; gnx_tracts_pairs: the gather's); each may be NULL                                  */
 int gnx_tracts_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* bytes_read);
 
+/* ---- close-kin pairs (csrc/gnx_kin.hip; the reference has no such analysis) ----------------
+ * Who is related to whom: KING-robust kinship (Manichaikul et al. 2010) and the IBS0 count of
+ * pairs of individuals, from which parent-offspring, full-sib and second-degree pairs are named
+ * (geonomics_amd/sim/kin.py).  Definitions, for individual a with homologue bits a0, a1 at the
+ * masked loci:
+ *   O_a = a0 | a1,  P_a = a0 & a1 (homozygous 1),  het_a = O_a ^ P_a;
+ *   nhet_a = popcount(het_a);
+ *   hh_ab = popcount(het_a & het_b)                              (both heterozygous);
+ *   ibs0_ab = popcount(P_a & ~O_b) + popcount(P_b & ~O_a)        (opposite homozygotes);
+ *   kinship_ab = (hh_ab - 2 ibs0_ab) / (nhet_a + nhet_b), in fp64, ON THE HOST ONLY; a zero
+ *   denominator gives NaN in the matrix, and such a pair is never kept in the list.
+ * Everything the device returns is an integer per individual or per pair: exact, independent of
+ * order (integer atomics are fine), and bit-equal to the numpy restatement (sim/kin.py).
+ * n, slots, locus_mask and the preconditions as gnx_geno_gram.
+ *
+ * gnx_kin_matrix: 1..8192 individuals.  HOST outputs, int32: nhet [n], hh [n][n], ibs0 [n][n],
+ * symmetric, with hh[a][a] = nhet_a and ibs0[a][a] = 0.                                        */
+int gnx_kin_matrix(gnx_state* h, int64_t n, const int64_t* slots, const uint64_t* locus_mask,
+                   int32_t* nhet /*[n]*/, int32_t* hh /*[n][n]*/, int32_t* ibs0 /*[n][n]*/);
+/* gnx_kin_pairs: the list of kept pairs of 1..2^24 individuals, no n x n matrix.  For a pair
+ * a != b of the sample r is taken as gnx_sgs_sums takes it (fp64 from the device's fp32 x and y,
+ * without contraction).  With 0 < max_dist < inf a pair is a CANDIDATE iff r < max_dist - pairs at
+ * r == 0 are candidates, unlike in gnx_sgs_sums - and only the pairs of individuals in the same
+ * or adjacent cells of gnx_sgs_sums' grid (side just above max_dist, at most 2^22 cells) are
+ * looked at; max_dist <= 0 or infinite: every pair is a candidate (one cell).  A candidate is KEPT
+ * iff nhet_a + nhet_b > 0 and (hh - 2 ibs0) 2^20 >= T (nhet_a + nhet_b) in int64; the host passes
+ * T = ceil(min_kinship 2^20), -2^20 <= T <= 2^19.  *work = the pairs of individuals in the same
+ * or adjacent cells times the number of words the mask touches; it is known after the cell sort
+ * and before the operand is gathered.  max_work <= 0: only *work is written (every other output
+ * may be NULL).  HOST outputs otherwise: *n_candidates, *n_found (the kept pairs), nhet int32 [n]
+ * and, for k < *n_found, the sample indices pa[k] < pb[k] with hh[k] and ibs0[k], int32
+ * [max_pairs] each, sorted by (pa, pb): a call repeated is byte-equal.  max_pairs in 1..2^26.
+ * Refused (return 1) before anything is launched: n, T or max_pairs out of range, max_dist NaN,
+ * a slot out of range; after the cell sort and before the gather: *work > max_work (*work is
+ * written); after the pair kernel: *n_found > max_pairs, with a message containing "exceed
+ * max_pairs" - *work and *n_found are written, nothing else.  Nothing of the handle changes.  */
+int gnx_kin_pairs(gnx_state* h, int64_t n, const int64_t* slots, const uint64_t* locus_mask,
+                  double max_dist, int64_t T, int64_t max_pairs, int64_t max_work, int64_t* work,
+                  int64_t* n_candidates, int64_t* n_found, int32_t* pa /*[max_pairs]*/,
+                  int32_t* pb /*[max_pairs]*/, int32_t* hh /*[max_pairs]*/,
+                  int32_t* ibs0 /*[max_pairs]*/, int32_t* nhet /*[n]*/);
+/* of the last gnx_kin_matrix / gnx_kin_pairs: its kernels' HIP-event time (ms), their number and
+ * its 64 x 64 tiles of pairs; each may be NULL                                                 */
+int gnx_kin_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* tasks);
+
 /* ---- haplotype sweep scans (csrc/gnx_sweeps.hip; the reference has no such analysis) -----------
  * Extended haplotype homozygosity around core loci of the phased genomes, from which EHH, iHS,
  * nSL and XP-EHH follow on the host (geonomics_amd/sim/sweeps.py).  Definitions:
