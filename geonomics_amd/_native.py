@@ -74,6 +74,7 @@ EXPORTS = [
     'gnx_divmap_sums', 'gnx_divmap_info',
     'gnx_circuit_matrix', 'gnx_circuit_current', 'gnx_circuit_potentials', 'gnx_circuit_budget',
     'gnx_circuit_info',
+    'gnx_lai_paint',
 ]
 
 
@@ -1351,6 +1352,61 @@ class Device:
                                           C.byref(inst)))
         return dict(kernel_ms=ms.value, launches=int(n.value), chunks=int(nc.value),
                     instance=int(inst.value))
+
+    # -- local ancestry along the genome (csrc/gnx_lai.hip) ------------------------------------
+    def lai_paint(self, F, sw, stay, Q, slots=None, loci=None, by=None, n_groups=0, budget=None,
+                  want_post=True, want_calls=False):
+        """the linkage model painted along every haplotype of `slots` (all living slots by
+        default, in the order given; include/gnx_hip.h, gnx_lai_paint): F fp64 [L_u][K], sw and
+        stay fp64 [L_u], Q fp64 [n][K]; loci int32 [L_u] ascending (None: all L); by int32 [n]
+        labels in -1..n_groups-1 or None; budget: bytes of device scratch per batch of
+        haplotypes (None: the default)
+        -> dict(loglik fp64 [2n], anc_hap fp64 [2n][K], anc_locus fp64 [max(n_groups, 1)][L_u][K],
+        switches int32 [2n], calls uint8 [2n][L_u] or None, batches, kernel_ms); with
+        want_post=False only loglik (the others None)"""
+        s, n = self._geno_slots(slots)
+        F = _arr(F, np.float64)
+        if F.ndim != 2:
+            raise ValueError('F: an array [L_u][K]')
+        L_u, K = int(F.shape[0]), int(F.shape[1])
+        sw, stay, Q = _arr(sw, np.float64).ravel(), _arr(stay, np.float64).ravel(), \
+            _arr(Q, np.float64)
+        if sw.size != L_u or stay.size != L_u:
+            raise ValueError('sw, stay: %d and %d entries, not L_u = %d' % (sw.size, stay.size,
+                                                                           L_u))
+        if Q.shape != (n, K):
+            raise ValueError('Q: %s, not (n, K) = (%d, %d)' % (Q.shape, n, K))
+        lo = None
+        if loci is not None:
+            lo = _arr(loci, np.int32).ravel()
+            if lo.size != L_u:
+                raise ValueError('loci: %d entries, not L_u = %d' % (lo.size, L_u))
+        b = None
+        if by is not None:
+            b = _arr(by, np.int32).ravel()
+            if b.size != n:
+                raise ValueError('by: %d labels, not n = %d' % (b.size, n))
+        post, wc = bool(want_post), bool(want_calls)
+        n_g = max(int(n_groups), 1)
+        # (the library refuses n < 1 and K outside 1..8 before it writes)
+        T = 2 * max(n, 0)
+        ll = np.zeros(max(T, 1))
+        ah = np.zeros((T, K)) if post else None
+        al = np.zeros((n_g, L_u, K)) if post else None
+        sn = np.zeros(max(T, 1), np.int32) if post else None
+        calls = np.zeros((T, L_u), np.uint8) if post and wc else None
+        nb, ms = C.c_int64(0), C.c_double(0.0)
+        self._chk(self.lib.gnx_lai_paint(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), C.c_int32(K), C.c_int32(L_u),
+            _ptr(lo, C.c_int32), _ptr(F, C.c_double), _ptr(sw, C.c_double),
+            _ptr(stay, C.c_double), _ptr(Q, C.c_double), _ptr(b, C.c_int32),
+            C.c_int32(int(n_groups)), C.c_int64(int(budget or 0)), C.c_int32(int(post)),
+            C.c_int32(int(wc)), _ptr(ll, C.c_double), _ptr(ah, C.c_double),
+            _ptr(al, C.c_double), _ptr(sn, C.c_int32), _ptr(calls, C.c_uint8), C.byref(nb),
+            C.byref(ms)))
+        return dict(loglik=ll[:T], anc_hap=ah, anc_locus=al,
+                    switches=None if sn is None else sn[:T], calls=calls,
+                    batches=int(nb.value), kernel_ms=ms.value)
 
     # -- identity tracts of the phased genomes (csrc/gnx_tracts.hip) ------------------------
     def _tract_args(self, pos, brk, edges):

@@ -1099,6 +1099,33 @@ class Model:
                                   init=init, seed=seed, accelerate=accelerate, tol=tol,
                                   max_sweeps=max_sweeps, fixed_F=fixed_F)
 
+    def calc_local_ancestry(self, spp=0, ancestry=None, F=None, loci=None, panels=None,
+                            prior='fit', gens=10.0, individs=None, n=None, by=None, eps=1e-3,
+                            calls=False, budget=None):
+        """local ancestry (an extension: the reference has no such analysis): where on the
+        genome the ancestry that calc_ancestry measures lies - after introductions, assisted
+        gene flow, secondary contact or genetic rescue (add_individuals) - from the linkage
+        model of Falush et al. (2003) with fixed frequencies and one admixture time, painted
+        along both phased haplotypes of every individual on the device with the architecture's
+        recombination map.  The frequencies come from exactly one of: ancestry (the dict
+        calc_ancestry returned), F [K][loci used] with loci (None: all; 'neutral'; an ascending
+        list), or panels (a label 0..K-1 per living individual in ascending-id order, -1: in no
+        panel; reference-panel frequencies (ones + 0.5) / (2 n_k + 1)); K <= 8; they are
+        clipped to [eps, 1 - eps].  prior: 'fit' (calc_ancestry's Q under those frequencies),
+        'uniform' or rows [n][K].  gens: the generations since admixture, or 'fit'.  individs,
+        or a random sample of n, restrict the analysis; by: a label 0..63 per analysed
+        individual (-1: left out) for per-group summaries.  calls: also the hard calls and
+        their tracts.  budget: bytes of device scratch per batch of haplotypes
+        -> dict: ids, loci, K, gens, gens_trace (when fitted: rows (gens, loglik)), loglik,
+        loglik_hap [2n] (haplotype 2 i + homologue), Q_local [n][K] (the share of the genome
+        per ancestry), Q_prior, anc_locus [L_u][K] (mean posterior per locus; [G][L_u][K] with
+        by), switches [2n], calls [2n][L_u] and tracts (if asked), map_len"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_local_ancestry(ancestry=ancestry, F=F, loci=loci, panels=panels,
+                                        prior=prior, gens=gens,
+                                        individs=self._test_sample(spp, individs, n), by=by,
+                                        eps=eps, calls=calls, budget=budget)
+
     def calc_roh(self, spp=0, min_len=0.01, min_loci=50, unit='morgans', individs=None, n=None,
                  edges=None, cover=False):
         """runs of homozygosity and the genomic inbreeding coefficient F_ROH per individual (an

@@ -954,6 +954,127 @@ class SpeciesAnalyses:
                        loci=np.arange(L_u, dtype=np.int64) if loci_u is None else loci_u,
                        individs=ids)
 
+    # -- local ancestry along the genome (sim/lai.py; csrc/gnx_lai.hip) ------------------------
+    def _calc_local_ancestry(self, ancestry=None, F=None, loci=None, panels=None, prior='fit',
+                             gens=10.0, individs=None, by=None, eps=1e-3, calls=False,
+                             budget=None):
+        """where on the genome the ancestry of the living individuals asked for (all by
+        default) lies: the linkage model of Falush et al. (2003) with the frequencies held fixed
+        and one admixture time, painted along both haplotypes of every individual on the device
+        (gnx_lai_paint; sim/lai.py states the model).  The frequencies come from exactly one of
+        ancestry (the dict calc_ancestry returned: its F and loci), F [K][the loci used] with
+        loci (None: all; 'neutral'; or an ascending list), or panels (a label 0..K-1 per living
+        individual in ascending-id order, -1: in no panel; F = (ones + 0.5) / (2 n_k + 1) of
+        each panel's counts).  They are clipped to [eps, 1 - eps].  prior: 'fit' (the Q of
+        _calc_ancestry under the held frequencies), 'uniform' or rows [n][K] that sum to 1.
+        gens: generations since admixture, or 'fit' (golden-section search on the total
+        log-likelihood, forward passes only).  by: a label per analysed individual, 0..63 (-1:
+        left out), for anc_locus per group.  calls: also the hard calls and their tracts.
+        budget: bytes of device scratch per batch of haplotypes (None: the library's default)
+        -> dict: ids, loci, K, gens, gens_trace (when fitted), loglik, loglik_hap [2n], Q_local
+        [n][K], Q_prior [n][K], anc_locus [L_u][K] ([G][L_u][K] with by; means over the
+        haplotypes), switches [2n], calls uint8 [2n][L_u] and tracts (sim/lai.calls_to_tracts;
+        if asked), map_len (Morgans, breaks left out)"""
+        import math
+        from ..sim import lai as _lai
+        from ..sim import ld as _ld
+        who = 'calc_local_ancestry'
+        _need_genomes(self, who)
+        given = [name for name, v in (('ancestry', ancestry), ('F', F), ('panels', panels))
+                 if v is not None]
+        if len(given) != 1:
+            raise ValueError('%s: exactly one of ancestry, F and panels gives the frequencies '
+                             '(got %s)' % (who, ', '.join(given) or 'none'))
+        if ancestry is not None:
+            if loci is not None:
+                raise ValueError('%s: ancestry brings its own loci; give no loci' % who)
+            try:
+                F, loci = ancestry['F'], ancestry['loci']
+            except (TypeError, KeyError, IndexError):
+                raise ValueError('%s: ancestry: the dict calc_ancestry returned (F and loci)'
+                                 % who) from None
+        if isinstance(loci, str):
+            if loci != 'neutral':
+                raise ValueError("%s: loci: a list of loci, None or 'neutral' (got %r)"
+                                 % (who, loci))
+            loci = self.gen_arch.neut_loci
+        if loci is not None and (np.diff(np.asarray(loci, dtype=np.int64).ravel()) <= 0).any():
+            raise ValueError('%s: loci: ascending and distinct (they are the columns of F)' % who)
+        loci_u, _ = self._geno_loci(loci)
+        L_u = self._dev.L if loci_u is None else int(loci_u.size)
+        ids, slots = self._geno_sample(individs)
+        n = int(ids.size)
+        if n < 1:
+            raise ValueError('%s: at least one individual' % who)
+        if isinstance(eps, bool) or not 0.0 < float(eps) < 0.5:
+            raise ValueError('%s: eps: a number in (0, 0.5) (got %r)' % (who, eps))
+        if panels is None:
+            F = np.array(F, dtype=np.float64)
+            if F.ndim != 2 or F.shape[1] != L_u or not np.isfinite(F).all():
+                raise ValueError('%s: F: finite frequencies [K][the %d loci used] (got %s)'
+                                 % (who, L_u, F.shape))
+            K = _lai.check_K(F.shape[0])
+        else:
+            lab = np.asarray(panels)
+            if lab.ndim != 1 or lab.dtype.kind not in 'iu' or lab.size != len(self):
+                raise ValueError('%s: panels: one integer label per living individual, in '
+                                 'ascending-id order' % who)
+            if lab.min() < -1 or lab.max() < 0:
+                raise ValueError('%s: panels: labels in -1..K-1 (-1: in no panel)' % who)
+            K = _lai.check_K(int(lab.max()) + 1)
+            if (np.bincount(lab[lab >= 0], minlength=K) < 1).any():
+                raise ValueError('%s: panels: every panel 0..%d holds at least one individual'
+                                 % (who, K - 1))
+        fit_t = isinstance(gens, str) and gens == 'fit'
+        if not fit_t:
+            gens = _lai.check_gens(gens)
+        fit_q = isinstance(prior, str) and prior == 'fit'
+        Q = None if fit_q else _lai.check_prior(prior, n, K)
+        by, n_groups = _lai.check_by(by, n)
+        if budget is not None and (isinstance(budget, bool) or int(budget) != budget
+                                   or budget < 1):
+            raise ValueError('%s: budget: a positive number of bytes (got %r)' % (who, budget))
+        # ---- from here on the device is asked
+        if panels is not None:
+            _, n_k, ones, _ = self._group_counts(lab.astype(np.int64), loci_u)
+            F = _lai.panel_freqs(ones, n_k)
+        F = _lai.clip_freqs(F, eps)
+        if fit_q:
+            Q = self._calc_ancestry(K, individs=ids, loci=loci_u, fixed_F=F)['Q']
+        pos = _ld.map_positions(_rec_rates(self))
+        if loci_u is not None:
+            pos = pos[loci_u]
+        Fd = np.ascontiguousarray(F.T)
+        loci_d = None if loci_u is None else loci_u.astype(np.int32)
+
+        def paint(g, post):
+            sw, stay = _lai.switch_probs(pos, g)
+            return self._dev.lai_paint(Fd, sw, stay, Q, slots, loci_d, by, n_groups, budget,
+                                       want_post=post, want_calls=post and bool(calls))
+
+        out = dict(ids=ids, loci=np.arange(L_u, dtype=np.int64) if loci_u is None else loci_u,
+                   K=K)
+        if fit_t:
+            gens, trace = _lai.fit_gens(
+                lambda g: math.fsum(paint(g, False)['loglik'].tolist()))
+            out['gens_trace'] = np.array(trace)
+        got = paint(gens, True)
+        ah = got['anc_hap']
+        per = np.full(1, 2.0 * n) if by is None else \
+            2.0 * np.bincount(by[by >= 0], minlength=n_groups)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            al = got['anc_locus'] / per[:, None, None]
+        d = np.diff(pos)
+        brk = np.r_[True, d >= _ld.BREAK_MORGANS / 2]
+        out.update(gens=float(gens), loglik=math.fsum(got['loglik'].tolist()),
+                   loglik_hap=got['loglik'], Q_local=0.5 * (ah[0::2] + ah[1::2]) / L_u,
+                   Q_prior=Q, anc_locus=al[0] if by is None else al, switches=got['switches'],
+                   map_len=float(d[~brk[1:]].sum()))
+        if calls:
+            out['calls'] = got['calls']
+            out['tracts'] = _lai.calls_to_tracts(got['calls'], pos, brk, K=K)
+        return out
+
     # -- identity tracts of the phased genomes (sim/tracts.py; csrc/gnx_tracts.hip) -----------
     # word steps (haplotype pairs x genome words) one pair scan may take: 4096 individuals at
     # 10^5 loci are 5.2e10

@@ -79,6 +79,10 @@ _NOT_TILED = {
                 'implemented; run the model on one GPU',
     '_calc_ancestry': 'calc_ancestry with a Species tiled over several GPUs is not '
                       'implemented; run the model on one GPU',
+    # local ancestry (row-local like the sweep above, but anc_locus adds over tiles in a fixed
+    # order and the prior comes from calc_ancestry)
+    '_calc_local_ancestry': 'calc_local_ancestry with a Species tiled over several GPUs is '
+                            'not implemented; run the model on one GPU',
     # identity tracts (a pair of individuals of different tiles: a gather of the sample)
     '_calc_roh': 'calc_roh with a Species tiled over several GPUs is not '
                  'implemented; run the model on one GPU',

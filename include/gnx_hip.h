@@ -1082,6 +1082,51 @@ int gnx_admix_sweep(gnx_state* h, int64_t n, const int64_t* slots /*NULL: all li
 int gnx_admix_info(gnx_state* h, double* kernel_ms, int64_t* launches, int64_t* chunks,
                    int32_t* instance);
 
+/* ---- local ancestry along the genome (csrc/gnx_lai.hip; the reference has no such analysis) ----
+ * The linkage model of Falush, Stephens & Pritchard (2003) with fixed frequencies and one
+ * admixture time, painted along every phased haplotype of the sample by forward-backward.  The
+ * hidden state of haplotype t = 2 i + homologue at used locus j is its ancestry z in 0..K-1.
+ * Inputs, all HOST buffers: the sample of n individuals (n, slots as in the genetic PCA calls, in
+ * the order given); 1 <= K <= 8; the L_u used loci, ascending (loci NULL: all, L_u = L);
+ * F fp64 [L_u][K] = P(allele 1 | ancestry k) strictly inside (0, 1); sw, stay fp64 [L_u], the
+ * probabilities that the ancestry is drawn anew from the prior between used loci j - 1 and j, and
+ * kept (sw[0] = 1, stay[0] = 0); Q fp64 [n][K], the prior of individual i (both homologues);
+ * by int32 [n] labels in -1..max(n_groups, 1)-1 (-1: left out of anc_locus) or NULL (one group),
+ * n_groups <= 64.  g = 1 - f rounded to fp64; E_k = f[j][k] if the haplotype's bit is 1, else
+ * g[j][k].  Forward, j = 0 .. L_u - 1, alpha_{-1} = q:
+ *   b_k = (stay_j alpha_{j-1,k} + sw_j q_k) E_k,  c = b_0 + b_1 + ..,  alpha_{j,k} = b_k / c,
+ *   ll += ln c
+ * Backward, beta_{L_u-1,k} = 1, j = L_u - 1 .. 0:
+ *   p_k = alpha_{j,k} beta_{j,k},  gamma_{j,k} = p_k / (p_0 + p_1 + ..)
+ *   j > 0: w_k = beta_{j,k} E_k,  u = q_0 w_0 + q_1 w_1 + ..,  b'_k = stay_j w_k + sw_j u,
+ *          beta_{j-1,k} = b'_k / (b'_0 + b'_1 + ..)
+ * Every operation is one IEEE fp64 +, * or / (no contraction), every sum over k runs left to
+ * right; the logarithm is the device library's.  Outputs, HOST buffers:
+ *   loglik    fp64 [2n]        the sum of ln c in ascending j
+ *   anc_hap   fp64 [2n][K]     the sum of gamma over j, in descending j        (want_post)
+ *   anc_locus fp64 [max(n_groups, 1)][L_u][K]  the sum of gamma over the haplotypes of the
+ *             group, one after the other in ascending t                        (want_post)
+ *   switches  int32 [2n]       the j >= 1 whose call differs from that of j - 1; the call is the
+ *             smallest k of largest gamma                                      (want_post)
+ *   calls     uint8 [2n][L_u]                                    (want_post and want_calls)
+ * want_post == 0: only the forward pass runs, nothing is stored and only loglik is written.
+ * budget: bytes of device scratch the posteriors (8 K L_u per haplotype, and 2 L_u with
+ * want_calls) of one batch of haplotypes may take (0: the default, 4 GiB); the haplotypes are
+ * worked off in batches of a multiple of 64.  No output depends on the budget, and a call repeated
+ * is bit-equal in every output: no floating-point atomics.  *batches (may be NULL): the batches;
+ * *kernel_ms (may be NULL): the HIP-event time of the call's kernels.  Preconditions as the
+ * genetic PCA calls; no individual, genome or later draw is changed.  Refused (return 1) before
+ * anything is launched: no genomes, ghost records, K outside 1..8, n < 1, L_u outside 1..L, loci
+ * not ascending or outside 0..L-1, n_groups outside 0..64, a label outside -1..max(n_groups,1)-1,
+ * a null pointer, budget < 0, a budget that cannot hold 64 haplotypes (want_post), a slot out of
+ * range.                                                                                       */
+int gnx_lai_paint(gnx_state* h, int64_t n, const int64_t* slots /*NULL: all living*/, int32_t K,
+                  int32_t L_u, const int32_t* loci /*[L_u] or NULL*/, const double* F,
+                  const double* sw, const double* stay, const double* Q, const int32_t* by,
+                  int32_t n_groups, int64_t budget, int32_t want_post, int32_t want_calls,
+                  double* loglik, double* anc_hap, double* anc_locus, int32_t* switches,
+                  uint8_t* calls, int64_t* batches, double* kernel_ms);
+
 /* ---- lineages through the recorded pedigree (csrc/gnx_lineage.hip; reference
  *      structs/genome.py:1638-1782 _get_lineage_dicts, structs/species.py:1242-1343) ---------
  * The pedigree is recorded on the host (geonomics_amd/structs/pedigree.py, TreeTables.
