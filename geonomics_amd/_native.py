@@ -75,6 +75,7 @@ EXPORTS = [
     'gnx_circuit_matrix', 'gnx_circuit_current', 'gnx_circuit_potentials', 'gnx_circuit_budget',
     'gnx_circuit_info',
     'gnx_lai_paint',
+    'gnx_assoc_cross',
 ]
 
 
@@ -1407,6 +1408,32 @@ class Device:
         return dict(loglik=ll[:T], anc_hap=ah, anc_locus=al,
                     switches=None if sn is None else sn[:T], calls=calls,
                     batches=int(nb.value), kernel_ms=ms.value)
+
+    # -- per-locus association scans (csrc/gnx_assoc.hip) --------------------------------------
+    def assoc_cross(self, Y, slots=None):
+        """D^T Y in fp64 and the integer moments of the dosages of `slots` (all living slots by
+        default, in the order given; include/gnx_hip.h, gnx_assoc_cross): Y fp64 [n][m] (or [n])
+        on the host, finite, 1 <= m <= 32
+        -> dict(DtY fp64 [L][m], s1 int64 [L] = sum d, s2 int64 [L] = sum d^2, stretch,
+        stretches (the summation order: sim/assoc.stretch_rule), kernel_ms)"""
+        s, n = self._geno_slots(slots)
+        Y = _arr(Y, np.float64)
+        if Y.ndim == 1:
+            Y = Y[:, None]
+        if Y.ndim != 2 or Y.shape[0] != n:
+            raise ValueError('Y: %s, not [n = %d][m]' % (Y.shape, n))
+        m = int(Y.shape[1])
+        # (the library refuses m outside 1..32 before it writes)
+        mo = m if 1 <= m <= 32 else 0
+        out = np.zeros((self.L, mo))
+        s1, s2 = np.zeros(self.L, np.int64), np.zeros(self.L, np.int64)
+        per, cnt, ms = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+        self._chk(self.lib.gnx_assoc_cross(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), C.c_int32(m), _ptr(Y, C.c_double),
+            _ptr(out, C.c_double), _ptr(s1, C.c_int64), _ptr(s2, C.c_int64), C.byref(per),
+            C.byref(cnt), C.byref(ms)))
+        return dict(DtY=out, s1=s1, s2=s2, stretch=int(per.value), stretches=int(cnt.value),
+                    kernel_ms=ms.value)
 
     # -- identity tracts of the phased genomes (csrc/gnx_tracts.hip) ------------------------
     def _tract_args(self, pos, brk, edges):

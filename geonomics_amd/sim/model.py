@@ -871,6 +871,43 @@ class Model:
                           'path); pass plot=False.  The results are returned.', stacklevel=2)
         return results
 
+    def run_gwas(self, trt=0, spp=0, y=None, covars=(), n_pcs=0, individs=None, n=None,
+                 loci=None, min_maf=0.01, calibrate=False):
+        """genome-wide association scan (an extension: the reference has no such analysis):
+        for every locus the regression of the response - the phenotype z of Trait trt, or y [n]
+        in ascending-id order - on the dosage, given the covariates and an intercept, over the
+        whole population by default, computed on the device in fp64 (gnx_assoc_cross; the
+        statistics are sim/assoc.py's).  covars: any of 'env' (the layers the Traits are tied
+        to), ('env', lyr), 'x', 'y', or an array [n][c] in ascending-id order; n_pcs > 0 appends
+        the first genetic PCs (calc_genetic_PCA, with its limits).  individs, or a random sample
+        of n, restrict the rows; loci selects rows of the result after the full scan.  Loci that
+        are monomorphic, below min_maf or collinear with the covariates are not tested (NaN).
+        calibrate: p from t^2 / gif against chi-square with 1 df.  At most 32 covariates and
+        responses together.
+        -> dict: loci, beta, se, t, p, q [n_loci][r], maf, tested, gif [r], df, ids, trait_loci,
+        pcs [n][n_pcs], kernel_ms"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._run_gwas(trt_num=self._get_trt_num(spp, trt), y=y, covars=covars,
+                             n_pcs=n_pcs, individs=self._test_sample(spp, individs, n),
+                             loci=loci, min_maf=min_maf, calibrate=calibrate)
+
+    def run_lfmm(self, K, spp=0, env_lyrs=None, lam=1e-5, individs=None, n=None, loci=None,
+                 min_maf=0.01, calibrate=True):
+        """genotype-environment association scan with K latent factors (LFMM2, Caye et al.
+        2019; an extension: the reference has no such analysis): for every locus the regression
+        of the dosage on each environmental layer (env_lyrs; default: the layers the Traits are
+        tied to, or all) given the other layers and the latent factors of the ridge estimate with
+        penalty lam, computed on the device in fp64.  K = 0 is the plain linear model.  At most
+        8192 individuals (the factors come from the n x n Gram matrix): individs, or a random
+        sample of n, restrict the rows; loci selects rows of the result after the full scan.
+        calibrate: p from t^2 / gif against chi-square with 1 df (LFMM's usual calibration).
+        -> dict: loci, beta, se, t, p, q [n_loci][layers], maf, tested, gif [layers], df, ids,
+        trait_loci (per layer), U [n][K], kernel_ms"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._run_lfmm(K, env_lyrs=env_lyrs, lam=lam,
+                             individs=self._test_sample(spp, individs, n), loci=loci,
+                             min_maf=min_maf, calibrate=calibrate)
+
     def _test_sample(self, spp, individs, n):
         """the ids a Mantel / MMRR call analyses: individs, or a random n of the living drawn
         as write_gendata draws its sample, or everybody"""

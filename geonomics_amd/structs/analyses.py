@@ -389,6 +389,160 @@ class SpeciesAnalyses:
         return dict(ind_df=res['ind_df'], loci_df=res['loci_df'], var_df=res['var_df'],
                     trait_loci=np.asarray(trt.loci), ids=ids)
 
+    # -- per-locus association scans (sim/assoc.py; csrc/gnx_assoc.hip) ----------------------
+    def _env_layers(self, who, env_lyrs):
+        """the layers of a request: env_lyrs, or the layers the Traits are tied to, or every
+        layer of a Species without Traits (as _dist_predictors)"""
+        n_layers = int(self._dev.cfg.n_layers)
+        lyrs = env_lyrs
+        if lyrs is None:
+            traits = self.gen_arch.traits or {}
+            lyrs = sorted({int(t.lyr_num) for t in traits.values()}) or range(n_layers)
+        lyrs = [int(l) for l in np.atleast_1d(lyrs)]
+        if not lyrs or min(lyrs) < 0 or max(lyrs) >= n_layers or len(set(lyrs)) != len(lyrs):
+            raise ValueError('%s: env_lyrs: distinct layers in 0..%d' % (who, n_layers - 1))
+        return lyrs
+
+    def _assoc_covars(self, who, covars, n):
+        """the covariates of run_gwas as [(columns or None, fetch(slots) -> [n][c])]: 'env' (the
+        layers the Traits are tied to), ('env', lyr), 'x', 'y', or an array [n][c] in
+        ascending-id order; the arrays are counted before the device is asked"""
+        if isinstance(covars, (str, np.ndarray)) or (
+                isinstance(covars, tuple) and len(covars) == 2 and covars[0] == 'env'
+                and not isinstance(covars[1], (str, tuple, list, np.ndarray))):
+            covars = [covars]
+        out = []
+        for c in covars:
+            if isinstance(c, str) and c in ('x', 'y'):
+                f = nat.F_X if c == 'x' else nat.F_Y
+                out.append((1, lambda slots, f=f: self._field(f)[slots].astype(np.float64)[:, None]))
+            elif isinstance(c, str) and c == 'env':
+                out.append((None, lambda slots: self._field(nat.F_E)[
+                    self._env_layers(who, None)][:, slots].T.astype(np.float64)))
+            elif isinstance(c, tuple) and len(c) == 2 and c[0] == 'env':
+                out.append((1, lambda slots, l=c[1]: self._field(nat.F_E)[
+                    self._env_layers(who, [l])][:, slots].T.astype(np.float64)))
+            elif isinstance(c, str):
+                raise ValueError("%s: covars: 'env', ('env', lyr), 'x', 'y' or an array [n][c] "
+                                 "(got %r)" % (who, c))
+            else:
+                a = np.asarray(c, dtype=np.float64)
+                a = a[:, None] if a.ndim == 1 else a
+                if a.ndim != 2 or a.shape[0] != n or not np.isfinite(a).all():
+                    raise ValueError('%s: covars: a finite array [n = %d][c] in ascending-id '
+                                     'order (got %s)' % (who, n, a.shape))
+                out.append((a.shape[1], lambda slots, a=a: a))
+        return out
+
+    def _assoc_result(self, res, ids, loci, trait_loci, **more):
+        """the dict an association scan returns: the scan's arrays at `loci` (all by default;
+        chosen on the host after the full scan, so gif and q are those of the whole genome)"""
+        loci_u, _ = self._geno_loci(loci)
+        if loci_u is None:
+            loci_u = np.arange(self._dev.L, dtype=np.int64)
+        out = {k: res[k][loci_u] for k in ('beta', 'se', 't', 'p', 'q', 'maf', 'tested')}
+        out.update(loci=loci_u, gif=res['gif'], df=res['df'], ids=ids, trait_loci=trait_loci,
+                   kernel_ms=res['kernel_ms'], **more)
+        return out
+
+    def _run_gwas(self, trt_num=0, y=None, covars=(), n_pcs=0, individs=None, loci=None,
+                  min_maf=0.01, calibrate=False, collinear_tol=1e-8):
+        """a genome-wide association scan over the living individuals asked for (all by
+        default): per locus the regression of the response - the phenotype z of Trait trt_num, or
+        y [n] (or [n][r]) in ascending-id order - on the dosage, given an intercept, the covariates
+        (_assoc_covars) and the first n_pcs genetic PCs (_calc_genetic_PCA, with its limits).  One
+        pass of gnx_assoc_cross over the packed genomes in fp64; the statistics are
+        sim/assoc.scan_stats'.  loci selects rows of the result on the host
+        -> dict: loci, beta, se, t, p, q [n_loci][r], maf, tested [n_loci], gif [r], df, ids,
+        trait_loci (the Trait's loci; None with y), pcs [n][n_pcs], kernel_ms"""
+        from ..sim import assoc as _as
+        who = 'run_gwas'
+        _need_genomes(self, who)
+        trait_loci = None
+        if y is None:
+            traits = self.gen_arch.traits
+            if not traits:
+                raise ValueError('%s: the Species has no Traits; give y' % who)
+            if isinstance(trt_num, bool) or trt_num not in traits:
+                raise ValueError('%s: no Trait %r (Traits: %s)' % (who, trt_num, sorted(traits)))
+            trait_loci = np.asarray(traits[trt_num].loci)
+        if isinstance(n_pcs, bool) or int(n_pcs) != n_pcs or n_pcs < 0:
+            raise ValueError('%s: n_pcs: a number of genetic PCs >= 0 (got %r)' % (who, n_pcs))
+        ids, slots = self._geno_sample(individs)
+        n = int(ids.size)
+        if y is not None:
+            y = np.asarray(y, dtype=np.float64)
+            y = y[:, None] if y.ndim == 1 else y
+            if y.ndim != 2 or y.shape[0] != n or y.shape[1] < 1 or not np.isfinite(y).all():
+                raise ValueError('%s: y: finite values [n = %d] in ascending-id order (got %s)'
+                                 % (who, n, y.shape))
+        cov = self._assoc_covars(who, covars, n)
+        n_cov = sum(len(self._env_layers(who, None)) if c is None else c for c, _ in cov)
+        _as.check_columns(n_cov + int(n_pcs) + (1 if y is None else y.shape[1]), who)
+        # ---- from here on the device is asked
+        if y is None:
+            y = self._field(nat.F_Z)[trt_num][slots].astype(np.float64)[:, None]
+        pcs = np.zeros((n, 0))
+        if n_pcs:
+            pcs = np.asarray(self._calc_genetic_PCA(int(n_pcs), individs=ids)[1], np.float64)
+        C = np.column_stack([f(slots) for _, f in cov] + [pcs])
+        res = _as.scan(lambda Y: self._dev.assoc_cross(Y, slots), n, y, C, 'gwas', False,
+                       min_maf, collinear_tol, calibrate)
+        return self._assoc_result(res, ids, loci, trait_loci, pcs=pcs)
+
+    def _run_lfmm(self, K, env_lyrs=None, lam=1e-5, individs=None, loci=None, min_maf=0.01,
+                  calibrate=True, collinear_tol=1e-8, env=None):
+        """a genotype-environment association scan with latent factors (LFMM2, Caye et al.
+        2019): per locus the regression of the dosage on each environmental layer (env_lyrs;
+        default: the layers the Traits are tied to, or all; env: a table [n][r] in ascending-id
+        order instead of layers), given the other layers and the K latent factors of the ridge
+        estimate (sim/assoc.latent_factors, from the exact Gram matrix of gnx_geno_gram: at most
+        8192 individuals).  K = 0: the plain linear model.  calibrate: p from t^2 / gif
+        -> dict as _run_gwas, with U [n][K] for pcs and trait_loci as a list, per tested layer the
+        loci of the Traits tied to it"""
+        from ..sim import assoc as _as
+        who = 'run_lfmm'
+        _need_genomes(self, who)
+        if isinstance(K, bool) or int(K) != K or K < 0:
+            raise ValueError('%s: K: a number of latent factors >= 0 (got %r)' % (who, K))
+        if isinstance(lam, bool) or not lam > 0:
+            raise ValueError('%s: lam: a positive ridge penalty (got %r)' % (who, lam))
+        ids, slots = self._geno_sample(individs)
+        n = int(ids.size)
+        if n > _as.GRAM_MAX:
+            raise ValueError('%s: at most %d individuals (the latent factors come from the n x n '
+                             'Gram matrix), got %d: pass n=... or individs=...'
+                             % (who, _as.GRAM_MAX, n))
+        if env is not None:
+            if env_lyrs is not None:
+                raise ValueError('%s: give env_lyrs or env, not both' % who)
+            X = np.asarray(env, dtype=np.float64)
+            X = X[:, None] if X.ndim == 1 else X
+            if X.ndim != 2 or X.shape[0] != n or X.shape[1] < 1 or not np.isfinite(X).all():
+                raise ValueError('%s: env: finite values [n = %d][r] in ascending-id order '
+                                 '(got %s)' % (who, n, X.shape))
+            lyrs, r = None, X.shape[1]
+        else:
+            lyrs = self._env_layers(who, env_lyrs)
+            r = len(lyrs)
+        # the columns sent: a basis of the factors and the layers, and the r residuals
+        _as.check_columns(int(K) + 2 * r, who)
+        if int(K) >= n:
+            raise ValueError('%s: K = %d latent factors for %d individuals' % (who, K, n))
+        # ---- from here on the device is asked
+        trait_loci = None
+        if lyrs is not None:
+            X = self._field(nat.F_E)[lyrs][:, slots].T.astype(np.float64)
+            traits = self.gen_arch.traits or {}
+            trait_loci = [np.unique(np.concatenate(
+                [np.asarray(t.loci, dtype=np.int64).ravel() for t in traits.values()
+                 if int(t.lyr_num) == l] + [np.zeros(0, np.int64)])) for l in lyrs]
+        U = _as.latent_factors(self._dev.geno_gram(slots), X, int(K), lam) if K else \
+            np.zeros((n, 0))
+        res = _as.scan(lambda Y: self._dev.assoc_cross(Y, slots), n, X, U, 'gea', True, min_maf,
+                       collinear_tol, calibrate)
+        return self._assoc_result(res, ids, loci, trait_loci, U=U)
+
     # -- Mantel tests and MMRR (sim/mmrr.py; csrc/gnx_mantel.hip) --------------------------
     def _dist_predictors(self, who, predictors, env_lyrs, trts):
         """the device columns [(field, index), ...] of each named predictor: 'geo' = (x, y),

@@ -83,6 +83,11 @@ _NOT_TILED = {
     # order and the prior comes from calc_ancestry)
     '_calc_local_ancestry': 'calc_local_ancestry with a Species tiled over several GPUs is '
                             'not implemented; run the model on one GPU',
+    # association scans (the sums add over tiles, but in a fixed order across them)
+    '_run_gwas': 'run_gwas with a Species tiled over several GPUs is not implemented; run the '
+                 'model on one GPU',
+    '_run_lfmm': 'run_lfmm with a Species tiled over several GPUs is not implemented; run the '
+                 'model on one GPU',
     # identity tracts (a pair of individuals of different tiles: a gather of the sample)
     '_calc_roh': 'calc_roh with a Species tiled over several GPUs is not '
                  'implemented; run the model on one GPU',

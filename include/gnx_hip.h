@@ -1127,6 +1127,33 @@ int gnx_lai_paint(gnx_state* h, int64_t n, const int64_t* slots /*NULL: all livi
                   double* loglik, double* anc_hap, double* anc_locus, int32_t* switches,
                   uint8_t* calls, int64_t* batches, double* kernel_ms);
 
+/* ---- per-locus association scans (csrc/gnx_assoc.hip; the reference has no such analysis) ----
+ * The cross-products of the dosages d = a + b in {0, 1, 2} (a, b the bits of the two homologues)
+ * of the sample with a HOST matrix Y fp64 [n][m], 1 <= m <= 32 (n, slots as in the genetic PCA
+ * calls, rows of Y in the order of the slots), and the integer moments of d per locus, from one
+ * pass over the packed genomes.  Outputs, HOST buffers:
+ *   DtY fp64 [L][m]   DtY[l][j] = sum over i of d_il Y_ij
+ *   s1  int64 [L]     sum over i of d_il        (exact: counted bits)
+ *   s2  int64 [L]     sum over i of d_il^2      (exact: s1 + 2 * the individuals with both bits)
+ * Order of the fp64 sums, fixed by (n, L) alone.  The individuals 0 .. n - 1 (positions in the
+ * sample) are cut into stretches of `*stretch` consecutive ones, the last one ragged:
+ *   tiles = ceil(n / 64), lines = gnx_words_per_hom(L) / 16,
+ *   want = min(tiles, 32, max(1, 2048 / lines))   (integer division),
+ *   *stretch = 64 ceil(tiles / want),  *stretches = ceil(n / *stretch).
+ * Within a stretch acc = fma(d, y, acc) from +0 over ascending individuals (d y is exact, so this
+ * is the rounded acc + d y, the same with or without a fused multiply-add); the stretches' sums
+ * are then added left to right from the first.  No atomics: a repeated call is byte-equal, and a
+ * column's sums do not depend on m or on its position in Y.  The partial sums take
+ * 8 m L *stretches bytes of device scratch, under 0.6 GB for L <= 2^21 and 8 m L beyond.
+ * *stretch, *stretches, *kernel_ms (each may be NULL): the rule's result and the HIP-event time of
+ * the call's kernels.  Preconditions as the genetic PCA calls; no individual, genome or later
+ * draw is changed.  Refused (return 1) before anything is launched: no genomes, ghost records, m
+ * outside 1..32, n outside 1..2^30, a null pointer, a NaN or infinity in Y, a slot out of range,
+ * n != N with slots NULL.                                                                      */
+int gnx_assoc_cross(gnx_state* h, int64_t n, const int64_t* slots /*NULL: all living*/, int32_t m,
+                    const double* Y, double* DtY, int64_t* s1, int64_t* s2, int64_t* stretch,
+                    int64_t* stretches, double* kernel_ms);
+
 /* ---- lineages through the recorded pedigree (csrc/gnx_lineage.hip; reference
  *      structs/genome.py:1638-1782 _get_lineage_dicts, structs/species.py:1242-1343) ---------
  * The pedigree is recorded on the host (geonomics_amd/structs/pedigree.py, TreeTables.
