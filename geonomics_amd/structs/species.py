@@ -108,6 +108,76 @@ def _introduction_plan(n, coords, individs, source_ids, land_dim):
     return chosen, xy.astype(np.float32)
 
 
+WALK_GATE = 0.66            # device-driven steps only while N <= WALK_GATE * capacity
+WALK_MAX_PIECE = 256
+WALK_EVIDENCE = 8           # steps of unchanged conditions that size a piece by what was seen
+WALK_TAIL = 6.0             # standard deviations above the mean in the worst-case birth bound
+
+
+def _births_bound(n, b, lam, births_fixed):
+    """Births one step cannot exceed, from n individuals.  Every individual is the focal one
+    of at most one pair and only if its Bernoulli(b) draw says so, so the pairs number at most
+    Bin(n, b) <= n; a pair has lam offspring (n_births_fixed) or Poisson(lam).  Bernstein's
+    inequality, P(X >= m + t) <= exp(-t^2 / (2 (v + t / 3))), with t = z sqrt(v) + 2 z and
+    z = WALK_TAIL = 6 leaves less than exp(-18) = 1.6e-8 per step for the binomial and for the
+    Poisson sum in turn; fixed births are bounded by lam * n outright."""
+    n, b, lam = float(n), min(max(float(b), 0.0), 1.0), max(float(lam), 0.0)
+    z = WALK_TAIL
+    pairs = min(n, n * b + z * np.sqrt(n * b * (1 - b)) + 2 * z)
+    if births_fixed:
+        return float(int(lam) * pairs)
+    m = lam * pairs
+    return float(m + z * np.sqrt(m) + 2 * z)
+
+
+def _walk_piece(steps_left, n, cap, R, b, lam, births_fixed, recent_Nt=()):
+    """How many of the `steps_left` main steps the next gnx_walk call takes when n individuals
+    live in a device state of cap slots - or 0: hand the steps to the function queue, whose
+    steps can move the population to a larger state (Species._grow_device).  A walk cannot, and
+    one that runs out of slots is fatal, so a piece must fit whatever its births are.
+
+    recent_Nt: the population sizes after the latest steps taken under the conditions that
+    hold now (nothing set or moved by a script since; the oldest first).
+    - Fewer than WALK_EVIDENCE + 1 of them: the piece is the longest over which the compounded
+      worst case n -> n + _births_bound(n), nobody dying, stays within cap.
+    - Otherwise the largest growth of one step among the last WALK_EVIDENCE, g, is taken for
+      what these conditions can do.  A population that did not grow by more than
+      max(0.02, R / 4) in any of them is at its equilibrium, where births and the
+      density-dependent deaths cancel: it may use half the free slots at a linear
+      max(0.02, R / 4) * n per step (the rule of every earlier version).  One that grew faster
+      compounds 1 + 1.5 g per step (a margin of one half), up to half the free slots.  Either
+      piece is shortened, down to 0, until the worst births of one more step
+      (_births_bound) fit on top of the population it assumes at its end.
+    Above WALK_GATE * cap nothing runs on the device."""
+    steps_left, n, cap = int(steps_left), int(n), int(cap)
+    if steps_left < 1 or n > WALK_GATE * cap:
+        return 0
+    most = min(steps_left, WALK_MAX_PIECE)
+    n = max(n, 1)
+    room = max(cap - n, 1)
+    recent = [float(v) for v in recent_Nt][-(WALK_EVIDENCE + 1):]
+    if len(recent) == WALK_EVIDENCE + 1 and min(recent) > 0:
+        g = max(max(b_ / a_ - 1.0 for a_, b_ in zip(recent[:-1], recent[1:])), 0.0)
+        calm = max(0.02, float(R) * 0.25)
+        if g <= calm:
+            k = int(max(1, min(most, 0.5 * room / (calm * n))))
+            seen = lambda q: n + q * calm * n
+        else:
+            k = min(most, int(np.log1p(0.5 * room / n) / np.log1p(1.5 * g)))
+            seen = lambda q: n * (1 + 1.5 * g) ** q
+        # (... and where that growth would leave it, a step's worst births must still fit)
+        while k > 0 and seen(k) + _births_bound(seen(k), b, lam, births_fixed) > cap:
+            k -= 1
+        return k
+    k, top = 0, float(n)
+    while k < most:
+        top += _births_bound(top, b, lam, births_fixed)
+        if top > cap:
+            break
+        k += 1
+    return k
+
+
 _INTRO_SPP_ATTRS = ('K_layer', 'selection', 'sex_ratio', 'move')
 _INTRO_GEN_ARCH_ATTRS = ('sex', 'use_tskit', 'x')
 _INTRO_RECOMB_ATTRS = ('_rates', '_r_distr_alpha', '_r_distr_beta', '_jitter_breakpoints')
@@ -174,6 +244,8 @@ class Species(SpeciesAnalyses):
         self.Nt = []
         self.n_births = []
         self.n_deaths = []
+        self._same_conditions_since = 0     # index into Nt (_conditions_changed)
+        self._params_seen = None            # (_check_conditions)
         self._K = None
         self.K_layer = None
         self.K_factor = None
@@ -229,6 +301,7 @@ class Species(SpeciesAnalyses):
         """Assigning Species.K (demographic change events do, ops/change.py:633-651)
         makes the raster the device's explicit K."""
         self._K = val
+        self._conditions_changed()
         if self.__dict__.get('_dev', None) is not None and val is not None:
             self._dev.set_K_raster(np.asarray(val, dtype=np.float64))
             self._K_explicit = True
@@ -245,6 +318,23 @@ class Species(SpeciesAnalyses):
                 self._dev.set_species_params(self._species_params_struct(self._land_ref))
             return
         object.__setattr__(self, attr, val)
+
+    def _conditions_changed(self):
+        """the carrying capacity or the positions were set from outside the time steps: the
+        population sizes recorded so far say nothing about what the next steps can do
+        (_walk_piece sizes a device walk's pieces by those recorded since)"""
+        self.__dict__['_same_conditions_since'] = len(self.__dict__.get('Nt', ()))
+
+    def _params_signature(self):
+        return repr(sorted(self._pv.__dict__.items(), key=lambda kv: kv[0]))
+
+    def _check_conditions(self):
+        """... or a parameter was, by whatever way, or individuals were removed or added:
+        seen here, at the start of a device walk, not reported by whoever did it"""
+        sig = self._params_signature()
+        if sig != self._params_seen or (self.Nt and len(self) != self.Nt[-1]):
+            self._conditions_changed()
+        self._params_seen = sig
 
     def _make_change(self, verbose=False):
         """reference structs/species.py:836-838"""
@@ -334,6 +424,8 @@ class Species(SpeciesAnalyses):
             dev.set_id_order(1)
         self._land_ref = land
         self._dev = dev
+        if self.__dict__.get('_params_seen') is None:
+            self._params_seen = self._params_signature()
         self._upload_gen_arch()
         return dev
 
@@ -413,6 +505,7 @@ class Species(SpeciesAnalyses):
                     y[pos[i]] = ny
         self._pending_xy = {}
         self._dev.set_positions(x, y)
+        self._conditions_changed()
 
     def __getitem__(self, idx):
         ids = self._field(nat.F_ID)
@@ -463,6 +556,7 @@ class Species(SpeciesAnalyses):
         """reference structs/species.py:545-546: K = K-layer raster * K_factor (this
         also drops whatever a demographic change had scaled K to, as there)"""
         self._K = land[self.K_layer].rast * self.K_factor
+        self._conditions_changed()
         if self._dev is not None:
             self._dev.upload_layer(self.K_layer, land[self.K_layer].rast)
             self._dev.set_K_raster(None)
@@ -550,18 +644,19 @@ class Species(SpeciesAnalyses):
         dev = self._dev
         with_selection = self.selection and self.burned
         done = 0
+        self._check_conditions()
         while done < T and not self.extinct:
             # the device-driven steps cannot grow the device state (the queue's steps can,
             # _grow_device): they run in pieces, and only while the population leaves a third
-            # of the capacity free - a piece whose births would not fit ends in an error
-            n_now = len(self)
-            if n_now > 0.66 * self._cap:
+            # of the capacity free - a piece whose births would not fit ends in an error, so
+            # _walk_piece sizes it to fit, or hands the remaining steps to the queue
+            pv = self._pv
+            chunk = _walk_piece(T - done, len(self), self._cap, getattr(pv, 'R', 0.5), pv.b,
+                                pv.n_births_distr_lambda, pv.n_births_fixed,
+                                self.Nt[max(self._same_conditions_since, len(self.Nt) - WALK_EVIDENCE - 1, 0):])
+            if chunk < 1:
                 break
-            # (the fuller the device, the shorter the piece: a population can grow by about R per
-            # step - a piece must not be able to outgrow the free third)
-            room = max(self._cap - n_now, 1)
-            grow = max(0.02, float(getattr(self._pv, 'R', 0.5)) * 0.25) * max(n_now, 1)
-            chunk = int(max(1, min(T - done, 256, 0.5 * room / grow)))
+            step0, done0 = dev.step_index, done
             try:
                 dev.walk(chunk, False, with_selection)
             except nat.GnxError as e:
@@ -571,7 +666,7 @@ class Species(SpeciesAnalyses):
                 # half-way (aged and moved, not yet born).  The library keeps such steps out
                 # of gnx_walk_history; here the run ends loudly, as the reference would on an
                 # inconsistent population - the pieces above are sized so that it does not
-                # happen (0.66 of the capacity, half the free room per piece).
+                # happen (_walk_piece).
                 if 'capacity exceeded' in str(e):
                     raise nat.GnxError(
                         '%s - inside Model.walk the device-driven steps cannot move the '
@@ -594,6 +689,11 @@ class Species(SpeciesAnalyses):
                     self.extinct = True
                     break
                 self.Nt.append(int(a + b - d))
+            if self.extinct:
+                # (the library went on stepping the empty population to the end of the piece; the
+                # queue stops at the step that killed the last ones, and so does the clock of
+                # the draws: whoever is introduced next meets the same draws on either route)
+                dev.step_index = step0 + (done - done0)
         return done
 
     def _grow_device(self, factor=2.0):
@@ -933,6 +1033,7 @@ class Species(SpeciesAnalyses):
                     sex=d.download(nat.F_SEX), id=d.download(nat.F_ID),
                     step=d.step_index, Nt=list(self.Nt), n_births=list(self.n_births),
                     n_deaths=list(self.n_deaths), burned=self.burned, t=self.t,
+                    same_conditions_since=self._same_conditions_since,
                     max_ind_idx=self.max_ind_idx, extinct=self.extinct,
                     spat=copy.deepcopy(self._burnin_spat_stats), geno=None,
                     K=None if self._K is None else np.array(self._K, copy=True),
@@ -963,6 +1064,9 @@ class Species(SpeciesAnalyses):
             d.set_K_raster(None)
             self._K_explicit = False
         d.upload_population(snap['x'], snap['y'], snap['age'], snap['sex'], snap['id'])
+        # (the upload leaves the largest LIVING id behind; offspring are numbered from the largest
+        # ever given, as _grow_device and add_individuals have it)
+        d.set_max_id(snap['max_ind_idx'])
         if snap['geno'] is not None:
             d.upload_genomes(snap['geno'])
         self._genomes_assigned = snap['geno'] is not None
@@ -971,6 +1075,7 @@ class Species(SpeciesAnalyses):
         self.Nt = list(snap['Nt'])
         self.n_births = list(snap['n_births'])
         self.n_deaths = list(snap['n_deaths'])
+        self._same_conditions_since = snap.get('same_conditions_since', 0)
         self.burned = snap['burned']
         self.t = snap['t']
         self.max_ind_idx = snap['max_ind_idx']

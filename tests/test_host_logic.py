@@ -569,3 +569,103 @@ def test_library_env_switches_are_listed_in_design():
     listed = set(re.findall(r'^\| `(GNX_[A-Z0-9_]+)` \|', table, re.M))
     assert read <= listed, 'read under csrc/ but missing from DESIGN.md 5.3: %s' % sorted(read - listed)
     assert listed <= read, 'listed in DESIGN.md 5.3 but read nowhere under csrc/: %s' % sorted(listed - read)
+
+
+def test_births_bound_holds_for_the_draws_it_describes():
+    """_births_bound against 10^5 steps' worth of the draws themselves (Bin(n, b) pairs, lam or
+    Poisson(lam) offspring each): never exceeded, and not absurdly loose"""
+    from geonomics_amd.structs.species import _births_bound
+    rng = np.random.RandomState(0)
+    for n, b, lam in [(1, 0.2, 1), (7, 0.9, 1), (320, 0.2, 1), (320, 0.2, 3), (5000, 0.5, 2),
+                      (100000, 0.2, 1), (50, 1.0, 4), (50, 0.0, 4)]:
+        pairs = rng.binomial(n, b, 100000)
+        fixed, pois = _births_bound(n, b, lam, True), _births_bound(n, b, lam, False)
+        assert (lam * pairs).max() <= fixed <= lam * n
+        assert rng.poisson(lam * pairs).max() <= pois
+        if n >= 320 and 0 < b < 1:
+            assert fixed < 2 * lam * n * b and pois < 3.5 * lam * n * b
+    # increasing in n: compounding it from the top of the step before is a bound for the piece
+    for fixed in (True, False):
+        v = [_births_bound(n, 0.2, 3, fixed) for n in range(1, 3000)]
+        assert (np.diff(v) >= 0).all()
+
+
+def test_walk_piece_gate_equilibrium_and_worst_case():
+    from geonomics_amd.structs.species import _walk_piece, _births_bound, WALK_GATE
+    from _model_walk import parent_piece as _parent_piece
+    kw = dict(R=0.5, b=0.2, lam=1, births_fixed=True)
+    calm = [318, 322, 316, 325, 320, 317, 323, 319, 321, 320]
+    # the gate: above 0.66 of the slots nothing runs on the device, whatever was seen
+    assert WALK_GATE == 0.66
+    for recent in ((), calm):
+        assert _walk_piece(40, 988, 1496, recent_Nt=recent, **kw) == 0
+        assert _walk_piece(40, 987, 1496, recent_Nt=[987] * 10, **kw) >= 1
+        assert _walk_piece(0, 300, 1496, recent_Nt=recent, **kw) == 0
+    # at equilibrium: exactly the pieces of the version before (~14, 14, 12 of walk(40) in 1496
+    # slots), never more than asked for or than 256
+    for n, cap, left in [(320, 1496, 40), (320, 1496, 12), (310, 1496, 26), (320, 2149, 12),
+                         (100000, 251024, 1000), (900, 1496, 40), (320, 631024, 5)]:
+        recent = [n + d for d in (-3, 2, -4, 5, 0, -3, 3, -1, 1, 0)]
+        assert _walk_piece(left, n, cap, recent_Nt=recent, **kw) == _parent_piece(left, n, cap)
+    assert _walk_piece(40, 320, 1496, recent_Nt=calm, **kw) == 14
+    # ... shortened where a step's worst births would not fit on top of R / 4 a step: close to the
+    # gate, or with many offspring per pair
+    assert _parent_piece(40, 987, 1496) == 2 and \
+        _walk_piece(40, 987, 1496, recent_Nt=[987] * 9, **kw) == 1
+    assert _parent_piece(40, 600, 1496) == 5 and \
+        _walk_piece(40, 600, 1496, recent_Nt=[600] * 9, **dict(kw, lam=3)) == 2
+    assert _walk_piece(40, 950, 1496, recent_Nt=[950] * 9, **dict(kw, lam=3)) == 0
+    for n in range(50, 988, 7):
+        k = _walk_piece(40, n, 1496, recent_Nt=[n] * 9, **dict(kw, lam=2))
+        assert k <= _parent_piece(40, n, 1496)
+        top = n + k * 0.125 * n
+        assert k == 0 or top + _births_bound(top, 0.2, 2, True) <= 1496
+    assert _walk_piece(1000, 100, 10 ** 6, recent_Nt=[100] * 9, **kw) == 256
+    assert _walk_piece(40, 320, 1496, recent_Nt=[320] * 9, **dict(kw, R=0.01)) == \
+        _parent_piece(40, 320, 1496, R=0.01) == 40
+    # nothing seen under these conditions (a script just set something), or too little: the
+    # compounded worst case must fit, for any parameters
+    for n, cap, b, lam, fixed in [(320, 1496, 0.2, 1, True), (380, 1496, 0.2, 3, True),
+                                  (380, 1496, 0.2, 3, False), (900, 1496, 0.2, 3, True),
+                                  (10, 1496, 1.0, 5, True), (320, 2149, 0.4, 1, True),
+                                  (320, 631024, 0.2, 1, True)]:
+        for recent in ((), calm[:8]):
+            k = _walk_piece(30, n, cap, 0.5, b, lam, fixed, recent_Nt=recent)
+            top = float(n)
+            for _ in range(k):
+                top += _births_bound(top, b, lam, fixed)
+            assert top <= cap, (n, cap, k)
+            assert k == 30 or top + _births_bound(top, b, lam, fixed) > cap    # ... and the longest
+    assert _walk_piece(30, 380, 1496, 0.5, 0.2, 3, True) == 2
+    assert _walk_piece(30, 900, 1496, 0.5, 0.2, 3, True) == 0          # the queue can grow, go there
+    assert _walk_piece(30, 320, 2149, 0.5, 0.2, 1, True) == 7
+    # a population seen growing compounds what it was seen to do, with a margin of one half, up
+    # to half the free slots - and shorter than the linear rule, which it replaces
+    grew = [300, 330, 380, 450, 540, 650, 780, 930, 1100]
+    k = _walk_piece(30, 1100, 4016, recent_Nt=grew, **kw)
+    g = max(b_ / float(a_) for a_, b_ in zip(grew[:-1], grew[1:])) - 1
+    assert 1100 * (1 + 1.5 * g) ** k <= 1100 + 0.5 * (4016 - 1100) < 1100 * (1 + 1.5 * g) ** (k + 1)
+    assert 1 <= k < _parent_piece(30, 1100, 4016)
+    assert _walk_piece(30, 2500, 4016, recent_Nt=[v * 2.4 for v in grew], **kw) == 0
+    # ... and never further than where a step's worst births still fit: a fecund population whose
+    # size jumps from step to step (b * lam = 2: a step can double it) goes to the queue
+    noisy = [2300, 2500, 2200, 2600, 2400, 2750, 2500, 2900, 2800]
+    assert 2800 + _births_bound(2800, 0.5, 4, True) > 5000
+    assert _walk_piece(30, 2800, 5000, 0.5, 0.5, 4, True, noisy) == 0
+    assert _walk_piece(30, 2800, 5000, 0.5, 0.5, 4, False, noisy) == 0
+    for b, lam, fixed in [(0.5, 4, True), (0.5, 1, True), (0.3, 2, False), (0.2, 1, True)]:
+        for scale, cap in [(1.0, 5000), (0.5, 5000), (0.2, 5000), (1.0, 20000)]:
+            rec = [v * scale for v in noisy]
+            n = int(rec[-1])
+            k = _walk_piece(30, n, cap, 0.5, b, lam, fixed, rec)
+            g = max(y / x for x, y in zip(rec[:-1], rec[1:])) - 1
+            top = n * (1 + 1.5 * g) ** k
+            assert k == 0 or top + _births_bound(top, b, lam, fixed) <= cap, (b, lam, scale, cap)
+            assert k == 0 or top <= n + 0.5 * (cap - n)
+    assert _walk_piece(30, 560, 20000, 0.5, 0.2, 1, True, [v * 0.2 for v in noisy]) >= 5
+    # only the last eight steps count: growth that is over does not shorten the pieces for good
+    assert _walk_piece(30, 1100, 4016, recent_Nt=grew + [1100] * 8, **kw) == \
+        _parent_piece(30, 1100, 4016)
+    # a shrinking population is not evidence of growth
+    assert _walk_piece(30, 300, 1496, recent_Nt=[900, 800, 700, 600, 500, 450, 400, 350, 300],
+                       **kw) == _parent_piece(30, 300, 1496)
