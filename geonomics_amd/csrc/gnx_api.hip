@@ -598,6 +598,7 @@ extern "C" int gnx_upload_rasters(gnx_state* h, const float* rasts) {
   size_t n = (size_t)h->cfg.n_layers * h->cfg.W * h->cfg.H;
   HIPCHK(hipMemcpyAsync(h->rast, rasts, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  h->e_stale = true;
   return 0;
 }
 
@@ -610,6 +611,7 @@ extern "C" int gnx_upload_layer(gnx_state* h, int32_t layer, const float* rast) 
   HIPCHK(hipMemcpyAsync(h->rast + layer * n, rast, n * sizeof(float), hipMemcpyHostToDevice,
                         h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  h->e_stale = true;
   return 0;
 }
 

@@ -457,6 +457,7 @@ extern long long g_host_steps;
 static int walk_prepare(gnx_state* h, int64_t* T, bool burn, bool sel, bool* dd_ok) {
   *dd_ok = gnx_dd_eligible(h, burn) && *T > 0;
   if (!*dd_ok) return 0;
+  h->e_stale = false;       // (eligible: the species moves, k_move writes e of everybody)
   DDExtra* x = extra(h);
   if (x->epoch != h->cfg_epoch) {          // parameters, traits or paths were set since
     dd_drop_graphs(h);

@@ -674,6 +674,10 @@ struct gnx_state {
   bool move_ahead_ok = false;
   bool moved_ahead = false;
   hipEvent_t ev_moved = nullptr;
+  // A raster was uploaded since the last step: the e column still holds what that step's mating
+  // sampled (the reference samples everybody at the end of every mating, structs/species.py:804).
+  // The next step's movement rewrites e of everybody; where nobody moves, its gnx_l_age gathers.
+  bool e_stale = false;
   bool move_writes_keys = false;     // set around the movement of gnx_step           // k_move has written this step's sort keys
   int n_bin_blocks = 0;
   double* nodes = nullptr;           // [Jy][Jx] scratch node values

@@ -104,6 +104,12 @@ int gnx_l_age(gnx_state* h) {
   hipLaunchKernelGGL(k_age, dim3(gnx_grid(h->N, 256)), dim3(256), 0, h->stream, h->N,
                      h->soa[h->cur].age);
   HIPCHK(hipGetLastError());
+  // the step of a species that stays put, the first after a raster was uploaded: nothing else
+  // on its chain writes e of the adults (k_move does for a species that moves)
+  if (h->e_stale && !h->sp.move) {
+    h->e_stale = false;
+    GNXCHK(gnx_l_gather_e(h, 0, h->N));
+  }
   return 0;
 }
 
@@ -475,6 +481,7 @@ int gnx_l_move(gnx_state* h, bool inc_age, const float* inj_theta, const float* 
   if (apply) {                            // bins counted before a movement are stale
     h->fb_adults = false;
     h->fb_pending = false;
+    h->e_stale = false;                   // (e of everybody alive is written below)
   }
   const gnx_config& c = h->cfg;
   const gnx_species_params& sp = h->sp;

@@ -12,7 +12,10 @@ on the device:
                         kernels sample the conductance neighbourhood from the
                         raster that is resident (reference builds one LUT per
                         step of the event, change.py:576-609, at the same
-                        timesteps).
+                        timesteps).  The individuals' e keeps what the last mating
+                        sampled until the next step, whose mating (movement, for a
+                        species that moves) samples everybody from the new raster
+                        (reference structs/species.py:582-585,804).
   * demographic change - `spp.K` is scaled (change.py:633-651); the K setter
                         uploads the raster as the device's explicit K.
   * life-history change - `setattr(spp, parameter, val)` (change.py:744-752);

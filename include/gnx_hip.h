@@ -129,7 +129,10 @@ int  gnx_set_stream(gnx_state* h, void* hip_stream);
 int  gnx_synchronize(gnx_state* h);
 
 /* ---- landscape / species setup ----------------------------------------- */
-/* Landscape layers: lyr.rast for every Layer (structs/landscape.py:34-120)  */
+/* Landscape layers: lyr.rast for every Layer (structs/landscape.py:34-120).
+ * An upload leaves the individuals' e as the last mating sampled it; the next
+ * step samples everybody from the new raster (its movement, or - where the
+ * species does not move - one gather behind its age kernel).                */
 int gnx_upload_rasters(gnx_state* h, const float* rasts /*[n_layers][H][W]*/);
 int gnx_upload_layer(gnx_state* h, int32_t layer, const float* rast);
 /* Species.K given explicitly, double [H][W] (demographic change events scale it:

@@ -167,7 +167,7 @@ def find_pairs(s):
         mate = choose_mates_fast(s)
     else:
         mate = O.choose_mates(s.x, s.y, s.id, p.mating_radius, s.seed, s.step,
-                              mode=p.mate_mode)
+                              mode=p.mate_mode, dim=(s.W, s.H))
     has = (mate >= 0) & keep
     m0 = np.maximum(mate, 0)
     has &= (s.age >= p.repro_age[0]) & (s.age[m0] >= p.repro_age[1])
@@ -270,6 +270,11 @@ def pop_dynamics(s, burn=False, with_selection=True):
         my = (s.y[pairs[:, 0]] + s.y[pairs[:, 1]]) / F(2.0)
         VP = s.lat.node_density(mx, my)
     B = mate(s, pairs, burn)
+    if not s.p.move and s.N:
+        # the reference samples everybody's habitat again at the end of mating
+        # (structs/species.py:804): where nobody moved this is what carries a changed raster
+        # to the adults.  (Movers were all sampled by move(): the same values either way.)
+        s.e = O.gather_e(list(s.rasts), s.x, s.y).astype(F)
     VN = s.lat.node_density(s.x, s.y)
     pd_, _ = death_probs(s, with_selection and not burn, VN, VP)
     u = D.death_draws(s.seed, s.id, s.step).astype(np.float64)

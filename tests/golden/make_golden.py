@@ -868,15 +868,55 @@ def g17_pedigree_segments():
     save('g17_pedigree_segments', **out)
 
 
+def g18_change_e():
+    """A whole reference model whose species does not move, under a layer-change
+    event on the layer its trait reads: after each of 8 main steps the layer-1
+    raster that was in force during the step and the id, position and e of
+    everybody alive.  (The reference re-samples everybody's e at the end of every
+    mating, structs/species.py:804: a change reaches those who stay put one step
+    later.)"""
+    # (K_factor 0.75: with 0.6 the species that stays put dwindles to ~25 in the burn-in)
+    p = base_params(dim=(20, 20), N=120, L=40, traits=True, seed=5, K_factor=0.75)
+    lyrs = p['landscape']['layers']
+    k1 = [*lyrs][1]
+    start_rast = lyrs[k1]['init']['defined']['rast']
+    end_rast = start_rast[:, ::-1].copy()
+    lyrs[k1]['change'] = {0: {'change_rast': end_rast, 'start_t': 2, 'end_t': 6,
+                              'n_steps': 3}}
+    sp = p['comm']['species'][[*p['comm']['species']][0]]
+    sp['movement']['move'] = False
+    p['model']['T'] = 8
+    mod = gnx.make_model(gnx.make_params_dict(p, 'golden'))
+    spp = mod.comm[0]
+    assert not spp._move
+    mod.walk(T=400, mode='burn', verbose=False)
+    assert mod.comm.burned
+    out = {'start_rast': start_rast, 'end_rast': end_rast}
+    n = []
+    for t in range(8):
+        rast = mod.land[1].rast.copy()
+        mod.walk(1, 'main', verbose=False)
+        inds = list(spp.values())
+        n.append(len(inds))
+        out['rast_%d' % t] = rast
+        out['ids_%d' % t] = np.array([ind.idx for ind in inds], np.int64)
+        out['x_%d' % t] = np.array([ind.x for ind in inds], np.float64)
+        out['y_%d' % t] = np.array([ind.y for ind in inds], np.float64)
+        out['e_%d' % t] = np.array([ind.e for ind in inds], np.float64)
+    print('g18 N per step', n, flush=True)
+    save('g18_change_e', **out)
+
+
 if __name__ == '__main__':
     which = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4', 'g5', 'g7', 'g8', 'g9',
-                             'g10', 'g11', 'g12', 'g13', 'g14', 'g15', 'g16', 'g17']
+                             'g10', 'g11', 'g12', 'g13', 'g14', 'g15', 'g16', 'g17',
+                             'g18']
     fns = {'g1': g1_crossover, 'g2': g2_recomb_paths,
            'g3': g3_phenotype_fitness, 'g4': g4_density,
            'g5': g5_demography, 'g7': g7_movement, 'g8': g8_pairing,
            'g9': g9_starting_genomes, 'g10': g10_envelopes,
            'g11': g11_conductance, 'g12': g12_stats, 'g13': g13_change,
            'g14': g14_data, 'g15': g15_wf, 'g16': g16_spatial_tester,
-           'g17': g17_pedigree_segments}
+           'g17': g17_pedigree_segments, 'g18': g18_change_e}
     for w in which:
         fns[w]()
