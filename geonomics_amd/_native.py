@@ -76,6 +76,7 @@ EXPORTS = [
     'gnx_circuit_info',
     'gnx_lai_paint',
     'gnx_assoc_cross',
+    'gnx_coal_times', 'gnx_coal_segments',
 ]
 
 
@@ -1738,6 +1739,115 @@ class Device:
     def lineage_forget(self):
         """drop the device's copy of the node table: the next lineage call uploads its own"""
         self._chk(self.lib.gnx_lineage_forget(self.h))
+
+    # -- pairwise coalescence through the recorded pedigree (csrc/gnx_coal.hip) -------------
+    COAL_TIMES_OUT = ('pair_sum', 'pair_cnt', 'locus_sum', 'locus_cnt', 'locus_max', 'thist',
+                      'mrca')
+
+    def _coal_args(self, node_tab, birth_t, nodes, loci):
+        tab = _arr(node_tab, np.int32)
+        bt = _arr(birth_t, np.int32).ravel()
+        if tab.ndim != 2 or tab.shape != (2 * bt.size, 2):
+            raise ValueError('node_tab: int32 [2 n_rows][2] with birth_t [n_rows]')
+        nodes = _arr(nodes, np.int32).ravel()
+        loci = _arr(loci, np.int32).ravel()
+        args = (self.h, C.c_int64(bt.size), _ptr(tab, C.c_int32), _ptr(bt, C.c_int32),
+                C.c_int64(nodes.size), _ptr(nodes, C.c_int32), int(loci.size),
+                _ptr(loci, C.c_int32))
+        # (the library refuses fewer than 2 and more than 4096 nodes before it writes)
+        n = int(nodes.size) if 2 <= nodes.size <= 4096 else 1
+        return (tab, bt, nodes, loci), args, n, int(loci.size)
+
+    def _coal_max_ago(self, max_time_ago):
+        """max_time_ago (None: no limit) as the library's max_ago, where negative means none"""
+        if max_time_ago is not None and not float(max_time_ago) >= 0:
+            raise ValueError('max_time_ago: >= 0, or None for no limit (got %r)' % (max_time_ago,))
+        return self._ago(max_time_ago, -1, False)
+
+    def coal_times(self, node_tab, birth_t, nodes, loci, t_curr, max_time_ago=None,
+                   time_edges=None, want=('pair_sum', 'pair_cnt', 'locus_sum', 'locus_cnt',
+                                          'locus_max'), max_work=0):
+        """gnx_coal_times (include/gnx_hip.h): the coalescence times of every two of the sample
+        `nodes` (2..4096, distinct) at `loci` (any order) through the pedigree
+        (TreeTables.node_table()).  max_time_ago None: no limit; time_edges int32 [2..65]
+        ascending: 'thist' is computed too.  want: the outputs to compute ('mrca' int32
+        [n_loci][n_pairs] on request only).  max_work <= 0: only the work is computed
+        -> dict(work, and the arrays named in want, 'thist' with time_edges); without the arrays
+        when max_work <= 0"""
+        bad = set(want) - set(self.COAL_TIMES_OUT) | ({'thist'} & set(want))
+        if bad:
+            raise ValueError('want: unknown output %s (thist comes with time_edges)'
+                             % sorted(bad))
+        keep, args, n, nl = self._coal_args(node_tab, birth_t, nodes, loci)
+        max_ago = self._coal_max_ago(max_time_ago)
+        run = max_work > 0
+        e = None
+        out = {}
+        if time_edges is not None:
+            e = _arr(time_edges, np.int32).ravel()
+            out['thist'] = np.zeros(e.size - 1 if 2 <= e.size <= 65 else 1, np.int64)
+            if e.size == 0:
+                e = np.zeros(1, np.int32)
+        m, ml = (n, nl) if run else (1, 1)
+        shapes = dict(pair_sum=((m, m), np.int64), pair_cnt=((m, m), np.int32),
+                      locus_sum=((ml,), np.int64), locus_cnt=((ml,), np.int64),
+                      locus_max=((ml,), np.int32), mrca=((ml, m * (m - 1) // 2), np.int32))
+        for k in want:
+            out[k] = np.zeros(*shapes[k])
+        work = np.zeros(1, np.int64)
+        ct = dict(pair_cnt=C.c_int32, locus_max=C.c_int32, mrca=C.c_int32)
+        self._chk(self.lib.gnx_coal_times(
+            *args, int(t_curr), max_ago,
+            C.c_int32(0 if time_edges is None else int(np.size(time_edges))),
+            _ptr(e, C.c_int32), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
+            *[_ptr(out.get(k), ct.get(k, C.c_int64)) for k in self.COAL_TIMES_OUT]))
+        if not run:
+            return dict(work=int(work[0]))
+        return dict(out, work=int(work[0]))
+
+    def coal_segments(self, node_tab, birth_t, nodes, loci, pos, t_curr, brk=None,
+                      max_time_ago=None, min_loci=1, min_len=0, edges=None, cover=False,
+                      max_work=0):
+        """gnx_coal_segments (include/gnx_hip.h): the stretches of the strictly ascending `loci`
+        over which two of the sample `nodes` keep one most recent common ancestor no older than
+        max_time_ago (identity by descent).  pos int64 [n_loci] non-decreasing; brk uint8
+        [n_loci] or None; edges int64 [2..65] ascending or None.  max_work <= 0: only the work is
+        computed
+        -> dict(work, cnt int32 [n][n], len, longest int64 [n][n], hist, cover); all but work
+        are None when max_work <= 0"""
+        keep, args, n, nl = self._coal_args(node_tab, birth_t, nodes, loci)
+        pos = _arr(pos, np.int64).ravel()
+        if pos.size != nl:
+            raise ValueError('pos: %d entries, not one per listed locus (%d)' % (pos.size, nl))
+        b = None
+        if brk is not None:
+            b = _arr(brk, np.uint8).ravel()
+            if b.size != nl:
+                raise ValueError('brk: %d entries, not one per listed locus (%d)' % (b.size, nl))
+        e, hist = None, None
+        if edges is not None:
+            e = _arr(edges, np.int64).ravel()
+            hist = np.zeros((e.size - 1 if 2 <= e.size <= 65 else 1, 2), np.int64)
+            if e.size == 0:
+                e = np.zeros(1, np.int64)
+        run = max_work > 0
+        m = n if run else 1
+        cnt = np.zeros((m, m), np.int32)
+        tot = np.zeros((m, m), np.int64)
+        longest = np.zeros((m, m), np.int64)
+        cov = np.zeros(max(nl, 1), np.int64) if cover else None
+        work = np.zeros(1, np.int64)
+        self._chk(self.lib.gnx_coal_segments(
+            *args, _ptr(pos, C.c_int64), _ptr(b, C.c_uint8), int(t_curr),
+            self._coal_max_ago(max_time_ago), C.c_int32(int(min_loci)),
+            C.c_int64(int(min_len)), C.c_int32(0 if edges is None else int(np.size(edges))),
+            _ptr(e, C.c_int64), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
+            _ptr(cnt, C.c_int32), _ptr(tot, C.c_int64), _ptr(longest, C.c_int64),
+            _ptr(hist, C.c_int64), _ptr(cov, C.c_int64)))
+        if not run:
+            return dict(work=int(work[0]), cnt=None, len=None, longest=None, hist=None,
+                        cover=None)
+        return dict(work=int(work[0]), cnt=cnt, len=tot, longest=longest, hist=hist, cover=cov)
 
     # -- introductions (csrc/gnx_transplant.hip) ----------------------------------------
     def transplant(self, src, slots, x, y, first_id):

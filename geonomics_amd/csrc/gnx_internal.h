@@ -1047,3 +1047,7 @@ int gnx_ld_bit_rows(gnx_state* h, GnxScratch& s, GnxCallTimer& tm, const int32_t
 // an earlier call when nothing was appended since) and every index in it is in range
 int lin_table(gnx_state* h, const char* who, int64_t n_rows, const int32_t* tab,
               const int32_t* bt, int32_t t_curr);
+// the sample nodes (inside the table) and the loci (inside 0..L-1), checked and uploaded into s
+int lin_request(gnx_state* h, const char* who, int64_t n_rows, int64_t n_nodes,
+                const int32_t* nodes, int32_t n_loci, const int32_t* loci, GnxScratch& s,
+                int32_t** d_nodes, int32_t** d_loci);

@@ -244,8 +244,6 @@ int lin_table(gnx_state* h, const char* who, int64_t n_rows, const int32_t* tab,
   return 0;
 }
 
-namespace {
-
 // the sample nodes and the loci, checked and uploaded
 int lin_request(gnx_state* h, const char* who, int64_t n_rows, int64_t n_nodes,
                 const int32_t* nodes, int32_t n_loci, const int32_t* loci, GnxScratch& s,
@@ -271,6 +269,8 @@ int lin_request(gnx_state* h, const char* who, int64_t n_rows, int64_t n_nodes,
   GNXCHK(gnx_h2d(h, *d_loci, loci, (size_t)n_loci * sizeof(int32_t)));
   return 0;
 }
+
+namespace {
 
 // the lane layout of a launch over n_q loci and n_groups node groups
 struct LinGrid {

@@ -1200,6 +1200,53 @@ class Model:
                                      n_classes=n_classes, max_dist=max_dist,
                                      tract_edges=tract_edges, cover=cover, max_work=max_work)
 
+    def calc_tmrca(self, spp=0, individs=None, n=None, loci=None, max_time_ago=None,
+                   time_edges=None, n_time_bins=20, dist_edges=None, n_classes=10, max_dist=None,
+                   groups=None, return_mrca=False, max_work=None):
+        """pairwise coalescence times from the recorded spatial pedigree ('use_tskit': True; an
+        extension: what tskit's divergence(mode='branch') and pair_coalescence_counts answer),
+        merged on the device: for every two sample nodes - both homologues of at most 2048 living
+        individuals (individs, or a random sample of n) - and every locus (loci: default all) the
+        most recent common ancestor in the local tree and its age T in steps.  A pair coalesces
+        at a locus when that ancestor is no older than max_time_ago (None: anywhere in the
+        tables).  Means are over the (pair, locus) cells that coalesce.  time_edges: whole-step
+        bounds of the histogram of T (default n_time_bins bins); dist_edges, n_classes,
+        max_dist: distance classes as calc_spatial_structure; groups as calc_fst.  max_work
+        bounds the look-up chains (pairs x loci) of the device call; a request above it raises
+        ValueError
+        -> dict: ids, nodes, loci, tmrca [n_nodes][n_nodes] (mean T per pair, NaN where it never
+        coalesces), n_coalesced, per_locus (mean, share_coalesced, max), diversity_branch (2 x
+        mean T), by_group (within, between), by_dist (mean T per distance class over pairs of
+        different individuals), coal_times (edges, counts, at_risk, ne: the inverse coalescence
+        rate per bin - the population-size history that calc_ne estimates), share_coalesced,
+        mrca (if return_mrca), work"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_tmrca(individs=self._test_sample(spp, individs, n), loci=loci,
+                               max_time_ago=max_time_ago, time_edges=time_edges,
+                               n_time_bins=n_time_bins, dist_edges=dist_edges,
+                               n_classes=n_classes, max_dist=max_dist, groups=groups,
+                               return_mrca=return_mrca, max_work=max_work)
+
+    def calc_ibd(self, spp=0, max_time_ago=None, min_len=0.02, min_loci=50, unit='morgans',
+                 individs=None, n=None, edges=None, n_classes=10, max_dist=None,
+                 tract_edges=None, cover=False, max_work=None):
+        """segments shared identical by descent, from the recorded spatial pedigree
+        ('use_tskit': True; an extension: what tskit's ibd_segments answers), merged on the
+        device: for every two haplotypes of at most 2048 living individuals (individs, or a
+        random sample of n) the stretches of loci, at least min_len (in the unit) and min_loci
+        loci long, inherited from one common ancestor no older than max_time_ago steps (None:
+        anywhere in the tables).  The truth beside calc_ibs_sharing, calc_roh and
+        calc_relatedness, which estimate it from identity by state; lengths, breaks, distance
+        classes and the histogram are calc_ibs_sharing's
+        -> dict: ids, n_tracts, shared_len, longest ([n][n]; the diagonal the individual's own
+        two haplotypes), by_dist, hist, cover, work, unit, f_ibd (the realised autozygosity per
+        individual), genome_len"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_ibd(max_time_ago=max_time_ago, min_len=min_len, min_loci=min_loci,
+                             unit=unit, individs=self._test_sample(spp, individs, n),
+                             edges=edges, n_classes=n_classes, max_dist=max_dist,
+                             tract_edges=tract_edges, cover=cover, max_work=max_work)
+
     def calc_ihs(self, spp=0, unit='morgans', min_maf=0.05, cutoff=0.05, max_gap=None,
                  max_extent=None, individs=None, n=None, loci=None, n_freq_bins=20,
                  keep_edge=False, max_work=None):

@@ -133,6 +133,13 @@ def _distance_classes(spp, who, edges, n_classes, max_dist):
     return _sgs.check_edges(edges)
 
 
+def _need_pedigree(spp, who):
+    """refuse a Species that recorded no pedigree"""
+    if spp._tt is None:
+        raise ValueError("%s: no pedigree was recorded for this Species ('use_tskit' False, "
+                         "or the genomes were not assigned yet)" % who)
+
+
 def _tract_hist(edges, hist, unit):
     """the tract-length histogram of a tract call, as the caller gave its edges"""
     from ..sim import tracts as _tr
@@ -1515,9 +1522,7 @@ class SpeciesAnalyses:
 
     def _lineage_request(self, individs, nodes, loci, who):
         """(the TreeTables, sample node ids int64, loci int64) of a lineage request"""
-        if self._tt is None:
-            raise ValueError("%s: no pedigree was recorded for this Species ('use_tskit' False, "
-                             "or the genomes were not assigned yet)" % who)
+        _need_pedigree(self, who)
         tt = self._tt
         if nodes is None:
             if individs is None:
@@ -1655,3 +1660,157 @@ class SpeciesAnalyses:
         if all_loci:
             return bool(co.all())
         return {locus: bool(c) for locus, c in zip(loci.tolist(), co)}
+
+    # -- pairwise coalescence through the recorded pedigree (sim/coal.py; csrc/gnx_coal.hip) ---
+    # look-up chains (pairs of sample nodes x loci) one call may take: 4096 nodes at 10^4 loci
+    # are 8.4e10
+    _COAL_MAX_WORK = 1 << 37
+
+    def _coal_request(self, who, individs):
+        """(the TreeTables, ids ascending, their slots, sample nodes: both of every individual in
+        id order) of a coalescence request.  The individuals must be living: a simplified table
+        is exact only on the lineages of the living"""
+        _need_pedigree(self, who)
+        ids, slots = self._geno_sample(individs)
+        if ids.size < 1 or ids.size > 2048:
+            raise ValueError('%s: 1..2048 individuals (4096 sample nodes) per call (got %d): '
+                             'sample them with n=... or individs=...' % (who, ids.size))
+        tt, nodes, _ = self._lineage_request(ids, None, None, who)
+        return tt, ids, slots, nodes
+
+    @staticmethod
+    def _coal_max_ago(who, max_time_ago):
+        if max_time_ago is not None and not float(max_time_ago) >= 0:
+            raise ValueError('%s: max_time_ago: a number of steps >= 0, or None (got %r)'
+                             % (who, max_time_ago))
+        return max_time_ago
+
+    def _calc_tmrca(self, individs=None, loci=None, max_time_ago=None, time_edges=None,
+                    n_time_bins=20, dist_edges=None, n_classes=10, max_dist=None, groups=None,
+                    return_mrca=False, max_work=None):
+        """the time to the most recent common ancestor (TMRCA) of every two sample nodes - both
+        homologues of the living individuals asked for (all by default, at most 2048) - at every
+        locus asked for, from the recorded pedigree, merged on the device (gnx_coal_times).  A
+        pair coalesces at a locus when its two lineages meet in one node no older than
+        max_time_ago steps (None: anywhere in the tables, the founders included); T is that
+        node's age in steps before now.  Means are over the (pair, locus) cells that coalesce,
+        and share_coalesced says how many do.  time_edges: integer bounds of the histogram of T
+        (default n_time_bins bins over 0 .. max_time_ago, or 0 .. the founders' age).  dist_edges,
+        n_classes, max_dist: the distance classes of by_dist, as calc_spatial_structure.  groups
+        as calc_fst takes them.  return_mrca: also the MRCA node of every (locus, pair).
+        max_work bounds the look-up chains (pairs x loci) of the device call
+        -> dict: ids, nodes (2 row + homologue in the pedigree tables, two per individual), loci,
+        tmrca float64 [n_nodes][n_nodes] (NaN where the pair never coalesces), n_coalesced int32
+        [n_nodes][n_nodes], per_locus (dict: mean, share_coalesced, max), diversity_branch (2 x
+        mean T), by_group (dict: names, within, between; or None), by_dist (dict: edges, pairs,
+        mean_tmrca, share_coalesced, mean_dist over the pairs of different individuals; None
+        with one individual), coal_times (dict: edges, counts, at_risk, ne: the inverse
+        coalescence rate 1 / (2 p) per bin, sim/coal.coal_rate), share_coalesced, mrca (int32
+        [n_loci][n_pairs], -1 where the pair does not coalesce; or None), work"""
+        from ..sim import coal as _co
+        from ..sim import fst as _fst
+        who = 'calc_tmrca'
+        tt, ids, slots, nodes = self._coal_request(who, individs)
+        loci = self._lineage_request(ids, None, loci, who)[2]
+        max_time_ago = self._coal_max_ago(who, max_time_ago)
+        if time_edges is None:
+            top = self.t + 1 if max_time_ago is None else min(self.t + 1, int(max_time_ago))
+            te = _co.default_time_edges(max(top, 0), n_time_bins)
+        else:
+            te = np.asarray(time_edges, dtype=np.float64).ravel()
+            if not 2 <= te.size <= 64 or (te != np.rint(te)).any() or (np.diff(te) <= 0).any() \
+                    or te[0] < 0 or te[-1] >= 2 ** 31:
+                raise ValueError('%s: time_edges: 2..64 strictly ascending whole numbers of '
+                                 'steps >= 0 (got %r)' % (who, time_edges))
+            te = te.astype(np.int64)
+        # (no T is negative, so an edge at 0 in front counts the cells that coalesce before te[0])
+        dev_te = te if te[0] == 0 else np.r_[0, te]
+        member = None
+        if groups is not None:
+            all_ids = self._geno_sample(None)[0]
+            names, order, start = _fst.make_groups(all_ids, groups)
+            label = np.full(all_ids.size, -1, np.int64)
+            label[order] = np.repeat(np.arange(len(names)), np.diff(start))
+            member = label[np.searchsorted(all_ids, ids)]
+        if ids.size >= 2:
+            dist_edges = _distance_classes(self, who, dist_edges, n_classes, max_dist)
+        max_work = _work_limit(who, max_work, self._COAL_MAX_WORK, 'look-up chains')
+        tab, bt = tt.node_table()
+        want = ('pair_sum', 'pair_cnt', 'locus_sum', 'locus_cnt', 'locus_max') + \
+            (('mrca',) if return_mrca else ())
+        got = _within_max_work(
+            who, lambda: self._dev.coal_times(tab, bt, nodes, loci, self.t, max_time_ago, dev_te,
+                                              want, max_work),
+            'analyse a sample (n=... or individs=...) or fewer loci (loci=...), or raise '
+            'max_work')
+        tm, per, share = _co.tmrca_stats(got['pair_sum'], got['pair_cnt'], got['locus_sum'],
+                                         got['locus_cnt'], got['locus_max'])
+        node_groups = None if member is None else \
+            [np.flatnonzero(np.repeat(member, 2) == g) for g in range(len(names))]
+        div, by_group = _co.branch_diversity(got['pair_sum'], got['pair_cnt'], node_groups)
+        if by_group is not None:
+            by_group['names'] = names
+        by_dist = None
+        if ids.size >= 2:
+            by_dist = _co.tmrca_by_distance(self._field(nat.F_X)[slots],
+                                            self._field(nat.F_Y)[slots], got['pair_sum'],
+                                            got['pair_cnt'], loci.size, dist_edges)
+            by_dist['edges'] = dist_edges
+        th = got['thist']
+        before = 0 if te[0] == 0 else int(th[0])
+        rate = _co.coal_rate(th if te[0] == 0 else th[1:], te, got['work'], before)
+        return dict(ids=ids, nodes=nodes, loci=loci, tmrca=tm, n_coalesced=got['pair_cnt'],
+                    per_locus=per, diversity_branch=div, by_group=by_group, by_dist=by_dist,
+                    coal_times=rate, share_coalesced=share, mrca=got.get('mrca'),
+                    work=got['work'])
+
+    def _calc_ibd(self, max_time_ago=None, min_len=0.02, min_loci=50, unit='morgans',
+                  individs=None, edges=None, n_classes=10, max_dist=None, tract_edges=None,
+                  cover=False, max_work=None):
+        """the segments shared identical BY DESCENT between the haplotypes of the living
+        individuals asked for (all by default, at most 2048), from the recorded pedigree: the
+        stretches of loci, no shorter than min_len (in the unit, as calc_ibs_sharing) and
+        min_loci loci, over which two haplotypes have one and the same most recent common
+        ancestor no older than max_time_ago steps (None: anywhere in the tables), merged on the
+        device (gnx_coal_segments).  The truth beside calc_ibs_sharing and calc_roh, which report
+        identity by state.  A recombination rate of 0.5 or more is a chromosome boundary no
+        segment crosses.  The matrices are folded from haplotypes to individuals as
+        calc_ibs_sharing's: off the diagonal the four haplotype pairs of two individuals, on the
+        diagonal the individual's own two haplotypes.  hist and cover count every pair of
+        haplotypes, an individual's own included
+        -> calc_ibs_sharing's dict (ids, n_tracts, shared_len, longest, by_dist, hist, cover,
+        work, unit) and f_ibd (per individual: the length its own two haplotypes share over
+        genome_len, the realised autozygosity within max_time_ago, which f_roh estimates),
+        genome_len"""
+        from ..sim import coal as _co
+        from ..sim import tracts as _tr
+        who = 'calc_ibd'
+        _need_pedigree(self, who)
+        ids, slots, pos, _, genome_len, ml, mloci = self._tract_request(
+            who, individs, unit, min_len, min_loci, 2048,
+            ' (4096 sample nodes): sample them with n=... or individs=...')
+        tt, ids, slots, nodes = self._coal_request(who, ids)
+        max_time_ago = self._coal_max_ago(who, max_time_ago)
+        brk = _tr.tract_map(_rec_rates(self), unit)[1]
+        edges = _distance_classes(self, who, edges, n_classes, max_dist)
+        te = self._tract_edges(who, tract_edges, unit)
+        max_work = _work_limit(who, max_work, self._COAL_MAX_WORK, 'look-up chains')
+        tab, bt = tt.node_table()
+        loci = np.arange(self._dev.L)
+        got = _within_max_work(
+            who, lambda: self._dev.coal_segments(tab, bt, nodes, loci, pos, self.t, brk,
+                                                 max_time_ago, mloci, ml, te, bool(cover),
+                                                 max_work),
+            'analyse a sample (n=... or individs=...), or raise max_work')
+        cnt, tot, longest = _co.fold_to_individuals(got['cnt'], got['len'], got['longest'])
+        by = _tr.sharing_stats(self._field(nat.F_X)[slots], self._field(nat.F_Y)[slots], cnt,
+                               tot, edges)
+        by['mean_len'] = _tr.from_units(by['mean_len'], unit)
+        by['edges'] = edges
+        hist = None if te is None else _tract_hist(tract_edges, got['hist'], unit)
+        own = np.diagonal(tot).astype(np.float64)
+        f = own / float(genome_len) if genome_len > 0 else np.full(own.shape, np.nan)
+        return dict(ids=ids, n_tracts=cnt, shared_len=_tr.from_units(tot, unit),
+                    longest=_tr.from_units(longest, unit), by_dist=by, hist=hist,
+                    cover=got['cover'], work=got['work'], unit=unit, f_ibd=f,
+                    genome_len=float(_tr.from_units(genome_len, unit)))

@@ -108,6 +108,10 @@ _NOT_TILED = {
                            'not implemented; run the model on one GPU',
     '_check_coalescence': 'the coalescence check of a Species tiled over several GPUs '
                           'is not implemented; run the model on one GPU',
+    '_calc_tmrca': 'calc_tmrca with a Species tiled over several GPUs is not '
+                   'implemented; run the model on one GPU',
+    '_calc_ibd': 'calc_ibd with a Species tiled over several GPUs is not '
+                 'implemented; run the model on one GPU',
     '_sort_and_simplify_table_collection':
         'simplifying the pedigree of a Species tiled over several '
         'GPUs is not implemented; run the model on one GPU',

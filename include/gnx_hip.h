@@ -1220,6 +1220,67 @@ int gnx_pedigree_reach(gnx_state* h, int64_t n_rows, const int32_t* node_tab,
  * host has renumbered the rows, the reuse check's row count and checksum mean nothing)      */
 int gnx_lineage_forget(gnx_state* h);
 
+/* ---- pairwise coalescence through the recorded pedigree (csrc/gnx_coal.hip; the reference has
+ *      no such analysis: what tskit's divergence(mode='branch'), pair_coalescence_counts and
+ *      ibd_segments answer) ------------------------------------------------------------------
+ * Tables: node_tab, birth_t and the handle's paths as for gnx_lineage_trace, taken with every
+ * call through the same resident copy.  anc(v, l) is the parent node of v at locus l,
+ * 2 prow + (start ^ bit l of the path); it is undefined for a founder node.  chain(v, l) = v,
+ * anc(v, l), ... down to a founder node.  Parent rows are smaller than child rows, so node ids
+ * strictly decrease along a chain.
+ * MRCA.  For sample nodes a != b, mrca(a, b, l) is the largest node id that lies on both chains,
+ * or -1 if there is none (the chains end in different founder nodes).  From their first common
+ * node on two chains are equal, so the largest common node is the most recent one; a itself is
+ * the MRCA when it lies on b's chain (a living parent and its living offspring both sampled).
+ * Age.  ago(v) = birth_t[v >> 1] + t_curr.  A pair COALESCES at l iff m = mrca(a, b, l) >= 0 and
+ * ago(m) <= max_ago (max_ago < 0: no limit); T(a, b, l) = ago(m) then.
+ * Everything the device returns is an integer function of mrca and ago.  Every output is
+ * therefore exact, independent of order (integer atomics are fine), and bit-equal to the
+ * restatement (geonomics_amd/sim/coal.py).  All pointers are HOST buffers.
+ * Refused (return 1) before anything is launched: what gnx_lineage_trace refuses; fewer than 2
+ * or more than 4096 sample nodes; a sample node listed twice; bad edges; *work > max_work; and
+ * for gnx_coal_segments loci not strictly ascending, pos decreasing, min_len < 0.  Nothing of the
+ * handle changes.  *work = n_pairs n_loci, n_pairs = n_nodes (n_nodes - 1) / 2; max_work <= 0:
+ * only *work is written.  gnx_lineage_info reports the call.
+ *
+ * gnx_coal_times: loci in any order, repeats allowed.  Each output may be NULL and is then not
+ * computed:
+ *   pair_sum int64 [n][n], pair_cnt int32 [n][n]: the sum of T over the loci at which the pair
+ *   coalesces, and their number; symmetric, the diagonal zero;
+ *   locus_sum, locus_cnt int64 [n_loci], locus_max int32 [n_loci]: the same over the unordered
+ *   pairs per listed locus, and the largest T; locus_max is -1 where no pair coalesces;
+ *   thist int64 [n_tedges - 1]: the unordered (pair, locus) cells with tedges[k] <= T <
+ *   tedges[k + 1]; tedges int32, 2..65 of them, strictly ascending (thist NULL: n_tedges = 0 and
+ *   no edges);
+ *   mrca int32 [n_loci][n_pairs], the pairs in row-major upper-triangle order ((0,1), (0,2), ..,
+ *   (1,2), ..): the MRCA where the pair coalesces, -1 where it does not.  With mrca the loci are
+ *   worked off in launches whose MRCAs stay under gnx_lineage_budget.                          */
+int gnx_coal_times(gnx_state* h, int64_t n_rows, const int32_t* node_tab, const int32_t* birth_t,
+                   int64_t n_nodes, const int32_t* nodes, int32_t n_loci, const int32_t* loci,
+                   int32_t t_curr, int32_t max_ago, int32_t n_tedges, const int32_t* tedges,
+                   int64_t max_work, int64_t* work, int64_t* pair_sum, int32_t* pair_cnt,
+                   int64_t* locus_sum, int64_t* locus_cnt, int32_t* locus_max, int64_t* thist,
+                   int32_t* mrca);
+/* gnx_coal_segments: loci strictly ascending; q is a position in that list.  pos int64 [n_loci]
+ * is non-decreasing, in an integer unit the caller chooses.  brk uint8 [n_loci] or NULL: when
+ * brk[q] is set no segment continues from q - 1 into q (brk[0] is ignored).
+ * A SEGMENT of the pair is a maximal stretch s..e of list positions over which the pair
+ * coalesces with the same MRCA node and no break lies in s < q <= e.  Its count is e - s + 1,
+ * its length pos[e] - pos[s]; it QUALIFIES iff count >= max(1, min_loci) and length >= min_len:
+ * the tract of gnx_tracts_*, with "same MRCA within max_ago" in place of "D_l = 0".
+ *   cnt int32, len, longest int64 [n][n]: the qualifying segments of the pair, the sum of their
+ *   lengths, the largest length; symmetric, the diagonal zero; each may be NULL;
+ *   hist int64 [n_edges - 1][2] = {segments, sum of length} and cover int64 [n_loci] (the pairs
+ *   with a qualifying segment over list position q) as in gnx_tracts_pairs, over the unordered
+ *   node pairs; each may be NULL (hist NULL: n_edges = 0 and no edges).                       */
+int gnx_coal_segments(gnx_state* h, int64_t n_rows, const int32_t* node_tab,
+                      const int32_t* birth_t, int64_t n_nodes, const int32_t* nodes,
+                      int32_t n_loci, const int32_t* loci, const int64_t* pos,
+                      const uint8_t* brk /*[n_loci] or NULL*/, int32_t t_curr, int32_t max_ago,
+                      int32_t min_loci, int64_t min_len, int32_t n_edges, const int64_t* edges,
+                      int64_t max_work, int64_t* work, int32_t* cnt, int64_t* len,
+                      int64_t* longest, int64_t* hist, int64_t* cover);
+
 /* ---- introductions (csrc/gnx_transplant.hip) ------------------------------------------ */
 /* Species._add_individuals with a Species as the source (structs/species.py:1631-2077):
  * n individuals of src, in the order of src_slots, appended to dst at (x[i], y[i]) with ids
