@@ -71,6 +71,9 @@ class State:
         self.ncx = max(1, int(np.ceil(self.W / cs)))
         self.ncy = max(1, int(np.ceil(self.H / cs)))
         self.Nt, self.n_births, self.n_deaths = [], [], []
+        # what the last step decided, for the tests that compare a device run decision by
+        # decision (tests/_step_regimes.py); nothing below reads them
+        self.last_move = self.last_pairs = self.last_births = self.last_death = None
 
     @property
     def N(self):
@@ -126,19 +129,25 @@ def move(s, inc_age=True):
     p = s.p
     if inc_age:
         s.age = s.age + 1
+    s.last_move = None
     if not p.move or s.N == 0:
         return
     th, ds = D.move_draws(s.seed, s.id, s.step, p.move_distr, p.move_p1, p.move_p2,
                           p.dir_mu, p.dir_kappa)
     s.x, s.y = O.move_transform(s.x, s.y, th, ds, (s.W, s.H), dtype=F)
     s.e = O.gather_e(list(s.rasts), s.x, s.y).astype(F)
+    s.last_move = dict(ids=s.id.copy(), theta=th, dist=ds, x=s.x.copy(), y=s.y.copy())
 
 
 def sort_by_cell(s):
     inv_cs = 1.0 / s.cs                 # (gnx_cell_of multiplies by the reciprocal)
     cx = np.minimum(s.ncx - 1, (s.x.astype(np.float64) * inv_cs).astype(np.int64))
     cy = np.minimum(s.ncy - 1, (s.y.astype(np.float64) * inv_cs).astype(np.int64))
-    order = np.argsort(cy * s.ncx + cx, kind='stable')
+    # by (hash cell, id), the device's slot order (gnx_l_sort_by_cell) - not a stable sort by
+    # cell of whatever order the last step left: under panmixia the trial's slot picks the two
+    # partners (D.panmixia_draws), and from the second step on those two orders differ for
+    # whoever changed its cell
+    order = np.lexsort((s.id, cy * s.ncx + cx))
     _permute(s, order)
 
 
@@ -181,6 +190,7 @@ def find_pairs(s):
 def mate(s, pairs, burn):
     p = s.p
     P_ = len(pairs)
+    s.last_births = None
     if P_ == 0:
         return 0
     if p.n_births_fixed:
@@ -195,10 +205,13 @@ def mate(s, pairs, burn):
     mx = (s.x[par[:, 0]] + s.x[par[:, 1]]) / F(2.0)
     my = (s.y[par[:, 0]] + s.y[par[:, 1]]) / F(2.0)
     th, ds = D.dispersal_draws(s.seed, oid, s.step, p.disp_distr, p.disp_p1, p.disp_p2)
-    ox, oy, _ = O.dispersal(mx, my, th, ds, (s.W, s.H), dtype=F)
+    ox, oy, used = O.dispersal(mx, my, th, ds, (s.W, s.H), dtype=F)
+    s.last_births = dict(child=oid, parents=s.id[par], n_per_pair=nb, mid_x=mx, mid_y=my,
+                         theta=th, dist=ds, attempt=used, x=ox.astype(F), y=oy.astype(F))
     genomes = (not burn) and s.geno is not None
     n_paths = s.paths.shape[0] if s.paths is not None else 1
     start, keys, sex = D.offspring_draws(s.seed, oid, s.step, n_paths, p.sexed, p.p_male)
+    s.last_births.update(keys=keys, start=start, sex=sex)
     n0 = s.N
     s.x = np.concatenate([s.x, ox.astype(F)])
     s.y = np.concatenate([s.y, oy.astype(F)])
@@ -264,6 +277,8 @@ def pop_dynamics(s, burn=False, with_selection=True):
         k = O.pair_order_keys(s.x[who], s.y[who], s.id[who], (s.W, s.H), s.p.mating_radius,
                               s.p.mate_mode)
         pairs = pairs[np.argsort(k, kind='stable')]
+    s.last_pairs = dict(ids=s.id[pairs].reshape(-1, 2), sex=s.sex[pairs].reshape(-1, 2),
+                        age=s.age[pairs].reshape(-1, 2))
     VP = None
     if len(pairs):
         mx = (s.x[pairs[:, 0]] + s.x[pairs[:, 1]]) / F(2.0)
@@ -276,11 +291,12 @@ def pop_dynamics(s, burn=False, with_selection=True):
         # to the adults.  (Movers were all sampled by move(): the same values either way.)
         s.e = O.gather_e(list(s.rasts), s.x, s.y).astype(F)
     VN = s.lat.node_density(s.x, s.y)
-    pd_, _ = death_probs(s, with_selection and not burn, VN, VP)
+    pd_, d_cell = death_probs(s, with_selection and not burn, VN, VP)
     u = D.death_draws(s.seed, s.id, s.step).astype(np.float64)
     dead = u < pd_
     # (kept for the tests that explain where a device run and this one part ways)
-    s.last_death = dict(ids=s.id.copy(), u=u, p=pd_.copy())
+    s.last_death = dict(ids=s.id.copy(), u=u, p=pd_.copy(), d=d_cell, age=s.age.copy(), sex=s.sex.copy(),
+                        x=s.x.copy(), y=s.y.copy())
     keep = ~dead
     _permute(s, np.nonzero(keep)[0])
     s.n_births.append(B)
