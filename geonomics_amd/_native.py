@@ -77,6 +77,7 @@ EXPORTS = [
     'gnx_lai_paint',
     'gnx_assoc_cross',
     'gnx_coal_times', 'gnx_coal_segments',
+    'gnx_grm', 'gnx_grm_info', 'gnx_grm_probe',
 ]
 
 
@@ -996,6 +997,32 @@ class Device:
         self._chk(self.lib.gnx_geno_gram(self.h, C.c_int64(n), _ptr(s, C.c_int64),
                                          _ptr(m, C.c_uint64), _ptr(out, C.c_int64)))
         return out
+
+    def grm(self, val, slots=None, locus_mask=None):
+        """G_ij = sum over the masked loci of val[l][d_il] val[l][d_jl] for `slots` (all living
+        slots by default; at most 8192): val fp32 [L][3], the value of each locus at dosage 0, 1,
+        2 (include/gnx_hip.h, gnx_grm) -> G float64 [n][n], symmetric"""
+        s, n = self._geno_slots(slots)
+        m = self._locus_mask_words(locus_mask)
+        v = _arr(val, np.float32)
+        if v.shape != (self.L, 3):
+            raise ValueError('val: shape %s, not (L = %d, 3)' % (v.shape, self.L))
+        # (the library refuses n outside 1..8192 before it writes: no n x n buffer for that)
+        out = np.zeros((n, n) if 1 <= n <= 8192 else (0, 0), np.float64)
+        self._chk(self.lib.gnx_grm(self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64),
+                                   _ptr(v, C.c_float), _ptr(out, C.c_double)))
+        return out
+
+    def grm_probe(self, mode):
+        """a measuring switch (tools/grm_bench.py): 1 = grm runs its expansion alone, 2 = its
+        MFMAs alone (zeros come back; only grm_info's kernel_ms means anything), 0 = the kernel"""
+        self._chk(self.lib.gnx_grm_probe(self.h, int(mode)))
+
+    def grm_info(self):
+        """of the last grm: dict(tiles, k_chunks, kernel_ms)"""
+        t, k, ms = C.c_int64(), C.c_int64(), C.c_double()
+        self._chk(self.lib.gnx_grm_info(self.h, C.byref(t), C.byref(k), C.byref(ms)))
+        return dict(tiles=int(t.value), k_chunks=int(k.value), kernel_ms=ms.value)
 
     @staticmethod
     def _f32_dev(t, name):

@@ -371,6 +371,12 @@ struct gnx_state {
   double kin_ms = 0.0;
   int64_t kin_launches = 0, kin_tasks = 0;
 
+  // weighted relationship matrices (gnx_grm.hip): the kernel time and launches of the last
+  // call, its 128 x 128 tiles and the fp32 chains (of at most 1024 loci) behind each entry
+  double grm_ms = 0.0;
+  int64_t grm_launches = 0, grm_tiles = 0, grm_chunks = 0;
+  int grm_probe = 0;             // gnx_grm_probe: 1 / 2 run half the kernel, for measuring only
+
   // haplotype sweep scans (gnx_sweeps.hip): the kernel time and launches of the last call and
   // the completed steps summed over its scans
   double sw_ms = 0.0;

@@ -908,6 +908,60 @@ class Model:
                              individs=self._test_sample(spp, individs, n), loci=loci,
                              min_maf=min_maf, calibrate=calibrate)
 
+    def calc_grm(self, spp=0, individs=None, n=None, loci=None, kind='additive', method='gcta',
+                 alpha=-1.0, min_maf=0.01, weights=None):
+        """the standardised genomic relationship matrix of at most 8192 individuals (an
+        extension: the reference has no such analysis), summed on the device from the packed
+        genomes (gnx_grm: f32 matrix cores, fp64 sums): G_ij = sum_l v_l(d_il) v_l(d_jl), every
+        locus centred by the sample's allele frequency p and scaled.  kind 'additive' with method
+        'gcta' ((d - 2p) / sqrt(2pq m), Yang et al. 2011), 'vanraden' ((d - 2p) / sqrt(sum 2pq))
+        or 'alpha' ((d - 2p) (2pq)^(alpha/2), normalised; Speed et al. 2012), or kind 'dominance'
+        (Zhu et al. 2015).  Loci monomorphic in the sample or below min_maf are left out;
+        weights [L] multiplies each locus' values (LD-weighted matrices).  individs, or a random
+        sample of n, and loci restrict the analysis
+        -> dict: G [n][n] float64 (symmetric; mean diagonal about 1), ids, loci_used, n_loci, p,
+        kernel_ms, kind, method"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_grm(individs=self._test_sample(spp, individs, n), loci=loci, kind=kind,
+                             method=method, alpha=alpha, min_maf=min_maf, weights=weights)
+
+    def calc_heritability(self, trt=0, spp=0, y=None, covars=(), n_pcs=0, individs=None, n=None,
+                          loci=None, method='gcta', alpha=-1.0, min_maf=0.01, grm=None):
+        """the SNP heritability of a response among at most 8192 individuals (an extension: the
+        reference has no such analysis): the mixed model y = X b + g + e with g ~ N(0, Vg G), G
+        the additive relationship matrix of calc_grm, fitted by restricted maximum likelihood in
+        the eigenbasis of G.  The response is the phenotype z of Trait trt or y [n] in
+        ascending-id order.  A Trait's z carries no environmental deviation in Geonomics (it is a
+        function of the genotype alone), so its h2 measures how much of z the additive matrix
+        captures and approaches 1; give y - fitness, or z plus noise - for a response with
+        environmental variance.  covars and n_pcs as run_gwas; an intercept is always fitted.
+        grm takes a previous calc_grm result (of the same individuals), so that several
+        responses share one matrix and its eigendecomposition
+        -> dict: h2, se_h2, Vg, Ve, beta, logL, logL0, lrt_p, delta, at_boundary, he_h2 (the
+        Haseman-Elston estimate, a non-iterative check), ids, n_loci, seconds"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_heritability(trt_num=self._get_trt_num(spp, trt), y=y, covars=covars,
+                                      n_pcs=n_pcs, individs=self._test_sample(spp, individs, n),
+                                      loci=loci, method=method, alpha=alpha, min_maf=min_maf,
+                                      grm=grm)
+
+    def predict_breeding_values(self, trt=0, spp=0, y=None, covars=(), n_pcs=0, train=None,
+                                individs=None, n=None, loci=None, method='gcta', alpha=-1.0,
+                                min_maf=0.01, grm=None):
+        """genomic BLUP of the breeding values of at most 8192 individuals (an extension: the
+        reference has no such analysis): the model of calc_heritability is fitted on the
+        individuals of train (ids; default: everybody) and predicts g_hat for every individual
+        of the sample, the untrained ones from their relationships with the trained; y of the
+        untrained is not read
+        -> dict: g_hat, y_hat [n], ids, train, beta, delta, h2, Vg, Ve, and for a Trait response
+        accuracy: the correlation of g_hat with the Trait's true z over the individuals that
+        were not trained on (NaN when there are none)"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._predict_breeding_values(
+            trt_num=self._get_trt_num(spp, trt), y=y, covars=covars, n_pcs=n_pcs, train=train,
+            individs=self._test_sample(spp, individs, n), loci=loci, method=method, alpha=alpha,
+            min_maf=min_maf, grm=grm)
+
     def _test_sample(self, spp, individs, n):
         """the ids a Mantel / MMRR call analyses: individs, or a random n of the living drawn
         as write_gendata draws its sample, or everybody"""

@@ -550,6 +550,176 @@ class SpeciesAnalyses:
                        collinear_tol, calibrate)
         return self._assoc_result(res, ids, loci, trait_loci, U=U)
 
+    # -- relationship matrices, heritability and breeding values (sim/quantgen.py;
+    # csrc/gnx_grm.hip) ---------------------------------------------------------------------
+    def _calc_grm(self, individs=None, loci=None, kind='additive', method='gcta', alpha=-1.0,
+                  min_maf=0.01, weights=None):
+        """the standardised genomic relationship matrix of the living individuals asked for (all
+        by default; at most 8192: the matrix is n x n): G_ij = sum_l v_l(d_il) v_l(d_jl) with the
+        per-locus values of sim/quantgen.grm_values (additive in GCTA's, VanRaden's or the
+        alpha model's weighting, or dominance), written from the sample's exact allele counts
+        (gnx_stats_group_counts) and summed on the device (gnx_grm).  weights [L] multiplies the
+        values per locus
+        -> dict: G float64 [n][n], ids, loci_used, n_loci, p [n_loci] (the sample's frequency of
+        the 1-allele at loci_used), kernel_ms, kind, method"""
+        from ..sim import quantgen as _qg
+        who = 'calc_grm'
+        _qg.check_request(who, kind, method, alpha, min_maf)
+        _need_genomes(self, who)
+        ids, slots = self._geno_sample(individs)
+        n = int(ids.size)
+        if n > _qg.GRM_MAX:
+            raise ValueError('%s: at most %d individuals (the relationship matrix is n x n), got '
+                             '%d: pass n=... or individs=...' % (who, _qg.GRM_MAX, n))
+        L = self._dev.L
+        loci_u, _ = self._geno_loci(loci)
+        subset = None
+        if loci_u is not None:
+            subset = np.zeros(L, bool)
+            subset[loci_u] = True
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.shape != (L,) or not np.isfinite(weights).all():
+                raise ValueError('%s: weights: finite values [L = %d] (got %s)'
+                                 % (who, L, weights.shape))
+        # ---- from here on the device is asked
+        c1 = self._dev.stats_group_counts(slots, np.array([0, n], np.int64))[0][0]
+        val, used = _qg.grm_values(c1, n, kind, method, alpha, min_maf, subset, weights)
+        loci_used = np.flatnonzero(used)
+        if loci_used.size == 0:
+            raise ValueError('%s: no locus of the request is polymorphic in the sample with a '
+                             'minor allele frequency of at least %g' % (who, min_maf))
+        _, mask = self._geno_loci(loci_used)
+        G = self._dev.grm(val, slots, mask)
+        return dict(G=G, ids=ids, loci_used=loci_used, n_loci=int(loci_used.size),
+                    p=c1[loci_used] / (2.0 * n), kernel_ms=self._dev.grm_info()['kernel_ms'],
+                    kind=kind, method=method)
+
+    def _quantgen_request(self, who, trt_num, y, covars, n_pcs, individs, loci, method, alpha,
+                          min_maf, grm, finite=None):
+        """what calc_heritability and predict_breeding_values share: the checked request, then
+        the response (read as run_gwas reads it), the design matrix [1, covariates, PCs], the
+        relationship matrix (grm: a calc_grm result of the same individuals, else computed) and
+        its eigendecomposition, kept in the grm dict for the next response
+        -> (ids, slots, y [n], X [n][c], grm, z or None, seconds)"""
+        import time
+        from ..sim import assoc as _as
+        from ..sim import quantgen as _qg
+        _qg.check_request(who, 'additive', method, alpha, min_maf)
+        _need_genomes(self, who)
+        if y is None:
+            traits = self.gen_arch.traits
+            if not traits:
+                raise ValueError('%s: the Species has no Traits; give y' % who)
+            if isinstance(trt_num, bool) or trt_num not in traits:
+                raise ValueError('%s: no Trait %r (Traits: %s)' % (who, trt_num, sorted(traits)))
+        if isinstance(n_pcs, bool) or int(n_pcs) != n_pcs or n_pcs < 0:
+            raise ValueError('%s: n_pcs: a number of genetic PCs >= 0 (got %r)' % (who, n_pcs))
+        if grm is not None:
+            if not isinstance(grm, dict) or 'G' not in grm or 'ids' not in grm:
+                raise ValueError('%s: grm: the dict calc_grm returns' % who)
+            if individs is None:
+                individs = grm['ids']
+        ids, slots = self._geno_sample(individs)
+        n = int(ids.size)
+        if n > _qg.GRM_MAX:
+            raise ValueError('%s: at most %d individuals (the relationship matrix is n x n), got '
+                             '%d: pass n=... or individs=...' % (who, _qg.GRM_MAX, n))
+        if grm is not None and not np.array_equal(np.asarray(grm['ids']), ids):
+            raise ValueError('%s: grm: its ids are not the individuals of this request' % who)
+        if y is not None:
+            y = np.asarray(y, dtype=np.float64)
+            ok = np.ones(n, bool) if finite is None else finite(ids)
+            if y.ndim != 1 or y.shape[0] != n or not np.isfinite(y[ok]).all():
+                raise ValueError('%s: y: finite values [n = %d] in ascending-id order (got %s)'
+                                 % (who, n, y.shape))
+        cov = self._assoc_covars(who, covars, n)
+        n_cov = sum(len(self._env_layers(who, None)) if c is None else c for c, _ in cov)
+        _as.check_columns(n_cov + int(n_pcs) + 1, who)
+        # ---- from here on the device is asked
+        z = None
+        if y is None:
+            y = z = self._field(nat.F_Z)[trt_num][slots].astype(np.float64)
+        pcs = np.zeros((n, 0))
+        if n_pcs:
+            pcs = np.asarray(self._calc_genetic_PCA(int(n_pcs), individs=ids)[1], np.float64)
+        X = np.column_stack([np.ones(n)] + [f(slots) for _, f in cov] + [pcs])
+        seconds = dict(grm=0.0, eigh=0.0)
+        if grm is None:
+            t0 = time.perf_counter()
+            grm = self._calc_grm(individs=ids, loci=loci, method=method, alpha=alpha,
+                                 min_maf=min_maf)
+            seconds['grm'] = time.perf_counter() - t0
+        if 'eig' not in grm:
+            t0 = time.perf_counter()
+            grm['eig'] = _qg.eig_grm(grm['G'])
+            seconds['eigh'] = time.perf_counter() - t0
+        return ids, slots, y, X, grm, z, seconds
+
+    def _calc_heritability(self, trt_num=0, y=None, covars=(), n_pcs=0, individs=None, loci=None,
+                           method='gcta', alpha=-1.0, min_maf=0.01, grm=None):
+        """the SNP heritability of a response over the living individuals asked for (all by
+        default; at most 8192): the mixed model y = X b + g + e, g ~ N(0, Vg G), with G the
+        additive relationship matrix (_calc_grm; grm: a previous result of the same individuals,
+        which then also keeps its eigendecomposition under 'eig'), X an intercept, the covariates
+        (_assoc_covars) and the first n_pcs genetic PCs, fitted by REML (sim/quantgen.reml).  The
+        response is the phenotype z of Trait trt_num or y [n] in ascending-id order
+        -> reml's dict plus he_h2 (Haseman-Elston), ids, n_loci, seconds (grm, eigh, reml)"""
+        import time
+        from ..sim import quantgen as _qg
+        ids, _, y, X, grm, _, seconds = self._quantgen_request(
+            'calc_heritability', trt_num, y, covars, n_pcs, individs, loci, method, alpha,
+            min_maf, grm)
+        t0 = time.perf_counter()
+        out = _qg.reml(grm['eig'][0], grm['eig'][1], y, X)
+        seconds['reml'] = time.perf_counter() - t0
+        out.update(he_h2=_qg.he_regression(grm['G'], y, X), ids=ids, n_loci=grm['n_loci'],
+                   seconds=seconds)
+        return out
+
+    def _predict_breeding_values(self, trt_num=0, y=None, covars=(), n_pcs=0, train=None,
+                                 individs=None, loci=None, method='gcta', alpha=-1.0,
+                                 min_maf=0.01, grm=None):
+        """genomic BLUP of the breeding values of the living individuals asked for (all by
+        default; at most 8192): the variance components are fitted by REML on the individuals
+        of `train` (ids; None: everybody) and g_hat = G[:, train] V_tt^-1 (y_t - X_t b) predicts
+        everybody (sim/quantgen.gblup).  y outside `train` is not read and may be NaN
+        -> dict: g_hat, y_hat [n], ids, train (ids), beta, delta, h2, Vg, Ve, and for a Trait
+        response accuracy: the correlation of g_hat with the Trait's z over the individuals not
+        trained on (NaN when there are none)"""
+        from ..sim import quantgen as _qg
+        who = 'predict_breeding_values'
+        tr_ids = None
+        if train is not None:
+            tr_ids = np.unique(np.asarray(train, dtype=np.int64).ravel())
+            if tr_ids.size < 2:
+                raise ValueError('%s: train: at least 2 individuals' % who)
+
+        def observed(ids):
+            return np.ones(ids.size, bool) if tr_ids is None else np.isin(ids, tr_ids)
+
+        given = y is not None
+        ids, _, y, X, grm, z, _ = self._quantgen_request(
+            who, trt_num, y, covars, n_pcs, individs, loci, method, alpha, min_maf, grm, observed)
+        idx = None
+        if tr_ids is not None:
+            idx = np.searchsorted(ids, tr_ids)
+            if (idx >= ids.size).any() or (ids[np.minimum(idx, ids.size - 1)] != tr_ids).any():
+                raise ValueError('%s: train: individuals outside the sample' % who)
+        got = _qg.gblup(grm['eig'][0], grm['eig'][1], np.where(observed(ids), y, 0.0), X,
+                        train=idx)
+        fit = got['fit']
+        out = dict(g_hat=got['g_hat'], y_hat=got['y_hat'], ids=ids,
+                   train=ids if tr_ids is None else tr_ids, beta=got['beta'], delta=got['delta'],
+                   h2=fit['h2'], Vg=fit['Vg'], Ve=fit['Ve'])
+        if not given:
+            rest = ~observed(ids)
+            acc = float('nan')
+            if rest.sum() > 1 and np.std(z[rest]) > 0 and np.std(got['g_hat'][rest]) > 0:
+                acc = float(np.corrcoef(got['g_hat'][rest], z[rest])[0, 1])
+            out['accuracy'] = acc
+        return out
+
     # -- Mantel tests and MMRR (sim/mmrr.py; csrc/gnx_mantel.hip) --------------------------
     def _dist_predictors(self, who, predictors, env_lyrs, trts):
         """the device columns [(field, index), ...] of each named predictor: 'geo' = (x, y),

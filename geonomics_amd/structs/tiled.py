@@ -88,6 +88,13 @@ _NOT_TILED = {
                  'model on one GPU',
     '_run_lfmm': 'run_lfmm with a Species tiled over several GPUs is not implemented; run the '
                  'model on one GPU',
+    # relationship matrices and what rests on them (a gather of the sample, as the Gram matrix)
+    '_calc_grm': 'calc_grm with a Species tiled over several GPUs is not implemented; run the '
+                 'model on one GPU',
+    '_calc_heritability': 'calc_heritability with a Species tiled over several GPUs is not '
+                          'implemented; run the model on one GPU',
+    '_predict_breeding_values': 'predict_breeding_values with a Species tiled over several GPUs '
+                                'is not implemented; run the model on one GPU',
     # identity tracts (a pair of individuals of different tiles: a gather of the sample)
     '_calc_roh': 'calc_roh with a Species tiled over several GPUs is not '
                  'implemented; run the model on one GPU',

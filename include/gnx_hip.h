@@ -654,6 +654,23 @@ int gnx_geno_matmul(gnx_state* h, int32_t k, const float* M, float* Y, int64_t n
 /* Z = D^T Y: Y fp32 [n][k] and Z fp32 [L][k] DEVICE pointers, as gnx_geno_matmul         */
 int gnx_geno_rmatmul(gnx_state* h, int32_t k, const float* Y, float* Z, int64_t n,
                      const int64_t* slots);
+/* Weighted relationship matrix (csrc/gnx_grm.hip): G_ij = sum over the loci l of the mask of
+ * val[l][d_il] * val[l][d_jl], double [n][n] on the HOST, 1 <= n <= 8192; val: fp32 [L][3] on
+ * the HOST, the value of locus l at dosage 0, 1, 2 (the host folds centring, weights and
+ * sqrt(w) into it; geonomics_amd/sim/quantgen.py).  n, slots, locus_mask and the preconditions
+ * as gnx_geno_gram.  f32 MFMA: every fp32 accumulation chain holds at most 1024 products and the
+ * chains are added in fp64 in locus order, so |G_ij - exact| <= (1024 * 2^-24 + L * 2^-53) *
+ * sum_l |val[l][d_il] val[l][d_jl]| to first order; G == G^T exactly and a repeated call is
+ * bit-equal.  Rows past n of a partial tile and loci outside the mask contribute exactly 0.
+ * gnx_grm_info: the 128 x 128 tiles, the fp32 chains behind each entry and the HIP-event time
+ * of the last call's kernels (each may be NULL).                                           */
+int gnx_grm(gnx_state* h, int64_t n, const int64_t* slots, const uint64_t* locus_mask,
+            const float* val, double* G);
+int gnx_grm_info(gnx_state* h, int64_t* tiles, int64_t* k_chunks, double* kernel_ms);
+/* A measuring switch (tools/grm_bench.py): mode 1 runs the kernel's expansion of the bits
+ * alone, mode 2 its MFMAs alone; gnx_grm then returns zeros and only its kernel time means
+ * anything.  Mode 0 (the default) is the kernel.                                         */
+int gnx_grm_probe(gnx_state* h, int32_t mode);
 
 /* ---- genotype-environment association (reference sim/model.py:2717-2780 Model.run_gea ->
  *      structs/species.py:2218-2355 _make_gea_df / _run_cca: the N x L table of mean
