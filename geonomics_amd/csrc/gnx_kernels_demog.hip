@@ -942,28 +942,51 @@ k_alive(int64_t N, const double* p_death, const uint8_t* dead_in, const int64_t*
   // the job list of the deferred crossover is appended to (k_xo_jobs_surv): empty it
   if (zero_jobs && blockIdx.x == 0 && threadIdx.x == 0) *zero_jobs = 0;
   bool fa[4], fd[4], fx[4];
+  // Every load here is indexed by the item itself: all four rounds' loads go out together, one
+  // round trip for the kernel instead of one per round and column.  Unconditional loads from
+  // indices clamped to the last live item (behind `i < N ? load : 0` the compiler waits for
+  // each one in turn); a block without a live item - N can be 0 under a capacity-sized grid -
+  // loads nothing.
+  uint8_t gh[4] = {0, 0, 0, 0}, din[4] = {0, 0, 0, 0};
+  int64_t idv[4] = {0, 0, 0, 0};
+  double pd[4] = {0.0, 0.0, 0.0, 0.0};
+  int32_t gr[4] = {0, 0, 0, 0};
+  if (base < N) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t ic = min(base + r * 256 + (int64_t)threadIdx.x, N - 1);
+      gh[r] = ghost[ic];
+      gr[r] = grow[ic];
+      if (dead_in) {
+        din[r] = dead_in[ic];
+      } else {
+        idv[r] = id[ic];
+        pd[r] = p_death[ic];
+      }
+    }
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t i = base + r * 256 + threadIdx.x;
     fa[r] = fd[r] = fx[r] = false;
     if (i < N) {
       bool dead;
-      const bool g = ghost[i] != 0;
+      const bool g = gh[r] != 0;
       if (g) {
         dead = true;
       } else if (dead_in) {
-        dead = dead_in[i] != 0;
+        dead = din[r] != 0;
       } else {
-        uint4 rr = gnx_rand4(seed, (unsigned long long)id[i], step, OP_DEATH, 0);
-        dead = (double)gnx_u01(rr.x) < p_death[i];
+        uint4 rr = gnx_rand4(seed, (unsigned long long)idv[r], step, OP_DEATH, 0);
+        dead = (double)gnx_u01(rr.x) < pd[r];
       }
       fa[r] = !dead;
       // rows to return to the free stack (offspring that die before their deferred
       // crossover never had one; ghosts own none)
-      fd[r] = dead && !g && grow[i] >= 0;
+      fd[r] = dead && !g && gr[r] >= 0;
       // surviving offspring of this step whose crossover was deferred: it gets its genome
       // row and its crossover now (xo_first < 0: nothing deferred).  alive[] bit 1 marks it.
-      fx[r] = !dead && xo_first >= 0 && i >= xo_first && grow[i] < 0;
+      fx[r] = !dead && xo_first >= 0 && i >= xo_first && gr[r] < 0;
       alive[i] = (fa[r] ? 1 : 0) | (fx[r] ? 2 : 0);
       dead_row[i] = fd[r] ? 1 : 0;
     }
@@ -1580,6 +1603,9 @@ __device__ __forceinline__ void gnx_ord_flags_body(int64_t N, int64_t ord_n, con
                                                    int* lds, int* lds2) {
   const int64_t base = (int64_t)blockIdx.x * GNX_CB;
   bool f[4];
+  // (the four rounds' loads issued together, level by level, as the death draws and the pair list
+  // do it: measured and removed - 27.7 against 27.5 us alone, k_ord_write 8.0 against 7.5,
+  // profiles/rounds_kernels_alone.txt; the last workgroup's scan of the counts is what takes long)
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t k = base + r * 256 + threadIdx.x;
@@ -1840,20 +1866,33 @@ k_dead_rows(int64_t N, const int32_t* __restrict__ dead_row, const int32_t* __re
   __shared__ int lds[16];
   const int64_t base = (int64_t)blockIdx.x * GNX_CB;
   bool fd[4];
+  // Everything this kernel reads is indexed by the item or by the block: it all goes out at once
+  // (unconditional loads from indices clamped to the last live item - k_alive), the dead's rows
+  // with the flags and not one round trip behind the ranks.
+  const int32_t popped = xo ? cnts[2] : 0;
+  const int32_t od = blk_off_d[blockIdx.x];
+  int32_t dr[4] = {0, 0, 0, 0}, gr[4] = {-1, -1, -1, -1};
+  if (base < N) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t ic = min(base + r * 256 + (int64_t)threadIdx.x, N - 1);
+      dr[r] = dead_row[ic];
+      gr[r] = grow[ic];
+    }
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t i = base + r * 256 + threadIdx.x;
-    fd[r] = i < N && dead_row[i] != 0;
+    fd[r] = i < N && dr[r] != 0;
   }
   int rd[4], td;
   gnx_block_ranks(fd, rd, td, lds);
-  if (xo) n_free -= cnts[2];
-  const int32_t od = blk_off_d[blockIdx.x];
+  n_free -= popped;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t i = base + r * 256 + threadIdx.x;
     if (fd[r]) {
-      free_rows[n_free + od + rd[r]] = grow[i];
+      free_rows[n_free + od + rd[r]] = gr[r];
       grow[i] = -1;               // (the slot stays until the next cell sort: it owns no row any more)
     }
   }

@@ -1782,7 +1782,8 @@ __device__ __forceinline__ bool pair_ok(const PairP& P, const GnxSoA& s, int64_t
 // every tile of a tiled run takes the same decision).  A pair belongs to the tile that
 // owns its focal individual: ghost focals only serve the reciprocity test.  Flags and
 // their per-block counts (gnx_compact.h).
-__global__ void __launch_bounds__(256)
+// (8 waves per SIMD as before the four rounds' loads went out together: 64 VGPRs, no scratch)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_pair_flags(PairP P, GnxSoA s, int32_t* flag2, int32_t* cnt, GnxVtOut vt) {
   __shared__ int lds[16];
   __shared__ int vtot[GNX_VTN];
@@ -1794,32 +1795,104 @@ k_pair_flags(PairP P, GnxSoA s, int32_t* flag2, int32_t* cnt, GnxVtOut vt) {
   // (tile-major ids: everybody's position goes out with the first loads - coalesced, and not one
   // more round trip behind the filters' chain of dependent loads)
   float px[4] = {0.f, 0.f, 0.f, 0.f}, py[4] = {0.f, 0.f, 0.f, 0.f};
-  if (vt.scls) {
+  if (vt.scls && base < P.N) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t ic = min(base + r * 256 + (int64_t)threadIdx.x, P.N - 1);
+      px[r] = s.x[ic];
+      py[r] = s.y[ic];
+    }
+  }
+  // The filters' loads by dependency level, each level for all four rounds before the next one
+  // starts: one round trip per level, not one per round and column.  Every load is
+  // unconditional, from an index that is legal whatever the lane holds (behind `ok ? load : 0`
+  // the compiler waits for each one in turn): items past N repeat item N - 1, an individual
+  // without a mate stands in for its mate itself, and a block without a live item - N can be 0
+  // under a capacity-sized grid - loads nothing.
+  // Radius path (focal == nullptr): the mate list is k_find_mates', which drew the focal
+  // individual's OP_PAIR_KEEP block itself - same seed, step, b and keep_in - and wrote
+  // mate[i] = -1 for everybody it did not keep (and for everybody who fails the focal side of
+  // the sex and age filters).  mate[i] >= 0 therefore implies keep, and mate[m] == i implies it
+  // for the mate in the reciprocity test: no draw, and no id load for one, here.  Panmixia
+  // (focal != nullptr) has no such list - k_panmixia draws both members for every trial - and
+  // the thinning is drawn here.
+  const bool draw = P.focal != nullptr && P.keep_in == nullptr;
+  int32_t mt[4] = {-1, -1, -1, -1}, fo4[4] = {0, 0, 0, 0};
+  int64_t idi[4] = {0, 0, 0, 0};
+  uint8_t kin[4] = {1, 1, 1, 1};
+  int32_t age_f[4] = {0, 0, 0, 0}, age_m[4] = {0, 0, 0, 0}, mm[4] = {-1, -1, -1, -1};
+  uint8_t sex_f[4] = {0, 0, 0, 0}, sex_m[4] = {0, 0, 0, 0}, gh[4] = {0, 0, 0, 0};
+  bool ok4[4] = {false, false, false, false};
+  if (base < P.N) {
+    // level 1: by the item itself
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t ic = min(base + r * 256 + (int64_t)threadIdx.x, P.N - 1);
+      mt[r] = P.mate[ic];
+      fo4[r] = P.focal ? P.focal[ic] : (int32_t)ic;
+      if (draw || P.dedup) idi[r] = s.id[ic];
+      if (P.focal && P.keep_in) kin[r] = P.keep_in[ic];
+    }
+    // by the focal individual (the item itself but for panmixia), then level 2: by the mate
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      age_f[r] = s.age[fo4[r]];
+      gh[r] = s.ghost[fo4[r]];
+      if (P.sexed) sex_f[r] = s.sex[fo4[r]];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int32_t mc = mt[r] >= 0 ? mt[r] : fo4[r];
+      age_m[r] = s.age[mc];
+      if (P.sexed) sex_m[r] = s.sex[mc];
+      if (P.dedup) mm[r] = P.mate[mc];
+    }
+  }
+  bool recip = false;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t i = base + r * 256 + threadIdx.x;
+    bool ok = i < P.N && mt[r] >= 0;
+    if (P.focal) {
+      bool keep = kin[r] != 0;
+      if (draw) {
+        uint4 rr = gnx_rand4(P.seed, (unsigned long long)idi[r], P.step, OP_PAIR_KEEP, 0);
+        keep = gnx_u01(rr.x) < P.b;
+      }
+      ok = ok && keep;
+    }
+    if (P.sexed) ok = ok && sex_f[r] == 0 && sex_m[r] == 1;
+    ok4[r] = ok && age_f[r] >= P.ra_f && age_m[r] >= P.ra_m;
+    recip = recip || (ok4[r] && P.dedup && mm[r] == (int32_t)i);
+  }
+  // the rare branch, behind the common levels: (m, i) may be on the list too - the pair with the
+  // smaller focal id stays
+  if (recip) {
+    int64_t idm[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) idm[r] = s.id[mt[r] >= 0 ? mt[r] : fo4[r]];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int64_t i = base + r * 256 + threadIdx.x;
-      if (i < P.N) {
-        px[r] = s.x[i];
-        py[r] = s.y[i];
+      if (!(ok4[r] && mm[r] == (int32_t)i && idm[r] < idi[r])) continue;
+      // is (m, i) a pair?  Its focal individual is m, its mate i
+      bool okm;
+      if (P.focal) {
+        okm = pair_ok(P, s, mt[r]);
+      } else {
+        okm = age_m[r] >= P.ra_f && age_f[r] >= P.ra_m;
+        if (P.sexed) okm = okm && sex_m[r] == 0 && sex_f[r] == 1;
       }
+      if (okm) ok4[r] = false;
     }
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t i = base + r * 256 + threadIdx.x;
-    f[r] = false;
-    if (i < P.N) {
-      bool ok = pair_ok(P, s, i);
-      if (ok && P.dedup) {
-        const int m = P.mate[i];
-        if (P.mate[m] == (int32_t)i && s.id[m] < s.id[i] && pair_ok(P, s, m)) ok = false;
-      }
-      // (a pair belongs to the tile that owns its focal individual: slot i itself, or - panmixia -
-      // the individual the trial of slot i drew)
-      if (s.ghost[P.focal ? P.focal[i] : (int)i]) ok = false;
-      f[r] = ok;
-      flag2[i] = ok ? 1 : 0;
-    }
+    // (a pair belongs to the tile that owns its focal individual: slot i itself, or - panmixia -
+    // the individual the trial of slot i drew)
+    f[r] = ok4[r] && gh[r] == 0;
+    if (i < P.N) flag2[i] = f[r] ? 1 : 0;
   }
   int rank[4], tot;
   gnx_block_ranks(f, rank, tot, lds);
@@ -1950,6 +2023,12 @@ k_pair_compact(int64_t N, const int32_t* focal, const int32_t* mate, const int32
   const int64_t base = (int64_t)blockIdx.x * GNX_CB;
   bool f[4];
   int sc[4] = {0, 0, 0, 0};
+  // (Every load of this kernel issued up front, level by level, as k_pair_flags does it: 13 - 15
+  // us alone against 17 - 19, measured and removed.  Workgroup 0 hands the host the pair count
+  // when this kernel STARTS, and the host has until its end to enqueue the births in front of
+  // the crossover that waits for the pair list; at 11.7 us instead of 15.8 in the step it lost
+  // that race in every second run of bench.py - births beside the crossover, 109 us against 58,
+  // a step of 0.49 - 0.53 ms against 0.47: profiles/rounds_ab_runs.txt, session 3)
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t i = base + r * 256 + threadIdx.x;
