@@ -78,6 +78,7 @@ EXPORTS = [
     'gnx_assoc_cross',
     'gnx_coal_times', 'gnx_coal_segments',
     'gnx_grm', 'gnx_grm_info', 'gnx_grm_probe',
+    'gnx_assoc_quad',
 ]
 
 
@@ -1462,6 +1463,26 @@ class Device:
             C.byref(cnt), C.byref(ms)))
         return dict(DtY=out, s1=s1, s2=s2, stretch=int(per.value), stretches=int(cnt.value),
                     kernel_ms=ms.value)
+
+    def assoc_quad(self, val, M, slots=None, locus_mask=None):
+        """q[l] = sum over the rows k of M of (sum_i M[k][i] val[l][d_il])^2 for the dosages of
+        `slots` (all living slots by default, in the order given; at most 8192) at the loci of the
+        mask (include/gnx_hip.h, gnx_assoc_quad): val fp32 [L][3] as grm's, M fp32 [m][n] on the
+        host, finite, 1 <= m <= 8192 -> dict(q fp64 [L], 0 outside the mask; kernel_ms)"""
+        s, n = self._geno_slots(slots)
+        mk = self._locus_mask_words(locus_mask)
+        v = _arr(val, np.float32)
+        if v.shape != (self.L, 3):
+            raise ValueError('val: shape %s, not (L = %d, 3)' % (v.shape, self.L))
+        M = _arr(M, np.float32)
+        if M.ndim != 2 or M.shape[1] != n:
+            raise ValueError('M: %s, not [m][n = %d]' % (M.shape, n))
+        out = np.zeros(self.L, np.float64)
+        ms = C.c_double(0.0)
+        self._chk(self.lib.gnx_assoc_quad(
+            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(mk, C.c_uint64), _ptr(v, C.c_float),
+            C.c_int32(int(M.shape[0])), _ptr(M, C.c_float), _ptr(out, C.c_double), C.byref(ms)))
+        return dict(q=out, kernel_ms=ms.value)
 
     # -- identity tracts of the phased genomes (csrc/gnx_tracts.hip) ------------------------
     def _tract_args(self, pos, brk, edges):

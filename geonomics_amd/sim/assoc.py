@@ -285,3 +285,165 @@ def latent_factors(G, X, K, lam=1e-5):
     w, V = np.linalg.eigh((M + M.T) * 0.5)
     u = V[:, ::-1][:, :K]
     return (Qx / d[None, :]) @ u
+
+
+# ---- the mixed-model scan (csrc/gnx_quad.hip) ---------------------------------------------------
+# y = X b + g beta + u + e, u ~ N(0, sg2 G), e ~ N(0, se2 I): with G = U diag(lambda) U^T and
+# delta = se2 / sg2 the rotation M = diag((lambda + delta)^-1/2) U^T whitens the model
+# (M^T M = (G + delta I)^-1), and the scan is the Frisch-Waugh scan above on M y, M X and M g.
+# The n x L matrix M D is never formed: per locus the test needs ||M z||^2, z the centred dosage
+# (the whitened intercept M 1 is a covariate, so centring changes nothing but the size of the
+# numbers), which is gnx_assoc_quad, and z . (M^T c) for a few whitened columns c, which is
+# gnx_assoc_cross.  delta is fixed at the null model's REML estimate and sigma^2 is re-estimated
+# per locus in closed form: the test of EMMAX (Kang et al. 2010, Nat. Genet. 42:348), P3D (Zhang
+# et al. 2010) and FaST-LMM with a fixed delta (Lippert et al. 2011).  delta is not refitted per
+# locus (exact GEMMA).
+
+def numpy_quad(D):
+    """quad(val [L][3], M [m][n], use bool [L]) of the dosages D [n][L] in plain fp64 numpy, for
+    the host tests: q[l] = sum_k (sum_i M[k][i] val[l][d_il])^2 at the loci in use, 0 elsewhere"""
+    Di = np.asarray(D).astype(np.int64)
+
+    def quad(val, M, use=None):
+        val = np.asarray(val, np.float64)
+        Z = np.take_along_axis(val.T, Di, axis=0)
+        q = ((np.asarray(M, np.float64) @ Z) ** 2).sum(axis=0)
+        if use is not None:
+            q[~np.asarray(use, bool)] = 0.0
+        return dict(q=q, kernel_ms=0.0)
+    return quad
+
+
+def lmm_rotation(evals, U, delta):
+    """M fp64 [n][n] = diag((max(lambda, 0) + delta)^-1/2) U^T of G = U diag(lambda) U^T:
+    M^T M = (G + delta I)^-1"""
+    delta = float(delta)
+    if not (np.isfinite(delta) and delta > 0):
+        raise ValueError('delta: a positive, finite ratio se2 / sg2 (got %r)' % (delta,))
+    lam = np.maximum(np.asarray(evals, np.float64).ravel(), 0.0)
+    U = np.asarray(U, np.float64)
+    if U.shape != (lam.size, lam.size):
+        raise ValueError('evals [n] and U [n][n] (got %s and %s)' % (lam.shape, U.shape))
+    # (in C order: U.T / ... would come back in U.T's Fortran order, and the device call would
+    # then copy all of it again, strided)
+    M = np.empty_like(U)
+    np.divide(U.T, np.sqrt(lam + delta)[:, None], out=M)
+    return M
+
+
+def lmm_design(y, X, M):
+    """the columns one mixed-model scan sends to gnx_assoc_cross: y [n] the response, X [n][c]
+    the covariates WITH the intercept column (the whitened intercept M 1 is not constant, so it
+    travels as a covariate), M [n][n] the rotation.  y* = M y, Q* an orthonormal basis of M X,
+    y~* = y* residualised on Q* (twice, as design), and A = M^T [Q* | y~*], so that for a dosage
+    column g  (M g) . Q*_j = g . A_j
+    -> dict(A [n][rank + 1], rank = the rank of M X, xx = y~* . y~*)"""
+    y = np.asarray(y, np.float64)
+    M = np.asarray(M, np.float64)
+    n = M.shape[1]
+    if y.shape != (n,):
+        raise ValueError('lmm_design: one response y [n = %d] (got %s)' % (n, y.shape))
+    X = np.asarray(X, np.float64).reshape(n, -1)
+    if not (np.isfinite(y).all() and np.isfinite(X).all()):
+        raise ValueError('the response and the covariates must be finite')
+    ys = M @ y
+    Q = _orthonormal(M @ X)
+    yt = ys
+    for _ in range(2):
+        yt = yt - Q @ (Q.T @ yt)
+    xx = float(yt @ yt)
+    # what two passes leave of a response inside the span is rounding: (n eps)^2 of y* . y*
+    if not xx > (n * np.finfo(np.float64).eps) ** 2 * float(ys @ ys):
+        raise ValueError('the response is constant or a combination of the covariates')
+    return dict(A=np.ascontiguousarray(M.T @ np.column_stack([Q, yt])), rank=int(Q.shape[1]),
+                xx=xx)
+
+
+def lmm_centre(s1, n):
+    """the centre of a locus' dosages: the mean s1 / n rounded to a multiple of 2^-20, so that
+    {0, 1, 2} - centre is exact in fp32 (21 bits) and the table of gnx_assoc_quad and the fp64
+    terms of lmm_scan_stats speak of the same z.  Any centre gives the same test (the whitened
+    intercept is a covariate); the mean keeps the numbers, and so the fp32 error of q, small"""
+    return np.rint(np.asarray(s1, np.float64) / float(n) * 2.0 ** 20) / 2.0 ** 20
+
+
+def lmm_table(s1, n, use=None):
+    """the centred table of gnx_assoc_quad: val[l] = {0, 1, 2} - lmm_centre(s1_l, n) in fp32,
+    without rounding; zero for the loci that are not to be tested (use bool [L]; None: all)"""
+    val = (np.arange(3.0)[None, :] - lmm_centre(s1, n)[:, None]).astype(np.float32)
+    if use is not None:
+        val[~np.asarray(use, bool)] = 0.0
+    return val
+
+
+def lmm_testable(s1, s2, n, min_maf=0.01):
+    """what the integers decide: polymorphic (n s2 != s1^2) and maf >= min_maf -> (bool [L], maf)"""
+    s1 = np.asarray(s1, np.int64)
+    s2 = np.asarray(s2, np.int64)
+    frq = s1 / (2.0 * int(n))
+    maf = np.minimum(frq, 1.0 - frq)
+    return (int(n) * s2 - s1 * s1 != 0) & (maf >= min_maf), maf
+
+
+def lmm_scan_stats(q, DtY, s1, s2, n, dsn, min_maf=0.01, collinear_tol=1e-8, calibrate=False):
+    """the statistics of one mixed-model scan at a fixed delta from the device's sums: q [L] =
+    ||M z||^2 of the centred dosages z = g - lmm_centre(s1, n) (gnx_assoc_quad), DtY [L][rank + 1]
+    = D^T A against dsn = lmm_design's dict, s1, s2 [L].  z . A_j = DtY_lj - centre_l sum A_j;
+    gg = q - sum over the covariate columns of (z . A_j)^2; gx = z . A_y; the partial correlation
+    rho = gx / sqrt(gg xx), t = rho sqrt(df / (1 - rho^2)) with df = n - rank - 1,
+    beta = gx / gg (the response on the dosage; sigma^2 is re-estimated per locus in closed form,
+    delta is not: EMMAX / P3D / FaST-LMM with a fixed delta), se = sqrt((1 - rho^2) xx /
+    (df gg)), p from the t distribution (calibrate: from t^2 / gif against chi-square with 1 df)
+    and Benjamini-Hochberg q.  Not tested (NaN; left out of gif and q), as scan_stats:
+    monomorphic loci, decided on the integers; maf < min_maf; gg <= collinear_tol q
+    -> dict(beta, se, t, p, q [L][1], maf, tested [L], gif [1], df)"""
+    from scipy.stats import t as t_dist
+    n = int(n)
+    if n > 1 << 30:
+        raise ValueError('n above 2^30: n s2 - s1^2 would leave int64')
+    rank, xx = int(dsn['rank']), float(dsn['xx'])
+    df = n - rank - 1
+    if df < 1:
+        raise ValueError('%d individuals leave no degrees of freedom beside %d covariates'
+                         % (n, rank))
+    qf = np.asarray(q, np.float64)
+    ok, maf = lmm_testable(s1, s2, n, min_maf)
+    zA = np.asarray(DtY, np.float64) - np.outer(lmm_centre(s1, n), dsn['A'].sum(axis=0))
+    gg = qf - (zA[:, :rank] ** 2).sum(axis=1)
+    gx = zA[:, rank]
+    tested = ok & (gg > collinear_tol * qf)
+    with np.errstate(all='ignore'):
+        rho = np.clip(gx / np.sqrt(gg * xx), -1.0, 1.0)
+        t = rho * np.sqrt(df / (1.0 - rho * rho))
+        beta = gx / gg
+        se = np.sqrt((1.0 - rho * rho) * xx / (df * gg))
+    beta, se, t = beta[:, None], se[:, None], t[:, None]
+    for a in (beta, se, t):
+        a[~tested] = np.nan
+    gif = genomic_inflation(t) if tested.any() else np.full(1, np.nan)
+    p = calibrated_p(t, gif) if calibrate else 2.0 * t_dist.sf(np.abs(t), df)
+    p[~tested] = np.nan
+    return dict(beta=beta, se=se, t=t, p=p, q=bh_qvalues(p), maf=maf, tested=tested,
+                gif=np.asarray(gif, np.float64).reshape(1), df=df)
+
+
+def lmm_scan(cross, quad, n, y, X, M, min_maf=0.01, collinear_tol=1e-8, calibrate=False):
+    """one mixed-model scan over every locus at the rotation M (lmm_rotation; rounded to fp32
+    by the caller where quad is the device's): cross(Y) as scan's; quad(val, M, use) ->
+    dict(q, kernel_ms) is Device.assoc_quad bound to the sample or numpy_quad(D).  The cross
+    call runs first: its exact s1, s2 decide the loci quad is asked for and write its table
+    -> lmm_scan_stats' dict, kernel_ms (both calls) and seconds (cross, quad)"""
+    import time
+    dsn = lmm_design(y, X, M)
+    check_columns(dsn['A'].shape[1], 'lmm')
+    t0 = time.perf_counter()
+    got = cross(dsn['A'])
+    t1 = time.perf_counter()
+    use, _ = lmm_testable(got['s1'], got['s2'], n, min_maf)
+    qd = quad(lmm_table(got['s1'], n, use), M, use)
+    t2 = time.perf_counter()
+    out = lmm_scan_stats(qd['q'], got['DtY'], got['s1'], got['s2'], n, dsn, min_maf,
+                         collinear_tol, calibrate)
+    out['kernel_ms'] = float(got.get('kernel_ms', 0.0)) + float(qd.get('kernel_ms', 0.0))
+    out['seconds'] = dict(cross=t1 - t0, quad=t2 - t1)
+    return out

@@ -945,6 +945,32 @@ class Model:
                                       loci=loci, method=method, alpha=alpha, min_maf=min_maf,
                                       grm=grm)
 
+    def run_lmm(self, trt=0, spp=0, y=None, covars=(), n_pcs=0, individs=None, n=None, loci=None,
+                grm=None, grm_loci=None, method='gcta', alpha=-1.0, min_maf=0.01, delta=None,
+                calibrate=False, collinear_tol=1e-8):
+        """mixed-model genome-wide association scan among at most 8192 individuals (an
+        extension: the reference has no such analysis): run_gwas' regression with a random effect
+        u ~ N(0, Vg G) against population structure and relatedness, y = X b + g beta + u + e, G
+        the additive relationship matrix of calc_grm over the loci grm_loci (all by default;
+        leave a region out by hand - there is no automatic leave-one-chromosome-out).  The ratio
+        delta = Ve / Vg is calc_heritability's REML estimate of the model without a locus, or
+        the given delta, and stays fixed over the scan (EMMAX / P3D / FaST-LMM with a fixed
+        delta; it is not refitted per locus as exact GEMMA does); the per-locus quadratic forms
+        g^T (G + delta I)^-1 g run on the matrix cores (gnx_assoc_quad), the cross-products in
+        fp64 (gnx_assoc_cross).  The response is the phenotype z of Trait trt or one y [n] in
+        ascending-id order (several responses: one call each, with grm= shared).  covars, n_pcs,
+        individs, n, loci, min_maf, calibrate as run_gwas; grm, method, alpha as
+        calc_heritability.  A locus whose whitened dosage keeps no more than collinear_tol of
+        its squared length beside the covariates is not tested
+        -> dict: loci, beta, se, t, p, q [n_loci][1], maf, tested, gif [1], df, ids, trait_loci,
+        kernel_ms, delta, h2, Vg, Ve, at_boundary, n_loci_grm, seconds (grm, eigh, reml, quad,
+        cross)"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._run_lmm(trt_num=self._get_trt_num(spp, trt), y=y, covars=covars, n_pcs=n_pcs,
+                            individs=self._test_sample(spp, individs, n), loci=loci, grm=grm,
+                            grm_loci=grm_loci, method=method, alpha=alpha, min_maf=min_maf,
+                            delta=delta, calibrate=calibrate, collinear_tol=collinear_tol)
+
     def predict_breeding_values(self, trt=0, spp=0, y=None, covars=(), n_pcs=0, train=None,
                                 individs=None, n=None, loci=None, method='gcta', alpha=-1.0,
                                 min_maf=0.01, grm=None):

@@ -720,6 +720,60 @@ class SpeciesAnalyses:
             out['accuracy'] = acc
         return out
 
+    def _run_lmm(self, trt_num=0, y=None, covars=(), n_pcs=0, individs=None, loci=None, grm=None,
+                 grm_loci=None, method='gcta', alpha=-1.0, min_maf=0.01, delta=None,
+                 calibrate=False, collinear_tol=1e-8):
+        """a mixed-model association scan over the living individuals asked for (all by default;
+        at most 8192): per locus the test of beta in y = X b + g beta + u + e, u ~ N(0, Vg G),
+        with G the additive relationship matrix of the loci grm_loci (_calc_grm; grm: a previous
+        result of the same individuals, which keeps its eigendecomposition under 'eig'), X an
+        intercept, the covariates and the first n_pcs genetic PCs.  The request, the response and
+        G are _calc_heritability's; delta = Ve / Vg is its REML estimate of the model without a
+        locus (delta: a given ratio instead) and stays fixed over the scan (sim/assoc.py,
+        lmm_scan_stats).  One response per call: delta belongs to the response, so y [n][r] is
+        refused.  One pass of gnx_assoc_cross and one of gnx_assoc_quad (f32 matrix cores, fp64
+        sums; the rotation is rounded to fp32 once and every term uses the rounded one)
+        -> _run_gwas' dict without pcs, plus delta, h2, Vg, Ve, at_boundary (NaN / False with a
+        given delta), n_loci_grm, seconds (grm, eigh, reml, quad, cross)"""
+        import time
+        from ..sim import assoc as _as
+        from ..sim import quantgen as _qg
+        who = 'run_lmm'
+        if y is not None and np.ndim(y) != 1:
+            raise ValueError('%s: one response y [n] per call (delta is fitted per response; got '
+                             'shape %s)' % (who, np.shape(y)))
+        if delta is not None and (isinstance(delta, bool) or not np.isfinite(delta)
+                                  or not delta > 0):
+            raise ValueError('%s: delta: a positive, finite ratio Ve / Vg (got %r)' % (who, delta))
+        trait_loci = None
+        if y is None and self.gen_arch.traits and trt_num in self.gen_arch.traits:
+            trait_loci = np.asarray(self.gen_arch.traits[trt_num].loci)
+        ids, slots, y, X, grm, _, seconds = self._quantgen_request(
+            who, trt_num, y, covars, n_pcs, individs, grm_loci, method, alpha, min_maf, grm)
+        n = int(ids.size)
+        fit = dict(h2=float('nan'), Vg=float('nan'), Ve=float('nan'), at_boundary=False)
+        seconds['reml'] = 0.0
+        if delta is None:
+            t0 = time.perf_counter()
+            fit = _qg.reml(grm['eig'][0], grm['eig'][1], y, X)
+            seconds['reml'] = time.perf_counter() - t0
+            delta = fit['delta']
+        M = _as.lmm_rotation(grm['eig'][0], grm['eig'][1], delta).astype(np.float32)
+
+        def quad(val, _, use):               # the device takes the fp32 M itself
+            if not use.any():
+                return dict(q=np.zeros(self._dev.L), kernel_ms=0.0)
+            _, mask = self._geno_loci(np.flatnonzero(use))
+            return self._dev.assoc_quad(val, M, slots, mask)
+
+        res = _as.lmm_scan(lambda Y: self._dev.assoc_cross(Y, slots), quad, n, y, X,
+                           M.astype(np.float64), min_maf, collinear_tol, calibrate)
+        seconds.update(res['seconds'])
+        return self._assoc_result(res, ids, loci, trait_loci, delta=float(delta),
+                                  h2=fit['h2'], Vg=fit['Vg'], Ve=fit['Ve'],
+                                  at_boundary=fit['at_boundary'], n_loci_grm=grm['n_loci'],
+                                  seconds=seconds)
+
     # -- Mantel tests and MMRR (sim/mmrr.py; csrc/gnx_mantel.hip) --------------------------
     def _dist_predictors(self, who, predictors, env_lyrs, trts):
         """the device columns [(field, index), ...] of each named predictor: 'geo' = (x, y),

@@ -95,6 +95,8 @@ _NOT_TILED = {
                           'implemented; run the model on one GPU',
     '_predict_breeding_values': 'predict_breeding_values with a Species tiled over several GPUs '
                                 'is not implemented; run the model on one GPU',
+    '_run_lmm': 'run_lmm with a Species tiled over several GPUs is not implemented; run the '
+                'model on one GPU',
     # identity tracts (a pair of individuals of different tiles: a gather of the sample)
     '_calc_roh': 'calc_roh with a Species tiled over several GPUs is not '
                  'implemented; run the model on one GPU',

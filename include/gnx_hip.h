@@ -1174,6 +1174,27 @@ int gnx_assoc_cross(gnx_state* h, int64_t n, const int64_t* slots /*NULL: all li
                     const double* Y, double* DtY, int64_t* s1, int64_t* s2, int64_t* stretch,
                     int64_t* stretches, double* kernel_ms);
 
+/* The quadratic forms of a mixed-model scan (csrc/gnx_quad.hip): for the loci l of the mask
+ *   q[l] = sum over k < m of ( sum over i < n of M[k][i] * val[l][d_il] )^2,   0 elsewhere,
+ * double [L] on the HOST.  val: fp32 [L][3] on the HOST, the value of locus l at dosage 0, 1, 2,
+ * as gnx_grm's (the host writes the centring into it; the kernel only selects).  M: fp32 [m][n]
+ * on the HOST, 1 <= m <= 8192, columns in the order of the slots: the n x n rotation
+ * diag((lambda + delta)^-1/2) U^T of a relationship matrix gives z_l^T (G + delta I)^-1 z_l
+ * (geonomics_amd/sim/assoc.py, lmm_*), its top rows alone the communality of every locus.
+ * 1 <= n <= 8192; n, slots, locus_mask and the preconditions as gnx_geno_gram.  f32 MFMA over
+ * the individuals: every fp32 chain holds at most 1024 products and the chains are added in fp64,
+ * so with C_kl = sum_i M_ki z_il and S_kl = sum_i |M_ki z_il|
+ *   |dC_kl| <= e_kl := (1.01 * min(n, 1024) * 2^-24 + n * 2^-53) * S_kl,
+ *   |dq_l|  <= sum_k (2 |C_kl| e_kl + e_kl^2) + m * 2^-53 * q_l.
+ * The squares are added in one fixed order without atomics: a repeated call is bit-equal.
+ * Individuals past n of a partial stage, padding rows of M and loci outside the mask contribute
+ * exactly 0.  *kernel_ms (may be NULL): the HIP-event time of the call's kernels.  Refused
+ * (return 1) before anything is launched: no genomes, ghost records, n or m outside 1..8192, a
+ * null pointer, a NaN or infinity in val or M, a slot out of range, n != N with slots NULL.  */
+int gnx_assoc_quad(gnx_state* h, int64_t n, const int64_t* slots /*NULL: all living*/,
+                   const uint64_t* locus_mask, const float* val, int32_t m, const float* M,
+                   double* q, double* kernel_ms);
+
 /* ---- lineages through the recorded pedigree (csrc/gnx_lineage.hip; reference
  *      structs/genome.py:1638-1782 _get_lineage_dicts, structs/species.py:1242-1343) ---------
  * The pedigree is recorded on the host (geonomics_amd/structs/pedigree.py, TreeTables.
