@@ -999,15 +999,20 @@ class Device:
                                          _ptr(m, C.c_uint64), _ptr(out, C.c_int64)))
         return out
 
+    def _val_table(self, val):
+        """the table of grm and assoc_quad: fp32 [L][3], the value of each locus at dosage 0, 1, 2"""
+        v = _arr(val, np.float32)
+        if v.shape != (self.L, 3):
+            raise ValueError('val: shape %s, not (L = %d, 3)' % (v.shape, self.L))
+        return v
+
     def grm(self, val, slots=None, locus_mask=None):
         """G_ij = sum over the masked loci of val[l][d_il] val[l][d_jl] for `slots` (all living
         slots by default; at most 8192): val fp32 [L][3], the value of each locus at dosage 0, 1,
         2 (include/gnx_hip.h, gnx_grm) -> G float64 [n][n], symmetric"""
         s, n = self._geno_slots(slots)
         m = self._locus_mask_words(locus_mask)
-        v = _arr(val, np.float32)
-        if v.shape != (self.L, 3):
-            raise ValueError('val: shape %s, not (L = %d, 3)' % (v.shape, self.L))
+        v = self._val_table(val)
         # (the library refuses n outside 1..8192 before it writes: no n x n buffer for that)
         out = np.zeros((n, n) if 1 <= n <= 8192 else (0, 0), np.float64)
         self._chk(self.lib.gnx_grm(self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64),
@@ -1471,9 +1476,7 @@ class Device:
         host, finite, 1 <= m <= 8192 -> dict(q fp64 [L], 0 outside the mask; kernel_ms)"""
         s, n = self._geno_slots(slots)
         mk = self._locus_mask_words(locus_mask)
-        v = _arr(val, np.float32)
-        if v.shape != (self.L, 3):
-            raise ValueError('val: shape %s, not (L = %d, 3)' % (v.shape, self.L))
+        v = self._val_table(val)
         M = _arr(M, np.float32)
         if M.ndim != 2 or M.shape[1] != n:
             raise ValueError('M: %s, not [m][n = %d]' % (M.shape, n))

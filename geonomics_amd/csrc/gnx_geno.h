@@ -11,8 +11,71 @@
 
 typedef unsigned long long u64;
 
-// words per LDS stage of k_geno_gram: the word count of its operand is a multiple of it
+// words per LDS stage of the 64 x 64 tile: the word count of its operand is a multiple of it
 #define GRAM_GK 16
+
+// ---- the 64 x 64 popcount tile of a 256-thread block over X [rows][2][Wm] (k_sgs_pairs,
+// k_tract_pairs).  LDS: [word][hom][row], GRAM_GK words of the tile's 64 rows (A) and 64
+// columns (B) per stage, so consecutive threads read consecutive u64.  The kernel declares the
+// stage __shared__.  (k_geno_gram and kin_tile of gnx_kin.hip keep their own copies of the
+// walk: the two kernels with one tile per block measured 1 to 5 % slower on geno_tile64, the
+// two that stride over a task list did not)
+struct GenoStage {
+  u64 A[GRAM_GK][2][64];
+  u64 B[GRAM_GK][2][64];
+};
+
+// words k0 .. k0 + GRAM_GK - 1 of rows a0 .. a0 + 63 into S.A and of rows b0 .. b0 + 63 into S.B
+// (no barrier: the caller places them)
+__device__ __forceinline__ void geno_stage_load(GenoStage& S, const u64* __restrict__ X, int Wm,
+                                                int64_t a0, int64_t b0, int k0) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const int q = tid + 256 * s;                      // (row, hom, word) with the word fastest
+    const int row = q >> 5, hh = (q >> 4) & 1, kk = q & 15;
+    S.A[kk][hh][row] = X[((a0 + row) * 2 + hh) * Wm + k0 + kk];
+    S.B[kk][hh][row] = X[((b0 + row) * 2 + hh) * Wm + k0 + kk];
+  }
+}
+
+// the walk over all Wm words: thread (tx, ty) = (tid & 15, tid >> 4) owns rows a0 + ty + 16 r and
+// columns b0 + tx + 16 c, and word(ai, bi, aj, bj) takes, word by word, homologues 0 (a) and 1
+// (b) of its four rows (i) and four columns (j).  Ends behind a barrier: S may be reused.
+template <class Word>
+__device__ __forceinline__ void geno_tile64(GenoStage& S, const u64* __restrict__ X, int Wm,
+                                            int64_t a0, int64_t b0, Word&& word) {
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  for (int k0 = 0; k0 < Wm; k0 += GRAM_GK) {
+    geno_stage_load(S, X, Wm, a0, b0, k0);
+    __syncthreads();
+#pragma unroll 4
+    for (int kk = 0; kk < GRAM_GK; ++kk) {
+      u64 ai[4], bi[4], aj[4], bj[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        ai[r] = S.A[kk][0][ty + 16 * r];
+        bi[r] = S.A[kk][1][ty + 16 * r];
+        aj[r] = S.B[kk][0][tx + 16 * r];
+        bj[r] = S.B[kk][1][tx + 16 * r];
+      }
+      word(ai, bi, aj, bj);
+    }
+    __syncthreads();
+  }
+}
+
+// acc[r][c] += the dosage dot product of row r and column c over one word
+__device__ __forceinline__ void geno_dot16(int (&acc)[4][4], const u64 (&ai)[4],
+                                           const u64 (&bi)[4], const u64 (&aj)[4],
+                                           const u64 (&bj)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      acc[r][c] += __popcll(ai[r] & aj[c]) + __popcll(ai[r] & bj[c]) +
+                   __popcll(bi[r] & aj[c]) + __popcll(bi[r] & bj[c]);
+}
 
 // gnx_geno.hip
 __global__ void k_geno_rows(int64_t n, const int64_t* __restrict__ slots,
@@ -114,6 +177,24 @@ int geno_operand(gnx_state* h, GnxScratch& s, int64_t n_pad, const std::vector<i
     GNXCHK(gnx_h2d(h, op->wmask, wmask.data(), op->nw * sizeof(u64)));
   }
   return 0;
+}
+
+// the words' three-value tables of gnx_grm and gnx_assoc_quad, [nw_pad][64][4] (nw_pad >= op.nw):
+// entry [bit][d] = val[locus][d] for d = 0, 1, 2; zero for the loci outside the mask, the
+// padding bits, the words past op.nw and at [bit][3]
+std::vector<float> geno_tables(const GenoOperand& op, const std::vector<int32_t>& widx,
+                               const std::vector<u64>& wmask, const float* val, int nw_pad) {
+  std::vector<float> tab((size_t)nw_pad * 256, 0.f);
+  for (int q = 0; q < op.nw; ++q)
+    for (int bit = 0; bit < 64; ++bit)
+      if ((wmask[q] >> bit) & 1ull) {
+        const float* v = val + ((int64_t)widx[q] * 64 + bit) * 3;
+        float* t = &tab[((size_t)q * 64 + bit) * 4];
+        t[0] = v[0];
+        t[1] = v[1];
+        t[2] = v[2];
+      }
+  return tab;
 }
 
 // X of the genome rows d_rows [n]: rows n .. n_pad - 1 and words nw .. Wm - 1 are zero

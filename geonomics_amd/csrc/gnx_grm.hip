@@ -11,70 +11,50 @@
 //
 // The operand is the gathered X [rows][2][words] of the Gram kernel (gnx_geno.h: masked words
 // only, rows past n zero).  One 128 x 128 tile of G per 256-thread block, upper triangle of tiles
-// only, mirrored on the write; wave (wr, wc) of the 2 x 2 waves owns 64 x 64 of it as 2 x 2
-// accumulators of v_mfma_f32_32x32x2_f32.  A stage is GRM_KS = 32 loci: thread t expands the 32
+// only, mirrored on the write; the waves' share of it, the MFMA loop and the numerics contract
+// are MmWave's (gnx_mfma.h).  A stage is MM_KS = 32 loci (half a word): thread t expands the 32
 // bits of row t & 127 of the tile's rows (t < 128) or columns (t >= 128) to fp32 - two bit
 // extracts, an add, and one LDS read of the word's table at [locus][d] - into S[op][locus][row],
-// once per block, and all four waves read their MFMA operands from there: lane l takes
-// A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31], one float each, so lanes 0..31 read
-// consecutive floats of locus 2 kk and lanes 32..63 of locus 2 kk + 1.
+// once per block, and all four waves read their MFMA operands from there.
 //
-// Numerics.  The MFMA result is a k-ordered fp32 fma chain.  After GRM_FLUSH = 16 words (at most
-// 1024 used loci) the fp32 accumulators are added into fp64 registers and cleared, so no fp32
-// chain is longer than 1024 products; the fp64 sum runs in word order.  Nothing is added
-// atomically: a repeated call is bit-equal.  The mirror writes the value itself, and a diagonal
+// Numerics (gnx_mfma.h).  The chains are flushed after GRM_FLUSH = 16 words (at most 1024 used
+// loci); the fp64 sum runs in word order.  The mirror writes the value itself, and a diagonal
 // tile writes only its upper triangle (and mirrors it), so G == G^T exactly.
-//
-// What contributes nothing expands to 0.0f, never to val[l][0] (non-zero for a centred locus):
-// the host zeroes the table of the loci outside the mask and of the padding bits past L, and a
-// row i >= n reads entry 3 of every locus, which is 0.
 #include "gnx_geno.h"
+#include "gnx_mfma.h"
 
-#define GRM_T 128        // tile edge
-#define GRM_KS 32        // loci per LDS stage (half a word)
 #define GRM_FLUSH 16     // words per fp32 chain: 1024 loci
-
-typedef float grm_f32x16 __attribute__((ext_vector_type(16)));
 
 // tab [nw][64][4]: the word's table, entry [bit][d] for d = 0, 1, 2 and [bit][3] = 0.
 // MODE 0 is the kernel; 1 (the expansion alone, no MFMA) and 2 (the MFMAs alone, on a stage of
 // zeros) only split its time for tools/grm_bench.py (gnx_grm_probe): zeros come back.
 template <int MODE>
-// two blocks per CU (226 VGPRs, 34 KiB of LDS): one block's expansion runs under the other's MFMAs
+// two blocks per CU (225 VGPRs, 34 KiB of LDS): one block's expansion runs under the other's MFMAs
 __global__ void __launch_bounds__(256, 2)
 k_grm(int64_t n, int nw, int Wm, const u64* __restrict__ X, const float* __restrict__ tab,
       double* __restrict__ out) {
   const int ti = blockIdx.y, tj = blockIdx.x;
   if (tj < ti) return;                              // block-uniform
-  __shared__ float S[2][GRM_KS][GRM_T];
+  __shared__ float S[2][MM_KS][MM_T];
   __shared__ float vt[2][64 * 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, r = lane & 31, hk = lane >> 5;
-  const int64_t i0 = (int64_t)ti * GRM_T, j0 = (int64_t)tj * GRM_T;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int64_t i0 = (int64_t)ti * MM_T, j0 = (int64_t)tj * MM_T;
   // the expansion's share of this thread: one row of the rows (op 0) or columns (op 1)
-  const int op = tid >> 7, xrow = tid & (GRM_T - 1);
+  const int op = tid >> 7, xrow = tid & (MM_T - 1);
   const int64_t gi = (op ? j0 : i0) + xrow;
   const unsigned dead = gi < n ? 0u : 3u;
   const u64* xa = X + (gi * 2) * Wm;
   const u64* xb = xa + Wm;
   float* dst = &S[op][0][xrow];
-  const float* sa = &S[0][hk][wr * 64 + r];
-  const float* sb = &S[1][hk][wc * 64 + r];
+  const float* sa = mm_operand(S[0], wr * 64, lane);
+  const float* sb = mm_operand(S[1], wc * 64, lane);
 
-  grm_f32x16 acc[2][2];
-  double sum[2][2][16];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        acc[m][c][e] = 0.f;
-        sum[m][c][e] = 0.0;
-      }
+  MmWave W;
+  W.clear();
 
   if (MODE == 2) {
-    for (int q = tid; q < 2 * GRM_KS * GRM_T; q += 256) (&S[0][0][0])[q] = 0.f;
+    for (int q = tid; q < 2 * MM_KS * MM_T; q += 256) (&S[0][0][0])[q] = 0.f;
   }
   u64 a = 0, b = 0;
   float tv = 0.f;
@@ -96,51 +76,29 @@ k_grm(int64_t n, int nw, int Wm, const u64* __restrict__ X, const float* __restr
     for (int hf = 0; hf < 2; ++hf) {
       __syncthreads();                    // the last stage's operands are read; vt[p] is written
       const unsigned a32 = (unsigned)(ca >> (32 * hf)), b32 = (unsigned)(cb >> (32 * hf));
-      const float* t = &vt[p][hf * GRM_KS * 4];
+      const float* t = &vt[p][hf * MM_KS * 4];
       if (MODE != 2) {
 #pragma unroll
-        for (int l = 0; l < GRM_KS; ++l) {
-          const unsigned d = (((a32 >> l) & 1u) + ((b32 >> l) & 1u)) | dead;
-          dst[l * GRM_T] = t[l * 4 + d];
-        }
+        for (int l = 0; l < MM_KS; ++l) dst[l * MM_T] = mm_dosage(t, a32, b32, l, dead);
       }
       __syncthreads();
       if (MODE == 1) continue;
-#pragma unroll 4
-      for (int kk = 0; kk < GRM_KS / 2; ++kk) {
-        const float a0 = sa[(2 * kk) * GRM_T], a1 = sa[(2 * kk) * GRM_T + 32];
-        const float b0 = sb[(2 * kk) * GRM_T], b1 = sb[(2 * kk) * GRM_T + 32];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-      }
+      W.stage(sa, sb);
     }
-    if ((q + 1) % GRM_FLUSH == 0 || q + 1 == nw) {        // block-uniform
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            sum[m][c][e] += (double)acc[m][c][e];
-            acc[m][c][e] = 0.f;
-          }
-    }
+    if ((q + 1) % GRM_FLUSH == 0 || q + 1 == nw) W.flush();      // block-uniform
   }
   if (MODE == 1) return;               // (MODE 2 writes its zeros: the MFMAs must stay live)
-  // C/D of the 32 x 32 MFMA: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int64_t i = i0 + wr * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * hk;
-        const int64_t j = j0 + wc * 64 + c * 32 + r;
+        const int64_t i = mm_row(i0 + wr * 64 + m * 32, e, lane);
+        const int64_t j = j0 + wc * 64 + c * 32 + (lane & 31);
         if (i < n && j < n && (ti != tj || j >= i)) {
-          out[i * n + j] = sum[m][c][e];
-          if (i != j) out[j * n + i] = sum[m][c][e];
+          out[i * n + j] = W.sum[m][c][e];
+          if (i != j) out[j * n + i] = W.sum[m][c][e];
         }
       }
 }
@@ -181,21 +139,11 @@ extern "C" int gnx_grm(gnx_state* h, int64_t n, const int64_t* slots, const uint
   std::vector<int32_t> widx;
   std::vector<u64> wmask;
   geno_words(h, locus_mask, widx, wmask);
-  const int64_t n_pad = (n + GRM_T - 1) / GRM_T * GRM_T;
-  const int T = (int)(n_pad / GRM_T);
+  const int64_t n_pad = (n + MM_T - 1) / MM_T * MM_T;
+  const int T = (int)(n_pad / MM_T);
   GenoOperand op;
   GNXCHK(geno_operand(h, s, n_pad, widx, wmask, 0, &op));
-  // the words' tables: zero for the loci outside the mask and the padding bits, and at [bit][3]
-  std::vector<float> tab((size_t)op.nw * 256, 0.f);
-  for (int q = 0; q < op.nw; ++q)
-    for (int bit = 0; bit < 64; ++bit)
-      if ((wmask[q] >> bit) & 1ull) {
-        const float* v = val + ((int64_t)widx[q] * 64 + bit) * 3;
-        float* t = &tab[((size_t)q * 64 + bit) * 4];
-        t[0] = v[0];
-        t[1] = v[1];
-        t[2] = v[2];
-      }
+  const std::vector<float> tab = geno_tables(op, widx, wmask, val, op.nw);
   float* d_tab = nullptr;
   double* d_G = nullptr;
   GNXCHK(s.get(&d_tab, tab.size()));

@@ -8,18 +8,16 @@
 //
 // The operand is the gathered X [rows][2][words] of the Gram kernel (gnx_geno.h: masked words
 // only, rows past n zero).  One 256-thread block per 128 rows of M x 128 loci (two words of the
-// list); wave (wr, wc) of the 2 x 2 waves owns 64 x 64 of C = M Z as 2 x 2 accumulators of
-// v_mfma_f32_32x32x2_f32, operands and C/D layout as k_grm.  The reduction runs over the
-// individuals in stages of QD_KS = 32.  Per stage thread (ind = t >> 3, seg = t & 7) copies 16
-// floats of row i0 + ind of M^T (k_quad_transpose writes it first, padded with zero rows to a
-// multiple of 32 and zero columns to a multiple of 128, so the copy is contiguous along k) and expands 16
-// loci of individual i0 + ind through the block's table, which sits in LDS once per block: a
-// block's loci do not change.  The next stage's 16 floats and two words are loaded before the
+// list) of C = M Z; the waves' share of it, the MFMA loop and the numerics contract are MmWave's
+// (gnx_mfma.h).  The reduction runs over the individuals in stages of MM_KS = 32.  Per stage
+// thread (ind = t >> 3, seg = t & 7) copies 16 floats of row i0 + ind of M^T (k_quad_transpose
+// writes it first, padded with zero rows to a multiple of 32 and zero columns to a multiple of
+// 128, so the copy is contiguous along k) and expands 16 loci of individual i0 + ind through the
+// block's table, which sits in LDS once per block: a block's loci do not change.  The next stage's 16 floats and two words are loaded before the
 // MFMAs of the current one.  The locus tile is the fastest grid dimension: consecutive blocks
 // read the same 128 x n slab of M (4 MiB at n = 8192) out of L2.
 //
-// Numerics.  After QD_FLUSH = 32 stages (1024 individuals) the fp32 accumulators are added into
-// fp64 registers and cleared, so no fp32 chain holds more than 1024 products:
+// Numerics (gnx_mfma.h).  The chains are flushed after QD_FLUSH = 32 stages (1024 individuals):
 //   |dC_kl| <= e_kl := (1.01 min(n, 1024) 2^-24 + n 2^-53) sum_i |M_ki z_il|,
 //   |dq_l|  <= sum_k (2 |C_kl| e_kl + e_kl^2) + m 2^-53 q_l.
 // The epilogue has one order and no atomics: a lane squares its fp64 sums and adds them over the
@@ -27,19 +25,14 @@
 // wr waves meet in LDS, and one partial per (128 rows of M, locus) is written; k_quad_sum adds
 // the partials in ascending row order.  A repeated call is bit-equal.
 //
-// What contributes nothing is exactly 0: the table of the loci outside the mask and of the
-// padding bits is zero, an individual i >= n reads entry 3 of every locus (0), and the padding
-// rows and columns of M^T are zero.
+// The padding rows and columns of M^T are zero, so they too contribute exactly 0.
 #include <cmath>
 #include <cstring>
 #include "gnx_geno.h"
+#include "gnx_mfma.h"
 
-#define QD_T 128         // tile edge: rows of M, loci
-#define QD_KS 32         // individuals per LDS stage
 #define QD_FLUSH 32      // stages per fp32 chain: 1024 individuals
 #define QD_VT 68         // floats of the table per 16 loci: 64 and 4 of padding (LDS banks)
-
-typedef float qd_f32x16 __attribute__((ext_vector_type(16)));
 
 // Mt [n_pad][m_pad] = M^T padded; X [n_pad][2][Wm]; tab [nwp][64][4] with [bit][3] = 0;
 // P [m_pad / 128][nwp * 64]: P[kt][c] = sum over the rows k of tile kt of C_kc^2
@@ -48,58 +41,48 @@ __global__ void __launch_bounds__(256, 2)
 k_quad(int64_t n, int64_t n_pad, int64_t m_pad, int Wm, int64_t Lp, const float* __restrict__ Mt,
        const u64* __restrict__ X, const float* __restrict__ tab, double* __restrict__ P) {
   // [0]: M^T slab [i][k], [1]: Z [i][locus]; written as float4
-  __shared__ __attribute__((aligned(16))) float S[2][QD_KS][QD_T];
+  __shared__ __attribute__((aligned(16))) float S[2][MM_KS][MM_T];
   __shared__ float vt[8 * QD_VT];
-  __shared__ double red[2][QD_T];
+  __shared__ double red[2][MM_T];
   const int lt = blockIdx.x, kt = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1, r = lane & 31, hk = lane >> 5;
   const int ind = tid >> 3, seg = tid & 7;
-  const float* ma = Mt + (int64_t)ind * m_pad + (int64_t)kt * QD_T + seg * 16;
+  const float* ma = Mt + (int64_t)ind * m_pad + (int64_t)kt * MM_T + seg * 16;
   const u64* xa = X + ((int64_t)ind * 2) * Wm + lt * 2 + (seg >> 2);
   const int sh = (seg & 3) * 16;
   float4* da = reinterpret_cast<float4*>(&S[0][ind][seg * 16]);
   float4* db = reinterpret_cast<float4*>(&S[1][ind][seg * 16]);
   const float* t = &vt[seg * QD_VT];
-  const float* sa = &S[0][hk][wr * 64 + r];
-  const float* sb = &S[1][hk][wc * 64 + r];
+  const float* sa = mm_operand(S[0], wr * 64, lane);
+  const float* sb = mm_operand(S[1], wc * 64, lane);
 
-  for (int j = tid; j < QD_T * 4; j += 256)    // locus j >> 2 of the tile, entry j & 3
-    vt[(j >> 6) * QD_VT + (j & 63)] = tab[(int64_t)lt * (QD_T * 4) + j];
+  for (int j = tid; j < MM_T * 4; j += 256)    // locus j >> 2 of the tile, entry j & 3
+    vt[(j >> 6) * QD_VT + (j & 63)] = tab[(int64_t)lt * (MM_T * 4) + j];
 
-  qd_f32x16 acc[2][2];
-  double sum[2][2][16];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        acc[mi][c][e] = 0.f;
-        sum[mi][c][e] = 0.0;
-      }
+  MmWave W;
+  W.clear();
 
-  const int stages = (int)(n_pad / QD_KS);
+  const int stages = (int)(n_pad / MM_KS);
   const float4* m4 = reinterpret_cast<const float4*>(ma);
   float4 p0 = m4[0], p1 = m4[1], p2 = m4[2], p3 = m4[3];
   u64 ha = xa[0], hb = xa[Wm];
   for (int s = 0; s < stages; ++s) {
     const unsigned a16 = (unsigned)(ha >> sh) & 0xffffu, b16 = (unsigned)(hb >> sh) & 0xffffu;
-    const unsigned dead = s * QD_KS + ind < (int)n ? 0u : 3u;
+    const unsigned dead = s * MM_KS + ind < (int)n ? 0u : 3u;
     __syncthreads();                      // the last stage's operands are read; vt is written
     da[0] = p0;
     da[1] = p1;
     da[2] = p2;
     da[3] = p3;
-#define QD_Z(l) t[(l) * 4 + ((((a16 >> (l)) & 1u) + ((b16 >> (l)) & 1u)) | dead)]
-    db[0] = make_float4(QD_Z(0), QD_Z(1), QD_Z(2), QD_Z(3));
-    db[1] = make_float4(QD_Z(4), QD_Z(5), QD_Z(6), QD_Z(7));
-    db[2] = make_float4(QD_Z(8), QD_Z(9), QD_Z(10), QD_Z(11));
-    db[3] = make_float4(QD_Z(12), QD_Z(13), QD_Z(14), QD_Z(15));
-#undef QD_Z
+    auto z = [&](int l) { return mm_dosage(t, a16, b16, l, dead); };
+    db[0] = make_float4(z(0), z(1), z(2), z(3));
+    db[1] = make_float4(z(4), z(5), z(6), z(7));
+    db[2] = make_float4(z(8), z(9), z(10), z(11));
+    db[3] = make_float4(z(12), z(13), z(14), z(15));
     if (s + 1 < stages) {                 // the next stage's, in flight under this stage's MFMAs
-      ma += QD_KS * m_pad;
-      xa += (int64_t)QD_KS * 2 * Wm;
+      ma += MM_KS * m_pad;
+      xa += (int64_t)MM_KS * 2 * Wm;
       m4 = reinterpret_cast<const float4*>(ma);
       p0 = m4[0];
       p1 = m4[1];
@@ -109,26 +92,8 @@ k_quad(int64_t n, int64_t n_pad, int64_t m_pad, int Wm, int64_t Lp, const float*
       hb = xa[Wm];
     }
     __syncthreads();
-#pragma unroll 4
-    for (int kk = 0; kk < QD_KS / 2; ++kk) {
-      const float a0 = sa[(2 * kk) * QD_T], a1 = sa[(2 * kk) * QD_T + 32];
-      const float b0 = sb[(2 * kk) * QD_T], b1 = sb[(2 * kk) * QD_T + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if ((s + 1) % QD_FLUSH == 0 || s + 1 == stages) {     // block-uniform
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            sum[mi][c][e] += (double)acc[mi][c][e];
-            acc[mi][c][e] = 0.f;
-          }
-    }
+    W.stage(sa, sb);
+    if ((s + 1) % QD_FLUSH == 0 || s + 1 == stages) W.flush();   // block-uniform
   }
   // C/D of the 32 x 32 MFMA: column = lane & 31; a lane's 16 elements and its lane ^ 32 partner's
   // are the 32 rows of that column, and every row of M is summed: the row map does not matter
@@ -138,12 +103,12 @@ k_quad(int64_t n, int64_t n_pad, int64_t m_pad, int Wm, int64_t Lp, const float*
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) v += sum[mi][c][e] * sum[mi][c][e];
+      for (int e = 0; e < 16; ++e) v += W.sum[mi][c][e] * W.sum[mi][c][e];
     v += __shfl_xor(v, 32);
     if (hk == 0) red[wr][wc * 64 + c * 32 + r] = v;
   }
   __syncthreads();
-  if (tid < QD_T) P[(int64_t)kt * Lp + (int64_t)lt * QD_T + tid] = red[0][tid] + red[1][tid];
+  if (tid < MM_T) P[(int64_t)kt * Lp + (int64_t)lt * MM_T + tid] = red[0][tid] + red[1][tid];
 }
 
 // Mt[i][k] = M[k][i] for k < m, i < n, in 32 x 32 tiles through LDS (block 32 x 8); the padding
@@ -237,25 +202,15 @@ extern "C" int gnx_assoc_quad(gnx_state* h, int64_t n, const int64_t* slots,
   std::vector<u64> wmask;
   geno_words(h, locus_mask, widx, wmask);
   if (widx.empty()) return 0;
-  const int64_t n_pad = (n + QD_KS - 1) / QD_KS * QD_KS;
-  const int64_t m_pad = ((int64_t)m + QD_T - 1) / QD_T * QD_T;
-  const int KT = (int)(m_pad / QD_T);
+  const int64_t n_pad = (n + MM_KS - 1) / MM_KS * MM_KS;
+  const int64_t m_pad = ((int64_t)m + MM_T - 1) / MM_T * MM_T;
+  const int KT = (int)(m_pad / MM_T);
   GenoOperand op;
   GNXCHK(geno_operand(h, s, n_pad, widx, wmask, 0, &op));
   const int nwp = (op.nw + 1) / 2 * 2;          // whole locus tiles; nwp <= Wm, a multiple of 16
   const int LT = nwp / 2;
   const int64_t Lp = (int64_t)nwp * 64;
-  // the words' tables: zero for the loci outside the mask and the padding bits, and at [bit][3]
-  std::vector<float> tab((size_t)nwp * 256, 0.f);
-  for (int w = 0; w < op.nw; ++w)
-    for (int bit = 0; bit < 64; ++bit)
-      if ((wmask[w] >> bit) & 1ull) {
-        const float* v = val + ((int64_t)widx[w] * 64 + bit) * 3;
-        float* t = &tab[((size_t)w * 64 + bit) * 4];
-        t[0] = v[0];
-        t[1] = v[1];
-        t[2] = v[2];
-      }
+  const std::vector<float> tab = geno_tables(op, widx, wmask, val, nwp);
   float *d_tab = nullptr, *d_M = nullptr, *d_Mt = nullptr;
   double *d_P = nullptr, *d_q = nullptr;
   GNXCHK(s.get(&d_tab, tab.size()));

@@ -17,9 +17,9 @@
 // rows of (cell, cell) or of (cell, one of its four forward neighbours).
 //
 // k_sgs_pairs: a fixed grid of workgroups, workgroup g takes tasks g, g + grid, ...  The body of
-// a task is the LDS-staged popcount tile of k_geno_gram (stages of GRAM_GK words, thread (tx, ty)
-// owns rows ty + 16 r and columns tx + 16 c).  The epilogue takes the thread's four rows one at a
-// time (all 16 pairs at once take more than 256 registers): r, the
+// a task is the popcount tile of k_geno_gram (geno_tile64 with geno_dot16, gnx_geno.h: thread
+// (tx, ty) owns rows ty + 16 r and columns tx + 16 c).  The epilogue takes the thread's four
+// rows one at a time (all 16 pairs at once take more than 256 registers): r, the
 // class and ln r of the row's four pairs (a diagonal tile of a cell with itself keeps i < j),
 // then, for every class present in the wave, each lane adds its own pairs' ten terms, the wave
 // adds its lanes by an xor butterfly and lane 0 adds the result to the wave's accumulators in LDS.  A workgroup
@@ -127,8 +127,7 @@ k_sgs_pairs(int64_t n_tasks, int Wm, int n_bins, const SgsTask* __restrict__ tas
             const float* __restrict__ ys, const int32_t* __restrict__ self,
             const double* __restrict__ w, const double* __restrict__ edges,
             long long* __restrict__ ipart, double* __restrict__ fpart) {
-  __shared__ u64 As[GRAM_GK][2][64];
-  __shared__ u64 Bs[GRAM_GK][2][64];
+  __shared__ GenoStage S;
   __shared__ double E[SGS_NB + 1];
   __shared__ float cx[2][64], cy[2][64];
   __shared__ int32_t cs[2][64];
@@ -152,34 +151,9 @@ k_sgs_pairs(int64_t n_tasks, int Wm, int n_bins, const SgsTask* __restrict__ tas
       cw[side][i] = live ? w[row] : 0.0;
     }
     int acc[4][4] = {};
-    for (int k0 = 0; k0 < Wm; k0 += GRAM_GK) {
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        const int q = tid + 256 * s;                  // (row, hom, word) with the word fastest
-        const int row = q >> 5, hh = (q >> 4) & 1, kk = q & 15;
-        As[kk][hh][row] = X[(((int64_t)T.a0 + row) * 2 + hh) * Wm + k0 + kk];
-        Bs[kk][hh][row] = X[(((int64_t)T.b0 + row) * 2 + hh) * Wm + k0 + kk];
-      }
-      __syncthreads();
-#pragma unroll 4
-      for (int kk = 0; kk < GRAM_GK; ++kk) {
-        u64 ai[4], bi[4], aj[4], bj[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          ai[r] = As[kk][0][ty + 16 * r];
-          bi[r] = As[kk][1][ty + 16 * r];
-          aj[r] = Bs[kk][0][tx + 16 * r];
-          bj[r] = Bs[kk][1][tx + 16 * r];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            acc[r][c] += __popcll(ai[r] & aj[c]) + __popcll(ai[r] & bj[c]) +
-                         __popcll(bi[r] & aj[c]) + __popcll(bi[r] & bj[c]);
-      }
-      __syncthreads();
-    }
+    geno_tile64(S, X, Wm, T.a0, T.b0, [&](auto& ai, auto& bi, auto& aj, auto& bj) {
+      geno_dot16(acc, ai, bi, aj, bj);
+    });
     // ---- epilogue, one of the thread's four rows (four pairs) at a time: r, class, ln r
     const bool diag = T.a0 == T.b0;
     long long nz = 0;

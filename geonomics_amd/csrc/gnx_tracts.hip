@@ -27,12 +27,12 @@
 //
 // Pair scan, k_tract_pairs: the operand is k_geno_gather's X (every word, full mask), tiled 64 x 64
 // as k_geno_gram, upper triangle of tiles, GRAM_GK words of the tile's rows staged in LDS per
-// step.  Thread (tx, ty) owns the individual pairs (ty + 16 r, tx + 16 c) and keeps their 4 x 16
-// scanner states in registers across the stages: per stage it takes its pairs one after the other
-// (the words of the stage in order) and rotates the register file of states by one pair, so the
-// scanner exists once in the code and no state is indexed dynamically (no scratch).  A pair's
-// sums go to its [i][j] entry, which only this thread touches; k_tract_mirror fills the lower
-// triangle.
+// step (GenoStage and geno_stage_load of gnx_geno.h).  Thread (tx, ty) owns the individual
+// pairs (ty + 16 r, tx + 16 c) and keeps their 4 x 16 scanner states in registers across the
+// stages: per stage it takes its pairs one after the other (the words of the stage in order) and
+// rotates the register file of states by one pair, so the scanner exists once in the code and no
+// state is indexed dynamically (no scratch).  A pair's sums go to its [i][j] entry, which only
+// this thread touches; k_tract_mirror fills the lower triangle.
 //
 // hist is collected in LDS per workgroup and flushed with one atomic per bin; cover is an int32
 // difference array (+1 at s, -1 at e + 1) summed by k_tract_cover.
@@ -232,8 +232,7 @@ k_tract_pairs(int64_t n, int Wm, int L, int W64, const u64* __restrict__ X,
               int* __restrict__ cdiff) {
   const int ti = blockIdx.y, tj = blockIdx.x;
   if (tj < ti) return;                                // block-uniform
-  __shared__ u64 As[GRAM_GK][2][64];
-  __shared__ u64 Bs[GRAM_GK][2][64];
+  __shared__ GenoStage S;
   __shared__ u64 Bk[GRAM_GK];
   __shared__ long long E[TR_NB + 1];
   __shared__ unsigned long long Hs[TR_NB * 2];
@@ -247,13 +246,7 @@ k_tract_pairs(int64_t n, int Wm, int L, int W64, const u64* __restrict__ X,
   for (int q = 0; q < 64; ++q) st[q] = -1;
   for (int k0 = 0; k0 < Wm; k0 += GRAM_GK) {
     __syncthreads();                                  // the last stage's words have been read
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const int q = tid + 256 * s;                    // (row, hom, word) with the word fastest
-      const int row = q >> 5, hh = (q >> 4) & 1, kk = q & 15;
-      As[kk][hh][row] = X[((i0 + row) * 2 + hh) * Wm + k0 + kk];
-      Bs[kk][hh][row] = X[((j0 + row) * 2 + hh) * Wm + k0 + kk];
-    }
+    geno_stage_load(S, X, Wm, i0, j0, k0);
     if (tid < GRAM_GK) Bk[tid] = (brk && k0 + tid < W64) ? brk[k0 + tid] : 0ull;
     __syncthreads();
 #pragma unroll 1
@@ -271,8 +264,8 @@ k_tract_pairs(int64_t n, int Wm, int L, int W64, const u64* __restrict__ X,
         for (int kk = 0; kk < GRAM_GK; ++kk) {
           const int w = k0 + kk, base = w * 64;
           const u64 vm = tract_valid(w, L), B = Bk[kk];
-          const u64 a0 = As[kk][0][ri], a1 = As[kk][1][ri];
-          const u64 b0 = Bs[kk][0][cj], b1 = Bs[kk][1][cj];
+          const u64 a0 = S.A[kk][0][ri], a1 = S.A[kk][1][ri];
+          const u64 b0 = S.B[kk][0][cj], b1 = S.B[kk][1][cj];
           s1 = tract_step(s1, ~(a0 ^ b1) & vm, B, base, fast != 0, emit);
           if (!own) {
             s0 = tract_step(s0, ~(a0 ^ b0) & vm, B, base, fast != 0, emit);

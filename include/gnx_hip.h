@@ -1182,7 +1182,7 @@ int gnx_assoc_cross(gnx_state* h, int64_t n, const int64_t* slots /*NULL: all li
  * diag((lambda + delta)^-1/2) U^T of a relationship matrix gives z_l^T (G + delta I)^-1 z_l
  * (geonomics_amd/sim/assoc.py, lmm_*), its top rows alone the communality of every locus.
  * 1 <= n <= 8192; n, slots, locus_mask and the preconditions as gnx_geno_gram.  f32 MFMA over
- * the individuals: every fp32 chain holds at most 1024 products and the chains are added in fp64,
+ * the individuals under gnx_grm's contract (chains of at most 1024 products, added in fp64),
  * so with C_kl = sum_i M_ki z_il and S_kl = sum_i |M_ki z_il|
  *   |dC_kl| <= e_kl := (1.01 * min(n, 1024) * 2^-24 + n * 2^-53) * S_kl,
  *   |dq_l|  <= sum_k (2 |C_kl| e_kl + e_kl^2) + m * 2^-53 * q_l.

@@ -94,6 +94,25 @@ def test_identity_anchor_gives_the_second_moment(devs, L, n):
     np.testing.assert_array_equal(s2, (D[slots] ** 2).sum(0))
 
 
+@pytest.mark.parametrize('n', [33, 129])
+@pytest.mark.parametrize('L', [70, 1000])
+def test_trace_of_the_grm_equals_the_sum_of_the_identity_forms(devs, L, n):
+    """the two users of the shared f32 MFMA tile on one handle and one table: trace(G) and the sum
+    of q under M = I are both sum_i sum_l val[l][d_il]^2, an integer below 2^53 (at most
+    129 * 1000 * 49), whichever of the two reductions (over the loci, over the individuals) ran"""
+    dev, D = devs(L)
+    rng = np.random.RandomState(11 * L + n)
+    slots = rng.choice(N_ALL, n, replace=False).astype(np.int64)
+    loci = np.union1d(np.sort(rng.choice(L, L // 2, replace=False)), [L - 1])
+    for val, shift in ((_val012(L), 0), (_val012(L) + 5.0, 5)):
+        for mask, used in ((None, np.arange(L)), (_mask(loci, dev.W64), loci)):
+            ref = int(((D[slots][:, used] + shift) ** 2).sum())
+            assert 0 < ref < 2 ** 53
+            tr = np.trace(dev.grm(val, slots, mask))
+            qs = dev.assoc_quad(val, np.eye(n), slots, mask)['q'].sum()
+            assert tr == qs == float(ref)
+
+
 @pytest.mark.parametrize('n', [1025, 2081])
 def test_exact_across_the_flushes_of_the_fp32_chains(devs, n):
     dev, D = devs(70, N_BIG)
