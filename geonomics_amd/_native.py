@@ -5,6 +5,7 @@ missing, and creating a device state fails if there is no HIP device.
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -20,67 +21,6 @@ SURF_NONE, SURF_MIXTURE, SURF_UNIMODAL = 0, 1, 2
 (R_N, R_NPAIRS, R_K, R_D, R_COUNTS) = range(5)
 KERNELS = ['move', 'sort', 'permute', 'find_mates', 'pairs', 'offspring',
            'crossover', 'phenotype', 'density', 'death', 'compact', 'crossover_tail']
-
-EXPORTS = [
-    'gnx_create', 'gnx_destroy', 'gnx_last_error', 'gnx_words_per_hom', 'gnx_blocks_per_hom',
-    'gnx_set_stream', 'gnx_synchronize', 'gnx_upload_rasters',
-    'gnx_upload_layer', 'gnx_set_species_params', 'gnx_upload_population',
-    'gnx_init_population', 'gnx_set_recomb_paths', 'gnx_set_trait',
-    'gnx_set_dominance', 'gnx_set_deleterious', 'gnx_upload_genomes',
-    'gnx_assign_genomes', 'gnx_set_z', 'gnx_age', 'gnx_move',
-    'gnx_pop_dynamics', 'gnx_pop_dynamics_mate', 'gnx_pop_dynamics_die',
-    'gnx_set_z_range', 'gnx_step', 'gnx_counts', 'gnx_step_index',
-    'gnx_set_step_index', 'gnx_mutate', 'gnx_download', 'gnx_download_genomes',
-    'gnx_download_raster', 'gnx_spatial_diff_stats', 'gnx_op_move',
-    'gnx_op_move_draws', 'gnx_op_find_pairs', 'gnx_op_crossover',
-    'gnx_op_dispersal', 'gnx_op_density', 'gnx_density_lattice_dims', 'gnx_density_nmax',
-    'gnx_op_death_probs', 'gnx_op_mortality', 'gnx_profiling',
-    'gnx_kernel_time', 'gnx_tile_set', 'gnx_tile_export_migrants',
-    'gnx_tile_export_halo', 'gnx_tile_get_staged', 'gnx_tile_import',
-    'gnx_tile_import_ghosts', 'gnx_tile_pairs', 'gnx_tile_pair_info',
-    'gnx_density_bin_count', 'gnx_get_bins', 'gnx_set_bins',
-    'gnx_tile_offspring', 'gnx_tile_get_requests', 'gnx_tile_serve_gametes',
-    'gnx_tile_put_gametes', 'gnx_tile_finish_births', 'gnx_tile_die',
-    'gnx_set_max_id', 'gnx_stats_locus_counts', 'gnx_stats_ld',
-    'gnx_set_k_raster', 'gnx_last_births', 'gnx_set_positions', 'gnx_n_slots', 'gnx_stats_ld_counts',
-    'gnx_set_defer_crossover', 'gnx_last_crossover_births', 'gnx_set_crossover_overlap', 'gnx_set_crossover_split', 'gnx_debug_halves', 'gnx_spatial_diff_sums', 'gnx_last_crossover_jobs',
-    'gnx_genome_info', 'gnx_measure_copy', 'gnx_totals', 'gnx_reset_totals',
-    'gnx_path_counts', 'gnx_reset_path_counts',
-    'gnx_step_begin', 'gnx_step_mid', 'gnx_step_end', 'gnx_step_many',
-    'gnx_walk', 'gnx_walk_many', 'gnx_walk_history',
-    'gnx_comm_unique_id', 'gnx_comm_init_rccl', 'gnx_comm_init_single', 'gnx_comm_local_create',
-    'gnx_comm_local_join', 'gnx_comm_local_abort', 'gnx_comm_local_destroy', 'gnx_comm_free',
-    'gnx_comm_bytes_sent', 'gnx_comm_selftest', 'gnx_tile_step', 'gnx_set_id_order',
-    'gnx_tile2_route_begin', 'gnx_tile2_route_finish', 'gnx_tile2_requests_dev',
-    'gnx_tile2_set_requests',
-    'gnx_stream_ptr', 'gnx_tile2_move_route', 'gnx_tile2_route_ptrs', 'gnx_tile2_import',
-    'gnx_tile2_pairs', 'gnx_tile2_offspring', 'gnx_tile2_serve', 'gnx_tile2_put',
-    'gnx_tile2_finish_births', 'gnx_tile2_die', 'gnx_tile_pair_ptrs_nosync',
-    'gnx_tile_step_begin', 'gnx_tile_step_births', 'gnx_tile_step_end', 'gnx_comm_probe',
-    'gnx_tile2_pairs_mode', 'gnx_tile2_pairs_settle', 'gnx_tile2_settle_births',
-    'gnx_tile2_vt_counts', 'gnx_tile2_vt_bases', 'gnx_tile_step_abort', 'gnx_comm_info', 'gnx_tile_walk',
-    'gnx_geno_gram', 'gnx_geno_matmul', 'gnx_geno_rmatmul', 'gnx_transplant',
-    'gnx_geno_locus_gram', 'gnx_geno_locus_cross',
-    'gnx_lineage_trace', 'gnx_lineage_chains', 'gnx_lineage_budget', 'gnx_lineage_info',
-    'gnx_pedigree_reach', 'gnx_lineage_forget', 'gnx_dist_perm_sums',
-    'gnx_stats_group_counts', 'gnx_sgs_sums',
-    'gnx_ld_bins', 'gnx_ld_budget', 'gnx_ld_info',
-    'gnx_tracts_self', 'gnx_tracts_pairs', 'gnx_tracts_info',
-    'gnx_kin_matrix', 'gnx_kin_pairs', 'gnx_kin_info',
-    'gnx_dist_perm_sums_mat',
-    'gnx_cost_surfaces', 'gnx_cost_matrix', 'gnx_cost_budget', 'gnx_cost_info',
-    'gnx_admix_sweep', 'gnx_admix_info',
-    'gnx_sweeps_scan', 'gnx_sweeps_info',
-    'gnx_divmap_sums', 'gnx_divmap_info',
-    'gnx_circuit_matrix', 'gnx_circuit_current', 'gnx_circuit_potentials', 'gnx_circuit_budget',
-    'gnx_circuit_info',
-    'gnx_lai_paint',
-    'gnx_assoc_cross',
-    'gnx_coal_times', 'gnx_coal_segments',
-    'gnx_grm', 'gnx_grm_info', 'gnx_grm_probe',
-    'gnx_assoc_quad',
-]
-
 
 class Config(C.Structure):
     _fields_ = [('W', C.c_int32), ('H', C.c_int32), ('n_layers', C.c_int32),
@@ -115,11 +55,49 @@ IND_REC = np.dtype([('x', np.float32), ('y', np.float32), ('age', np.int32),
                     ('nbr_mask', np.int32)], align=True)
 assert IND_REC.itemsize == 32
 
+# -- the signatures, read from include/gnx_hip.h: the header is the one place that says them ----
+_SCALARS = {'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64,
+            'uint8_t': C.c_uint8, 'float': C.c_float, 'double': C.c_double}
+# every type the header uses, `const` dropped: scalars are exact, pointers to scalars are typed
+# (ctypes checks them), handles and records are opaque
+_CTYPES = {'void': None, 'int': C.c_int, 'char*': C.c_char_p,
+           'int32_t': C.c_int32, 'int64_t': C.c_int64, 'double': C.c_double,
+           'void*': C.c_void_p, 'gnx_state*': C.c_void_p, 'gnx_ind_rec*': C.c_void_p,
+           'void**': C.POINTER(C.c_void_p), 'gnx_state**': C.POINTER(C.c_void_p),
+           'gnx_config*': C.POINTER(Config), 'gnx_species_params*': C.POINTER(SpeciesParams)}
+_CTYPES.update((t + '*', C.POINTER(c)) for t, c in _SCALARS.items())
+_NP_PTR = {np.dtype(c): C.POINTER(c) for c in _SCALARS.values()}
+
+
+def parse_prototypes(text):
+    """{name: (restype, [argtypes])} of every `ret gnx_name(args);` in the header `text`;
+    a type outside _CTYPES raises, naming the prototype"""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    protos = {}
+    for ret, name, args in re.findall(r'^[ \t]*([\w \t*]+?)\b(gnx_\w+)\s*\(([^)]*)\)\s*;', text,
+                                      flags=re.M):
+        args = [] if args.strip() in ('', 'void') else args.split(',')
+        types = []
+        for k, decl in enumerate([ret + ' _'] + args):
+            m = re.fullmatch(r'\s*(\w+)\s*(\**)\s*\w*\s*', re.sub(r'\bconst\b', ' ', decl))
+            if not m or m.group(1) + m.group(2) not in _CTYPES:
+                raise TypeError('include/gnx_hip.h, %s: no ctypes type for "%s"'
+                                % (name, ' '.join(decl.split()) if k else ret.strip()))
+            types.append(_CTYPES[m.group(1) + m.group(2)])
+        protos[name] = (types[0], types[1:])
+    return protos
+
+
+with open(os.path.join(_HERE, '..', 'include', 'gnx_hip.h')) as _f:
+    PROTOTYPES = parse_prototypes(_f.read())
+EXPORTS = list(PROTOTYPES)
+
 _lib = None
 
 
 def load():
-    """Load libgnxhip.so; raises if it has not been built."""
+    """Load libgnxhip.so and declare every prototype of the header on it; raises if it has
+    not been built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -129,21 +107,28 @@ def load():
             '`python -m geonomics_amd.build` (hipcc, gfx950). There is no CPU '
             'fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    lib.gnx_last_error.restype = C.c_char_p
-    lib.gnx_step_index.restype = C.c_int64
-    lib.gnx_n_slots.restype = C.c_int64
-    lib.gnx_last_crossover_births.restype = C.c_int64
-    lib.gnx_walk_history.restype = C.c_int64
-    lib.gnx_comm_bytes_sent.restype = C.c_int64
-    lib.gnx_destroy.restype = None
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)       # (None: an older build behind GNX_LIB lacks it)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
 
-def _ptr(a, ctype):
+def _ptr(a):
+    """a numpy array as the typed pointer its dtype says (None: NULL)"""
     if a is None:
         return None
-    return a.ctypes.data_as(C.POINTER(ctype))
+    return a.ctypes.data_as(_NP_PTR[a.dtype])
+
+
+def _dev_ptr(t):
+    """a torch tensor's device address as the typed pointer its dtype says (None or an empty
+    tensor: NULL)"""
+    if t is None or not t.data_ptr():
+        return None
+    ctype = {'torch.float32': C.c_float, 'torch.float64': C.c_double}[str(t.dtype)]
+    return C.cast(t.data_ptr(), C.POINTER(ctype))
 
 
 def _arr(a, dtype):
@@ -209,16 +194,23 @@ class Device:
         if rc:
             raise GnxError(self.lib.gnx_last_error().decode())
 
+    def _outs(self, fn, names, *args):
+        """fn(h, *args, &out...) with one out scalar per name, of the types of fn's trailing
+        pointer parameters -> {name: value}, int or float"""
+        outs = [t._type_() for t in fn.argtypes[-len(names):]]
+        self._chk(fn(self.h, *args, *map(C.byref, outs)))
+        return {k: o.value for k, o in zip(names, outs)}
+
     # -- setup ---------------------------------------------------------------
     def upload_rasters(self, rasts):
         r = _arr(rasts, np.float32)
         assert r.shape == (self.n_layers, self.H, self.W), r.shape
-        self._chk(self.lib.gnx_upload_rasters(self.h, _ptr(r, C.c_float)))
+        self._chk(self.lib.gnx_upload_rasters(self.h, _ptr(r)))
 
     def upload_layer(self, layer, rast):
         r = _arr(rast, np.float32)
         assert r.shape == (self.H, self.W)
-        self._chk(self.lib.gnx_upload_layer(self.h, int(layer), _ptr(r, C.c_float)))
+        self._chk(self.lib.gnx_upload_layer(self.h, int(layer), _ptr(r)))
 
     def set_K_raster(self, K):
         """explicit K raster (float64 [H][W]) or None for rast[K_layer] * K_factor"""
@@ -227,7 +219,7 @@ class Device:
             return
         k = _arr(K, np.float64)
         assert k.shape == (self.H, self.W), k.shape
-        self._chk(self.lib.gnx_set_k_raster(self.h, _ptr(k, C.c_double)))
+        self._chk(self.lib.gnx_set_k_raster(self.h, _ptr(k)))
 
     @property
     def births_fixed_lambda(self):
@@ -249,22 +241,20 @@ class Device:
         ids = _arr(ids, np.int64)
         assert y.size == n and age.size == n and sex.size == n and ids.size == n
         self._chk(self.lib.gnx_upload_population(
-            self.h, C.c_int64(n), _ptr(x, C.c_float), _ptr(y, C.c_float),
-            _ptr(age, C.c_int32), _ptr(sex, C.c_uint8), _ptr(ids, C.c_int64)))
+            self.h, n, _ptr(x), _ptr(y), _ptr(age), _ptr(sex), _ptr(ids)))
 
     def set_positions(self, x, y):
         x, y = _arr(x, np.float32), _arr(y, np.float32)
         assert x.size == self.N and y.size == self.N
-        self._chk(self.lib.gnx_set_positions(self.h, _ptr(x, C.c_float), _ptr(y, C.c_float)))
+        self._chk(self.lib.gnx_set_positions(self.h, _ptr(x), _ptr(y)))
 
     def init_population(self, n):
-        self._chk(self.lib.gnx_init_population(self.h, C.c_int64(n)))
+        self._chk(self.lib.gnx_init_population(self.h, n))
 
     def set_recomb_paths(self, paths_packed):
         p = _arr(paths_packed, np.uint64)
         assert p.ndim == 2 and p.shape[1] == self.W64, (p.shape, self.W64)
-        self._chk(self.lib.gnx_set_recomb_paths(self.h, p.shape[0],
-                                                _ptr(p, C.c_uint64)))
+        self._chk(self.lib.gnx_set_recomb_paths(self.h, p.shape[0], _ptr(p)))
 
     def set_trait(self, t, loci, alpha, layer, phi, gamma, univ_adv):
         loci = _arr(loci, np.int32)
@@ -278,31 +268,27 @@ class Device:
         else:
             phi_s = float(phi)
         self._chk(self.lib.gnx_set_trait(
-            self.h, int(t), int(loci.size), _ptr(loci, C.c_int32),
-            _ptr(alpha, C.c_double), int(layer), C.c_double(phi_s),
-            _ptr(phi_rast, C.c_float), C.c_double(float(gamma)),
-            int(bool(univ_adv))))
+            self.h, int(t), int(loci.size), _ptr(loci), _ptr(alpha), int(layer), phi_s,
+            _ptr(phi_rast), float(gamma), int(bool(univ_adv))))
 
     def set_dominance(self, dom):
         d = None if dom is None else _arr(dom, np.uint8)
-        self._chk(self.lib.gnx_set_dominance(self.h, _ptr(d, C.c_uint8)))
+        self._chk(self.lib.gnx_set_dominance(self.h, _ptr(d)))
 
     def set_deleterious(self, loci, s):
         loci = _arr(loci, np.int32)
         s = _arr(s, np.float64)
-        self._chk(self.lib.gnx_set_deleterious(self.h, int(loci.size),
-                                               _ptr(loci, C.c_int32),
-                                               _ptr(s, C.c_double)))
+        self._chk(self.lib.gnx_set_deleterious(self.h, int(loci.size), _ptr(loci), _ptr(s)))
 
     def upload_genomes(self, geno):
         g = _arr(geno, np.uint64)
         assert g.shape == (self.N, 2, self.W64), (g.shape, self.N, self.W64)
-        self._chk(self.lib.gnx_upload_genomes(self.h, _ptr(g, C.c_uint64)))
+        self._chk(self.lib.gnx_upload_genomes(self.h, _ptr(g)))
 
     def assign_genomes(self, n_per_site):
         n = _arr(n_per_site, np.int32)
         assert n.size == self.L
-        self._chk(self.lib.gnx_assign_genomes(self.h, _ptr(n, C.c_int32)))
+        self._chk(self.lib.gnx_assign_genomes(self.h, _ptr(n)))
 
     def set_z(self):
         self._chk(self.lib.gnx_set_z(self.h))
@@ -326,7 +312,7 @@ class Device:
                                                 int(bool(with_selection))))
 
     def set_z_range(self, first, n):
-        self._chk(self.lib.gnx_set_z_range(self.h, C.c_int64(first), C.c_int64(n)))
+        self._chk(self.lib.gnx_set_z_range(self.h, first, n))
 
     def step(self, burn, with_selection):
         self._chk(self.lib.gnx_step(self.h, int(bool(burn)),
@@ -335,16 +321,14 @@ class Device:
     def walk(self, T, burn, with_selection):
         """T time steps in one call, counts kept on the device (gnx_walk): no read-back and
         one graph launch per step"""
-        self._chk(self.lib.gnx_walk(self.h, C.c_int64(int(T)), int(bool(burn)),
-                                    int(bool(with_selection))))
+        self._chk(self.lib.gnx_walk(self.h, int(T), int(bool(burn)), int(bool(with_selection))))
 
     def walk_history(self, max_steps=1 << 16):
         """(N at the start, births, deaths) of the last walk's steps, int64 arrays"""
         n = np.zeros(max_steps, np.int64)
         b = np.zeros(max_steps, np.int64)
         d = np.zeros(max_steps, np.int64)
-        k = self.lib.gnx_walk_history(self.h, C.c_int64(max_steps), _ptr(n, C.c_int64),
-                                      _ptr(b, C.c_int64), _ptr(d, C.c_int64))
+        k = self.lib.gnx_walk_history(self.h, max_steps, _ptr(n), _ptr(b), _ptr(d))
         return n[:k], b[:k], d[:k]
 
     # -- one tiled step per call, exchanges issued by the library (csrc/gnx_comm.hip) -------
@@ -382,7 +366,7 @@ class Device:
         """what the handle's tile communicator says about itself (gnx_comm_info): transport, rank,
         world, ncclCommCount / UserRank / CuDevice, device ordinal, steps, per-phase host ms per step"""
         out = np.zeros(16, np.int64)
-        self._chk(self.lib.gnx_comm_info(self.h, _ptr(out, C.c_int64)))
+        self._chk(self.lib.gnx_comm_info(self.h, _ptr(out)))
         steps = max(int(out[7]), 1)
         names = ('route_and_count_exchange', 'migrant_ghost_exchange_import',
                  'sort_pairs_second_count_exchange', 'births_gamete_service',
@@ -403,7 +387,7 @@ class Device:
         landscape (gnx_tile_step) -> (N, births, deaths), see include/gnx_hip.h"""
         out = np.zeros(3, np.int64)
         self._chk(self.lib.gnx_tile_step(self.h, int(bool(burn)), int(bool(with_selection)),
-                                         int(bool(exact)), _ptr(out, C.c_int64)))
+                                         int(bool(exact)), _ptr(out)))
         self._id_order = 1          # (the library numbers a tiled step's offspring tile-major)
         return int(out[0]), int(out[1]), int(out[2])
 
@@ -412,9 +396,8 @@ class Device:
         deaths) of the last step as tile_step reports them, sum of the global N at the start of
         every step, sum of the global births)"""
         out = np.zeros(5, np.int64)
-        self._chk(self.lib.gnx_tile_walk(self.h, C.c_int64(int(T)), int(bool(burn)),
-                                         int(bool(with_selection)), int(bool(exact)),
-                                         _ptr(out, C.c_int64)))
+        self._chk(self.lib.gnx_tile_walk(self.h, int(T), int(bool(burn)), int(bool(with_selection)),
+                                         int(bool(exact)), _ptr(out)))
         self._id_order = 1
         return (int(out[0]), int(out[1]), int(out[2])), int(out[3]), int(out[4])
 
@@ -424,26 +407,24 @@ class Device:
         (mutations, pedigree rows) goes between this and tile_step_end"""
         self._chk(self.lib.gnx_tile_step_begin(self.h, int(bool(burn))))
         self._id_order = 1
-        a, b = C.c_int64(), C.c_int64()
-        self._chk(self.lib.gnx_tile_step_births(self.h, C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return tuple(self._outs(self.lib.gnx_tile_step_births, ('first_id', 'total')).values())
 
     def tile_step_end(self, burn, with_selection, exact=True):
         out = np.zeros(3, np.int64)
         self._chk(self.lib.gnx_tile_step_end(self.h, int(bool(burn)), int(bool(with_selection)),
-                                             int(bool(exact)), _ptr(out, C.c_int64)))
+                                             int(bool(exact)), _ptr(out)))
         return int(out[0]), int(out[1]), int(out[2])
 
     def tile2_vt_counts(self):
         """tile-major offspring ids: this tile's births per virtual tile, int64 [64]"""
         cnt = np.zeros(64, np.int64)
-        self._chk(self.lib.gnx_tile2_vt_counts(self.h, _ptr(cnt, C.c_int64)))
+        self._chk(self.lib.gnx_tile2_vt_counts(self.h, _ptr(cnt)))
         return cnt
 
     def tile2_vt_bases(self, bases):
         b = _arr(bases, np.int64)
         assert b.size == 64
-        self._chk(self.lib.gnx_tile2_vt_bases(self.h, _ptr(b, C.c_int64)))
+        self._chk(self.lib.gnx_tile2_vt_bases(self.h, _ptr(b)))
 
     def step_begin(self, burn):
         self._chk(self.lib.gnx_step_begin(self.h, int(bool(burn))))
@@ -455,15 +436,13 @@ class Device:
         self._chk(self.lib.gnx_step_end(self.h, int(bool(burn))))
 
     def counts(self):
-        n, b, d = C.c_int64(), C.c_int64(), C.c_int64()
-        self._chk(self.lib.gnx_counts(self.h, C.byref(n), C.byref(b), C.byref(d)))
-        return n.value, b.value, d.value
+        return tuple(self._outs(self.lib.gnx_counts, ('N', 'births', 'deaths')).values())
 
     def totals(self):
         """dict(steps, ind_steps, births, deaths, xo_births, dd_steps) summed over the gnx_step calls
         since reset_totals() - host-side bookkeeping of the library, no device access"""
         out = np.zeros(6, np.int64)
-        self._chk(self.lib.gnx_totals(self.h, _ptr(out, C.c_int64)))
+        self._chk(self.lib.gnx_totals(self.h, _ptr(out)))
         return dict(zip(('steps', 'ind_steps', 'births', 'deaths', 'xo_births', 'dd_steps'),
                         (int(v) for v in out)))
 
@@ -478,7 +457,7 @@ class Device:
         """dict of how often the host-driven steps took each path since the handle was made or
         reset_path_counts() (gnx_path_counts) - host-side bookkeeping, no device access"""
         out = np.zeros(len(self.PATH_COUNTS), np.int64)
-        n = self.lib.gnx_path_counts(self.h, _ptr(out, C.c_int64), len(out))
+        n = self.lib.gnx_path_counts(self.h, _ptr(out), len(out))
         assert n == len(out), 'gnx_path_counts: the library has %d counters' % n
         return dict(zip(self.PATH_COUNTS, (int(v) for v in out)))
 
@@ -495,7 +474,7 @@ class Device:
 
     @step_index.setter
     def step_index(self, v):
-        self._chk(self.lib.gnx_set_step_index(self.h, C.c_int64(int(v))))
+        self._chk(self.lib.gnx_set_step_index(self.h, int(v)))
 
     def synchronize(self):
         self._chk(self.lib.gnx_synchronize(self.h))
@@ -514,14 +493,14 @@ class Device:
         """(logical blocks in use / 2, broken references, collections so far, physical blocks
         in use, free blocks, blocks in all) of the shared genome blocks, after a collection"""
         out = np.zeros(6, np.int64)
-        self._chk(self.lib.gnx_debug_halves(self.h, _ptr(out, C.c_int64)))
+        self._chk(self.lib.gnx_debug_halves(self.h, _ptr(out)))
         return out
 
     def genome_info(self):
         """host-side view of the genome blocks, no device access: dict(NB, BW, gc_runs,
         row_spread, sparse, free_blocks_est, free_rows, deferred)"""
         out = np.zeros(8, np.int64)
-        self._chk(self.lib.gnx_genome_info(self.h, _ptr(out, C.c_int64)))
+        self._chk(self.lib.gnx_genome_info(self.h, _ptr(out)))
         return dict(zip(('NB', 'BW', 'gc_runs', 'row_spread', 'sparse', 'free_blocks_est',
                          'free_rows', 'deferred'), (int(v) for v in out)))
 
@@ -537,8 +516,7 @@ class Device:
         self._chk(self.lib.gnx_last_crossover_jobs(self.h, None, 0, C.byref(n)))
         out = np.zeros((n.value, 4), np.int32)
         if n.value:
-            self._chk(self.lib.gnx_last_crossover_jobs(self.h, _ptr(out, C.c_int32), n.value,
-                                                       C.byref(n)))
+            self._chk(self.lib.gnx_last_crossover_jobs(self.h, _ptr(out), n.value, C.byref(n)))
         return out
 
     @property
@@ -546,16 +524,13 @@ class Device:
         return self.lib.gnx_last_crossover_births(self.h)
 
     def set_stream(self, stream_ptr):
-        self._chk(self.lib.gnx_set_stream(self.h, C.c_void_p(stream_ptr)))
+        self._chk(self.lib.gnx_set_stream(self.h, stream_ptr))
 
     def mutate(self, slots, loci, homs):
         slots = _arr(slots, np.int64)
         loci = _arr(loci, np.int32)
         homs = _arr(homs, np.uint8)
-        self._chk(self.lib.gnx_mutate(self.h, int(slots.size),
-                                      _ptr(slots, C.c_int64),
-                                      _ptr(loci, C.c_int32),
-                                      _ptr(homs, C.c_uint8)))
+        self._chk(self.lib.gnx_mutate(self.h, int(slots.size), _ptr(slots), _ptr(loci), _ptr(homs)))
 
     # -- read-back -----------------------------------------------------------
     _FIELD_DT = {F_X: np.float32, F_Y: np.float32, F_AGE: np.int32,
@@ -573,48 +548,40 @@ class Device:
         else:
             out = np.empty(n, dtype=self._FIELD_DT[field])
         if out.size:
-            self._chk(self.lib.gnx_download(self.h, field,
-                                            out.ctypes.data_as(C.c_void_p),
-                                            C.c_int64(out.nbytes)))
+            self._chk(self.lib.gnx_download(self.h, field, out.ctypes.data_as(C.c_void_p),
+                                            out.nbytes))
         return out
 
     def download_genomes(self, slots):
         slots = _arr(slots, np.int64)
         out = np.empty((slots.size, 2, self.W64), dtype=np.uint64)
         if slots.size:
-            self._chk(self.lib.gnx_download_genomes(
-                self.h, C.c_int64(slots.size), _ptr(slots, C.c_int64),
-                _ptr(out, C.c_uint64)))
+            self._chk(self.lib.gnx_download_genomes(self.h, slots.size, _ptr(slots), _ptr(out)))
         return out
 
     def download_raster(self, which):
         out = np.empty((self.H, self.W), dtype=np.float64)
-        self._chk(self.lib.gnx_download_raster(self.h, which, _ptr(out, C.c_double)))
+        self._chk(self.lib.gnx_download_raster(self.h, which, _ptr(out)))
         return out
 
     def spatial_diff_stats(self):
-        m, s = C.c_double(), C.c_double()
-        self._chk(self.lib.gnx_spatial_diff_stats(self.h, C.byref(m), C.byref(s)))
-        return m.value, s.value
+        return tuple(self._outs(self.lib.gnx_spatial_diff_stats, ('mean', 'std')).values())
 
     def spatial_diff_sums(self):
-        a, b = C.c_double(), C.c_double()
-        self._chk(self.lib.gnx_spatial_diff_sums(self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return tuple(self._outs(self.lib.gnx_spatial_diff_sums, ('sum', 'sum_sq')).values())
 
     # -- operator-level (tests) ----------------------------------------------
     def op_move(self, theta, dist):
         t = _arr(theta, np.float32)
         d = _arr(dist, np.float32)
         assert t.size == self.N and d.size == self.N
-        self._chk(self.lib.gnx_op_move(self.h, _ptr(t, C.c_float), _ptr(d, C.c_float)))
+        self._chk(self.lib.gnx_op_move(self.h, _ptr(t), _ptr(d)))
 
     def op_move_draws(self):
         n = self.N
         t = np.empty(n, np.float32)
         d = np.empty(n, np.float32)
-        self._chk(self.lib.gnx_op_move_draws(self.h, _ptr(t, C.c_float),
-                                             _ptr(d, C.c_float)))
+        self._chk(self.lib.gnx_op_move_draws(self.h, _ptr(t), _ptr(d)))
         return t, d
 
     def op_find_pairs(self, keep=None):
@@ -623,9 +590,7 @@ class Device:
         mate = np.empty(n, np.int32)
         pairs = np.empty((max(n, 1), 2), np.int32)
         npairs = C.c_int64()
-        self._chk(self.lib.gnx_op_find_pairs(self.h, _ptr(k, C.c_uint8),
-                                             _ptr(mate, C.c_int32),
-                                             _ptr(pairs, C.c_int32),
+        self._chk(self.lib.gnx_op_find_pairs(self.h, _ptr(k), _ptr(mate), _ptr(pairs),
                                              C.byref(npairs)))
         return mate, pairs[:npairs.value].copy()
 
@@ -635,10 +600,7 @@ class Device:
         s = _arr(start_homs, np.uint8)
         B = p.shape[0]
         assert p.shape == (B, 2) and k.shape == (B, 2) and s.shape == (B, 2)
-        self._chk(self.lib.gnx_op_crossover(self.h, C.c_int64(B),
-                                            _ptr(p, C.c_int32),
-                                            _ptr(k, C.c_int32),
-                                            _ptr(s, C.c_uint8)))
+        self._chk(self.lib.gnx_op_crossover(self.h, B, _ptr(p), _ptr(k), _ptr(s)))
 
     def op_dispersal(self, mid_x, mid_y, theta, dist):
         mx = _arr(mid_x, np.float32)
@@ -650,21 +612,16 @@ class Device:
         oy = np.empty(B, np.float32)
         used = np.empty(B, np.int32)
         self._chk(self.lib.gnx_op_dispersal(
-            self.h, C.c_int64(B), int(A), _ptr(mx, C.c_float),
-            _ptr(my, C.c_float), _ptr(th, C.c_float), _ptr(ds, C.c_float),
-            _ptr(ox, C.c_float), _ptr(oy, C.c_float), _ptr(used, C.c_int32)))
+            self.h, B, int(A), _ptr(mx), _ptr(my), _ptr(th), _ptr(ds), _ptr(ox), _ptr(oy),
+            _ptr(used)))
         return ox, oy, used
 
     def lattice_dims(self):
-        jx, jy = C.c_int32(), C.c_int32()
-        self._chk(self.lib.gnx_density_lattice_dims(self.h, C.byref(jx), C.byref(jy)))
-        return jx.value, jy.value
+        return tuple(self._outs(self.lib.gnx_density_lattice_dims, ('Jx', 'Jy')).values())
 
     def density_nmax(self):
         """N.max() of the last death probabilities' density raster (ops/demography.py:116)"""
-        v = C.c_double()
-        self._chk(self.lib.gnx_density_nmax(self.h, C.byref(v)))
-        return v.value
+        return self._outs(self.lib.gnx_density_nmax, ('nmax',))['nmax']
 
     def op_density(self, x, y, want_raster=True):
         x = _arr(x, np.float32)
@@ -672,10 +629,8 @@ class Device:
         jx, jy = self.lattice_dims()
         nodes = np.empty((jy, jx), np.float64)
         rast = np.empty((self.H, self.W), np.float64) if want_raster else None
-        self._chk(self.lib.gnx_op_density(self.h, C.c_int64(x.size),
-                                          _ptr(x, C.c_float), _ptr(y, C.c_float),
-                                          _ptr(nodes, C.c_double),
-                                          _ptr(rast, C.c_double)))
+        self._chk(self.lib.gnx_op_density(self.h, x.size, _ptr(x), _ptr(y), _ptr(nodes),
+                                          _ptr(rast)))
         return nodes, rast
 
     def op_death_probs(self, with_selection, nodes_N, nodes_pairs=None):
@@ -684,17 +639,14 @@ class Device:
         n = self.N
         p = np.empty(n, np.float64)
         d = np.empty(n, np.float64)
-        self._chk(self.lib.gnx_op_death_probs(self.h, int(bool(with_selection)),
-                                              _ptr(nN, C.c_double),
-                                              _ptr(nP, C.c_double),
-                                              _ptr(p, C.c_double),
-                                              _ptr(d, C.c_double)))
+        self._chk(self.lib.gnx_op_death_probs(self.h, int(bool(with_selection)), _ptr(nN), _ptr(nP),
+                                              _ptr(p), _ptr(d)))
         return p, d
 
     def op_mortality(self, dead):
         d = _arr(dead, np.uint8)
         assert d.size == self.N
-        self._chk(self.lib.gnx_op_mortality(self.h, _ptr(d, C.c_uint8)))
+        self._chk(self.lib.gnx_op_mortality(self.h, _ptr(d)))
 
     # -- spatial tiling (geonomics_amd/parallel.py) ---------------------------------
     def tile_set(self, R, C, r, c):
@@ -707,65 +659,59 @@ class Device:
         geno = np.zeros((n, 2, self.W64), np.uint64) if with_geno else None
         if n:
             self._chk(self.lib.gnx_tile_get_staged(
-                self.h, rec.ctypes.data_as(C.c_void_p), _ptr(z, C.c_float),
-                _ptr(geno, C.c_uint64)))
+                self.h, rec.ctypes.data_as(C.c_void_p), _ptr(z), _ptr(geno)))
         return rec, z, geno
 
     def tile_export_migrants(self, with_geno):
-        n = C.c_int64()
-        self._chk(self.lib.gnx_tile_export_migrants(self.h, C.byref(n)))
-        return self._get_staged(n.value, True, with_geno and self.L > 0)
+        n = self._outs(self.lib.gnx_tile_export_migrants, ('n',))['n']
+        return self._get_staged(n, True, with_geno and self.L > 0)
 
     def tile_export_halo(self):
-        n = C.c_int64()
-        self._chk(self.lib.gnx_tile_export_halo(self.h, C.byref(n)))
-        return self._get_staged(n.value, False, False)[0]
+        n = self._outs(self.lib.gnx_tile_export_halo, ('n',))['n']
+        return self._get_staged(n, False, False)[0]
 
     def tile_import(self, rec, z=None, geno=None):
         rec = np.ascontiguousarray(rec, dtype=IND_REC)
         z = None if z is None else _arr(z, np.float32)
         geno = None if geno is None else _arr(geno, np.uint64)
-        self._chk(self.lib.gnx_tile_import(self.h, C.c_int64(rec.size),
-                                           rec.ctypes.data_as(C.c_void_p),
-                                           _ptr(z, C.c_float), _ptr(geno, C.c_uint64)))
+        self._chk(self.lib.gnx_tile_import(self.h, rec.size, rec.ctypes.data_as(C.c_void_p),
+                                           _ptr(z), _ptr(geno)))
 
     def tile_import_ghosts(self, rec):
         rec = np.ascontiguousarray(rec, dtype=IND_REC)
-        self._chk(self.lib.gnx_tile_import_ghosts(self.h, C.c_int64(rec.size),
-                                                  rec.ctypes.data_as(C.c_void_p)))
+        self._chk(self.lib.gnx_tile_import_ghosts(self.h, rec.size, rec.ctypes.data_as(C.c_void_p)))
 
     def tile_pairs(self, burn):
-        p, b = C.c_int64(), C.c_int64()
-        self._chk(self.lib.gnx_tile_pairs(self.h, int(bool(burn)), C.byref(p), C.byref(b)))
-        self._n_pairs = p.value
-        return p.value, b.value
+        p, b = self._outs(self.lib.gnx_tile_pairs, ('n_pairs', 'n_births'),
+                          int(bool(burn))).values()
+        self._n_pairs = p
+        return p, b
 
     def tile_pair_info(self):
         P = self._n_pairs
         ids = np.zeros(P, np.int64)
         nb = np.zeros(P, np.int32)
         if P:
-            self._chk(self.lib.gnx_tile_pair_info(self.h, _ptr(ids, C.c_int64),
-                                                  _ptr(nb, C.c_int32)))
+            self._chk(self.lib.gnx_tile_pair_info(self.h, _ptr(ids), _ptr(nb)))
         return ids, nb
 
     def get_bins(self, which):
         out = np.zeros(self.lib.gnx_density_bin_count(self.h), np.int32)
-        self._chk(self.lib.gnx_get_bins(self.h, int(which), _ptr(out, C.c_int32)))
+        self._chk(self.lib.gnx_get_bins(self.h, int(which), _ptr(out)))
         return out
 
     def set_bins(self, which, bins):
         b = _arr(bins, np.int32)
         assert b.size == self.lib.gnx_density_bin_count(self.h)
-        self._chk(self.lib.gnx_set_bins(self.h, int(which), _ptr(b, C.c_int32)))
+        self._chk(self.lib.gnx_set_bins(self.h, int(which), _ptr(b)))
 
     def tile_offspring(self, burn, id_base, pair_goff):
         """pair_goff None: tile-major offspring ids (tile2_vt_counts / tile2_vt_bases came first)"""
         g = None if pair_goff is None else _arr(pair_goff, np.int64)
         assert g is None or g.size == self._n_pairs
         n = C.c_int64()
-        self._chk(self.lib.gnx_tile_offspring(self.h, int(bool(burn)), C.c_int64(int(id_base)),
-                                              _ptr(g, C.c_int64), C.byref(n)))
+        self._chk(self.lib.gnx_tile_offspring(self.h, int(bool(burn)), int(id_base), _ptr(g),
+                                              C.byref(n)))
         self._n_req = n.value
         return n.value
 
@@ -779,8 +725,7 @@ class Device:
         py = np.zeros(n, np.float32)
         if n:
             self._chk(self.lib.gnx_tile_get_requests(
-                self.h, _ptr(pid, C.c_int64), _ptr(ck, C.c_int32), _ptr(key, C.c_int32),
-                _ptr(st, C.c_uint8), _ptr(px, C.c_float), _ptr(py, C.c_float)))
+                self.h, _ptr(pid), _ptr(ck), _ptr(key), _ptr(st), _ptr(px), _ptr(py)))
         return pid, ck, key, st, px, py
 
     def tile_serve_gametes(self, pids, keys, starts):
@@ -790,8 +735,7 @@ class Device:
         out = np.zeros((pids.size, self.W64), np.uint64)
         if pids.size:
             self._chk(self.lib.gnx_tile_serve_gametes(
-                self.h, C.c_int64(pids.size), _ptr(pids, C.c_int64), _ptr(keys, C.c_int32),
-                _ptr(starts, C.c_uint8), _ptr(out, C.c_uint64)))
+                self.h, pids.size, _ptr(pids), _ptr(keys), _ptr(starts), _ptr(out)))
         return out
 
     def tile_put_gametes(self, child_k, data):
@@ -799,8 +743,7 @@ class Device:
         d = _arr(data, np.uint64)
         if ck.size:
             assert d.shape == (ck.size, self.W64)
-            self._chk(self.lib.gnx_tile_put_gametes(self.h, C.c_int64(ck.size),
-                                                    _ptr(ck, C.c_int32), _ptr(d, C.c_uint64)))
+            self._chk(self.lib.gnx_tile_put_gametes(self.h, ck.size, _ptr(ck), _ptr(d)))
 
     def tile_finish_births(self, burn):
         self._chk(self.lib.gnx_tile_finish_births(self.h, int(bool(burn))))
@@ -810,7 +753,7 @@ class Device:
                                         int(bool(have_pairs))))
 
     def set_max_id(self, v):
-        self._chk(self.lib.gnx_set_max_id(self.h, C.c_int64(int(v))))
+        self._chk(self.lib.gnx_set_max_id(self.h, int(v)))
 
     # -- tile2: the device-driven protocol (include/gnx_hip.h); addresses are plain ints
     # (device memory) --------------------------------------------------------------------
@@ -830,7 +773,7 @@ class Device:
         """-> counts int64 [2][R*C]: migrants per rank, ghosts per rank (one host wait)"""
         T = max(getattr(self, '_n_tiles', 1), 1)
         cnt = np.zeros(2 * T, np.int64)
-        self._chk(self.lib.gnx_tile2_move_route(self.h, int(bool(move)), _ptr(cnt, C.c_int64)))
+        self._chk(self.lib.gnx_tile2_move_route(self.h, int(bool(move)), _ptr(cnt)))
         return cnt.reshape(2, T)
 
     def tile2_route_ptrs(self):
@@ -841,31 +784,30 @@ class Device:
 
     def tile2_import(self, n_mig, rec, z, geno, n_ghost, ghost_rec):
         self._chk(self.lib.gnx_tile2_import(
-            self.h, C.c_int64(int(n_mig)), C.c_void_p(rec or None), C.c_void_p(z or None),
-            C.c_void_p(geno or None), C.c_int64(int(n_ghost)), C.c_void_p(ghost_rec or None)))
+            self.h, int(n_mig), rec or None, z or None, geno or None, int(n_ghost),
+            ghost_rec or None))
 
     def tile2_pairs(self, burn):
         """-> P, births, gamete requests per owning rank int64 [R*C]"""
         T = max(getattr(self, '_n_tiles', 1), 1)
         cnt = np.zeros(2 + T, np.int64)
-        self._chk(self.lib.gnx_tile2_pairs(self.h, int(bool(burn)), _ptr(cnt, C.c_int64)))
+        self._chk(self.lib.gnx_tile2_pairs(self.h, int(bool(burn)), _ptr(cnt)))
         self._n_pairs = int(cnt[0])
         return int(cnt[0]), int(cnt[1]), cnt[2:]
 
     def tile2_offspring(self, burn, id_base, goff_ptr):
         a = C.c_void_p()
-        self._chk(self.lib.gnx_tile2_offspring(self.h, int(bool(burn)), C.c_int64(int(id_base)),
-                                               C.c_void_p(goff_ptr or None), C.byref(a)))
+        self._chk(self.lib.gnx_tile2_offspring(self.h, int(bool(burn)), int(id_base),
+                                               goff_ptr or None, C.byref(a)))
         return a.value or 0
 
     def tile2_serve(self, n, req_ptr):
         a = C.c_void_p()
-        self._chk(self.lib.gnx_tile2_serve(self.h, C.c_int64(int(n)), C.c_void_p(req_ptr or None),
-                                           C.byref(a)))
+        self._chk(self.lib.gnx_tile2_serve(self.h, int(n), req_ptr or None, C.byref(a)))
         return a.value or 0
 
     def tile2_put(self, n, data_ptr):
-        self._chk(self.lib.gnx_tile2_put(self.h, C.c_int64(int(n)), C.c_void_p(data_ptr or None)))
+        self._chk(self.lib.gnx_tile2_put(self.h, int(n), data_ptr or None))
 
     def tile2_finish_births(self, burn):
         a, n = C.c_void_p(), C.c_int64()
@@ -877,7 +819,7 @@ class Device:
         """-> the all-reduced (N before this step's deaths, births, deaths of the previous step)"""
         tot = np.zeros(3, np.int64)
         self._chk(self.lib.gnx_tile2_die(self.h, int(bool(burn)), int(bool(with_selection)),
-                                         int(bool(have_pairs)), _ptr(tot, C.c_int64)))
+                                         int(bool(have_pairs)), _ptr(tot)))
         return int(tot[0]), int(tot[1]), int(tot[2])
 
     def last_births(self, with_gametes=True):
@@ -891,17 +833,15 @@ class Device:
         xy = np.zeros((B, 2), np.float32)
         if B:
             self._chk(self.lib.gnx_last_births(
-                self.h, _ptr(child, C.c_int64), _ptr(par, C.c_int64),
-                _ptr(keys, C.c_int32) if with_gametes else None,
-                _ptr(starts, C.c_uint8) if with_gametes else None, _ptr(xy, C.c_float)))
+                self.h, _ptr(child), _ptr(par), _ptr(keys) if with_gametes else None,
+                _ptr(starts) if with_gametes else None, _ptr(xy)))
         return child, par, keys, starts, xy
 
     # -- statistics ------------------------------------------------------------------
     def stats_locus_counts(self):
         c1 = np.zeros(self.L, np.int32)
         ch = np.zeros(self.L, np.int32)
-        self._chk(self.lib.gnx_stats_locus_counts(self.h, _ptr(c1, C.c_int32),
-                                                  _ptr(ch, C.c_int32)))
+        self._chk(self.lib.gnx_stats_locus_counts(self.h, _ptr(c1), _ptr(ch)))
         return c1, ch
 
     def stats_group_counts(self, slots, group_start):
@@ -918,9 +858,8 @@ class Device:
         c1 = np.zeros(shape, np.int32)
         ch = np.zeros(shape, np.int32)
         self._chk(self.lib.gnx_stats_group_counts(
-            self.h, C.c_int64(int(s.size)), _ptr(s, C.c_int32), C.c_int32(max(G, -1)),
-            _ptr(gs if gs.size else np.zeros(1, np.int64), C.c_int64), _ptr(c1, C.c_int32),
-            _ptr(ch, C.c_int32)))
+            self.h, int(s.size), _ptr(s), max(G, -1),
+            _ptr(gs if gs.size else np.zeros(1, np.int64)), _ptr(c1), _ptr(ch)))
         return c1, ch
 
     # -- moving-window diversity sums (csrc/gnx_divmap.hip; sim/divmap.py) -----------------
@@ -945,32 +884,27 @@ class Device:
         out = dict(n=np.zeros(shape, np.int32), S=np.zeros(shape, np.int32),
                    sum_het=np.zeros(shape, np.int64), sum_cc=np.zeros(shape, np.int64))
         self._chk(self.lib.gnx_divmap_sums(
-            self.h, C.c_int64(int(s.size)), _ptr(s, C.c_int32), C.c_int32(nx), C.c_int32(ny),
-            _ptr(cs if cs.size else np.zeros(1, np.int64), C.c_int64), C.c_int32(r),
-            _ptr(m, C.c_uint64), C.c_int64(int(max_counts)), _ptr(out['n'], C.c_int32),
-            _ptr(out['S'], C.c_int32), _ptr(out['sum_het'], C.c_int64),
-            _ptr(out['sum_cc'], C.c_int64)))
+            self.h, int(s.size), _ptr(s), nx, ny, _ptr(cs if cs.size else np.zeros(1, np.int64)),
+            r, _ptr(m), int(max_counts), _ptr(out['n']), _ptr(out['S']), _ptr(out['sum_het']),
+            _ptr(out['sum_cc'])))
         return out
 
     def divmap_info(self):
         """locus tiles, chunks and kernel launches of the last divmap_sums"""
-        t, c, n = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._chk(self.lib.gnx_divmap_info(self.h, C.byref(t), C.byref(c), C.byref(n)))
-        return dict(tiles=int(t.value), chunks=int(c.value), launches=int(n.value))
+        return self._outs(self.lib.gnx_divmap_info, ('tiles', 'chunks', 'launches'))
 
     def stats_ld(self, loci):
         loci = _arr(loci, np.int32)
         out = np.zeros((loci.size, loci.size), np.float64)
-        self._chk(self.lib.gnx_stats_ld(self.h, int(loci.size), _ptr(loci, C.c_int32),
-                                        _ptr(out, C.c_double)))
+        self._chk(self.lib.gnx_stats_ld(self.h, int(loci.size), _ptr(loci), _ptr(out)))
         return out
 
     def stats_ld_counts(self, loci):
         loci = _arr(loci, np.int32)
         c = np.zeros(loci.size, np.int64)
         cc = np.zeros((loci.size, loci.size), np.int64)
-        self._chk(self.lib.gnx_stats_ld_counts(self.h, int(loci.size), _ptr(loci, C.c_int32),
-                                               _ptr(c, C.c_int64), _ptr(cc, C.c_int64)))
+        self._chk(self.lib.gnx_stats_ld_counts(self.h, int(loci.size), _ptr(loci), _ptr(c),
+                                               _ptr(cc)))
         return c, cc
 
     # -- genetic PCA and distances (csrc/gnx_geno.hip) ---------------------------------
@@ -995,8 +929,7 @@ class Device:
         m = self._locus_mask_words(locus_mask)
         # (the library refuses n outside 1..8192 before it writes: no n x n buffer for that)
         out = np.zeros((n, n) if 1 <= n <= 8192 else (0, 0), np.int64)
-        self._chk(self.lib.gnx_geno_gram(self.h, C.c_int64(n), _ptr(s, C.c_int64),
-                                         _ptr(m, C.c_uint64), _ptr(out, C.c_int64)))
+        self._chk(self.lib.gnx_geno_gram(self.h, n, _ptr(s), _ptr(m), _ptr(out)))
         return out
 
     def _val_table(self, val):
@@ -1015,8 +948,7 @@ class Device:
         v = self._val_table(val)
         # (the library refuses n outside 1..8192 before it writes: no n x n buffer for that)
         out = np.zeros((n, n) if 1 <= n <= 8192 else (0, 0), np.float64)
-        self._chk(self.lib.gnx_grm(self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64),
-                                   _ptr(v, C.c_float), _ptr(out, C.c_double)))
+        self._chk(self.lib.gnx_grm(self.h, n, _ptr(s), _ptr(m), _ptr(v), _ptr(out)))
         return out
 
     def grm_probe(self, mode):
@@ -1026,9 +958,7 @@ class Device:
 
     def grm_info(self):
         """of the last grm: dict(tiles, k_chunks, kernel_ms)"""
-        t, k, ms = C.c_int64(), C.c_int64(), C.c_double()
-        self._chk(self.lib.gnx_grm_info(self.h, C.byref(t), C.byref(k), C.byref(ms)))
-        return dict(tiles=int(t.value), k_chunks=int(k.value), kernel_ms=ms.value)
+        return self._outs(self.lib.gnx_grm_info, ('tiles', 'k_chunks', 'kernel_ms'))
 
     @staticmethod
     def _f32_dev(t, name):
@@ -1051,9 +981,8 @@ class Device:
         s, n = self._geno_slots(slots)
         Y = torch.empty((n, M.shape[1]), dtype=torch.float32, device=M.device)
         torch.cuda.current_stream(M.device).synchronize()
-        self._chk(self.lib.gnx_geno_matmul(self.h, int(M.shape[1]), C.c_void_p(M.data_ptr()),
-                                           C.c_void_p(Y.data_ptr() or None), C.c_int64(n),
-                                           _ptr(s, C.c_int64)))
+        self._chk(self.lib.gnx_geno_matmul(self.h, int(M.shape[1]), _dev_ptr(M), _dev_ptr(Y), n,
+                                           _ptr(s)))
         return Y
 
     def geno_rmatmul(self, Y, slots=None):
@@ -1065,10 +994,8 @@ class Device:
             raise ValueError('Y: %d rows, not n = %d' % (Y.shape[0], n))
         Z = torch.empty((self.L, Y.shape[1]), dtype=torch.float32, device=Y.device)
         torch.cuda.current_stream(Y.device).synchronize()
-        self._chk(self.lib.gnx_geno_rmatmul(self.h, int(Y.shape[1]),
-                                            C.c_void_p(Y.data_ptr() or None),
-                                            C.c_void_p(Z.data_ptr() or None), C.c_int64(n),
-                                            _ptr(s, C.c_int64)))
+        self._chk(self.lib.gnx_geno_rmatmul(self.h, int(Y.shape[1]), _dev_ptr(Y), _dev_ptr(Z), n,
+                                            _ptr(s)))
         return Z
 
     # -- genotype-environment association (csrc/gnx_gea.hip) ----------------------------
@@ -1081,9 +1008,8 @@ class Device:
         m = int(loci.size) if 1 <= loci.size <= 8192 else 0    # the library refuses the rest
         Cm = np.zeros((m, m), np.int64)
         cs = np.zeros(m, np.int64)
-        self._chk(self.lib.gnx_geno_locus_gram(self.h, int(loci.size), _ptr(loci, C.c_int32),
-                                               C.c_int64(n), _ptr(s, C.c_int64),
-                                               _ptr(Cm, C.c_int64), _ptr(cs, C.c_int64)))
+        self._chk(self.lib.gnx_geno_locus_gram(self.h, int(loci.size), _ptr(loci), n, _ptr(s),
+                                               _ptr(Cm), _ptr(cs)))
         return Cm, cs
 
     def geno_locus_cross(self, loci, lyr, slots=None):
@@ -1095,10 +1021,8 @@ class Device:
         DtZ = np.zeros((m, 3), np.float64)
         ZtZ = np.zeros((3, 3), np.float64)
         Zt1 = np.zeros(3, np.float64)
-        self._chk(self.lib.gnx_geno_locus_cross(self.h, int(loci.size), _ptr(loci, C.c_int32),
-                                                int(lyr), C.c_int64(n), _ptr(s, C.c_int64),
-                                                _ptr(DtZ, C.c_double), _ptr(ZtZ, C.c_double),
-                                                _ptr(Zt1, C.c_double)))
+        self._chk(self.lib.gnx_geno_locus_cross(self.h, int(loci.size), _ptr(loci), int(lyr), n,
+                                                _ptr(s), _ptr(DtZ), _ptr(ZtZ), _ptr(Zt1)))
         return DtZ, ZtZ, Zt1
 
     # -- Mantel tests and MMRR (csrc/gnx_mantel.hip) --------------------------------------
@@ -1137,15 +1061,14 @@ class Device:
             raise ValueError('perm: [n_perm][%d], not %s' % (n, perm.shape))
         sums = np.zeros((perm.shape[0], k), np.float64)
         mom = np.zeros(3 + 2 * k + k * (k + 1) // 2, np.float64)
-        head = (self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), len(predictors),
-                _ptr(off, C.c_int32), _ptr(cols if cols.size else None, C.c_int32))
-        tail = (int(perm.shape[0]), _ptr(perm, C.c_int32), _ptr(sums, C.c_double),
-                _ptr(mom, C.c_double))
+        head = (self.h, n, _ptr(s), _ptr(m), len(predictors), _ptr(off),
+                _ptr(cols if cols.size else None))
+        tail = (int(perm.shape[0]), _ptr(perm), _ptr(sums), _ptr(mom))
         if mats is None:
             self._chk(self.lib.gnx_dist_perm_sums(*head, *tail))
         else:
             self._chk(self.lib.gnx_dist_perm_sums_mat(
-                *head, int(mats.shape[0]), _ptr(mats if mats.size else None, C.c_double), *tail))
+                *head, int(mats.shape[0]), _ptr(mats if mats.size else None), *tail))
         sxx = np.zeros((k, k))
         sxx[np.triu_indices(k)] = mom[3 + 2 * k:]
         sxx = sxx + np.triu(sxx, 1).T
@@ -1167,9 +1090,8 @@ class Device:
         src = _arr(src, np.int32).ravel()
         out = np.zeros((src.size, self.cfg.H, self.cfg.W), np.float64)
         self._chk(self.lib.gnx_cost_surfaces(
-            self.h, _ptr(R, C.c_double), C.c_double(float(res[0])), C.c_double(float(res[1])),
-            C.c_int32(int(src.size)), _ptr(src if src.size else None, C.c_int32),
-            _ptr(out if out.size else None, C.c_double)))
+            self.h, _ptr(R), float(res[0]), float(res[1]), int(src.size),
+            _ptr(src if src.size else None), _ptr(out if out.size else None)))
         return out
 
     def cost_matrix(self, R, res, cells):
@@ -1180,32 +1102,26 @@ class Device:
         n = int(cells.size) if 1 <= cells.size <= 32768 else 0   # the library refuses the rest
         D = np.zeros((n, n), np.float64)
         self._chk(self.lib.gnx_cost_matrix(
-            self.h, _ptr(R, C.c_double), C.c_double(float(res[0])), C.c_double(float(res[1])),
-            C.c_int32(int(cells.size)), _ptr(cells if cells.size else None, C.c_int32),
-            _ptr(D if D.size else None, C.c_double)))
+            self.h, _ptr(R), float(res[0]), float(res[1]), int(cells.size),
+            _ptr(cells if cells.size else None), _ptr(D if D.size else None)))
         return D
 
     def cost_budget(self, n_bytes):
         """bytes of distance rasters one batch of sources may take (0: the default, 2 GiB)"""
-        self._chk(self.lib.gnx_cost_budget(self.h, C.c_int64(int(n_bytes))))
+        self._chk(self.lib.gnx_cost_budget(self.h, int(n_bytes)))
 
     def cost_info(self):
         """of the last cost_surfaces / cost_matrix: dict(kernel_ms, launches, rounds, batches)"""
-        ms, n, r, b = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64()
-        self._chk(self.lib.gnx_cost_info(self.h, C.byref(ms), C.byref(n), C.byref(r),
-                                         C.byref(b)))
-        return dict(kernel_ms=ms.value, launches=int(n.value), rounds=int(r.value),
-                    batches=int(b.value))
+        return self._outs(self.lib.gnx_cost_info, ('kernel_ms', 'launches', 'rounds', 'batches'))
 
     # -- circuit-theory resistances and current maps (csrc/gnx_circuit.hip) ----------------
     def _circuit_args(self, R, res, cells, tol, max_iter):
         R = self._cost_raster(R)
         cells = _arr(cells, np.int32).ravel()
         return R, cells, (
-            self.h, _ptr(R, C.c_double), C.c_double(float(res[0])), C.c_double(float(res[1])),
-            C.c_int32(int(cells.size)), _ptr(cells if cells.size else None, C.c_int32),
-            C.c_double(1e-10 if tol is None else float(tol)),
-            C.c_int64(0 if max_iter is None else int(max_iter)))
+            self.h, _ptr(R), float(res[0]), float(res[1]), int(cells.size),
+            _ptr(cells if cells.size else None), 1e-10 if tol is None else float(tol),
+            0 if max_iter is None else int(max_iter))
 
     def circuit_matrix(self, R, res, cells, tol=None, max_iter=None):
         """the pairwise effective resistances of distinct cells (y * W + x) over the resistance
@@ -1216,7 +1132,7 @@ class Device:
         R, cells, args = self._circuit_args(R, res, cells, tol, max_iter)
         n = int(cells.size) if 1 <= cells.size <= 8192 else 0     # the library refuses the rest
         D = np.zeros((n, n), np.float64)
-        self._chk(self.lib.gnx_circuit_matrix(*args, _ptr(D if D.size else None, C.c_double)))
+        self._chk(self.lib.gnx_circuit_matrix(*args, _ptr(D if D.size else None)))
         return D
 
     def circuit_current(self, R, res, cells, tol=None, max_iter=None):
@@ -1226,8 +1142,7 @@ class Device:
         R, cells, args = self._circuit_args(R, res, cells, tol, max_iter)
         out = np.zeros((self.cfg.H, self.cfg.W), np.float64)
         counts = np.zeros(2, np.int64)
-        self._chk(self.lib.gnx_circuit_current(*args, _ptr(out, C.c_double),
-                                               _ptr(counts, C.c_int64)))
+        self._chk(self.lib.gnx_circuit_current(*args, _ptr(out), _ptr(counts)))
         return out, int(counts[0]), int(counts[1])
 
     def circuit_potentials(self, R, res, cells, tol=None, max_iter=None):
@@ -1239,22 +1154,18 @@ class Device:
         out = np.zeros((n, self.cfg.H, self.cfg.W), np.float64)
         anchor = np.full(n, -1, np.int32)
         self._chk(self.lib.gnx_circuit_potentials(
-            *args, _ptr(anchor if n else None, C.c_int32),
-            _ptr(out if out.size else None, C.c_double)))
+            *args, _ptr(anchor if n else None), _ptr(out if out.size else None)))
         return out, anchor
 
     def circuit_budget(self, n_bytes):
         """bytes of solver rasters one batch of systems may take (0: the default, 4 GiB)"""
-        self._chk(self.lib.gnx_circuit_budget(self.h, C.c_int64(int(n_bytes))))
+        self._chk(self.lib.gnx_circuit_budget(self.h, int(n_bytes)))
 
     def circuit_info(self):
         """of the last circuit_matrix / circuit_current / circuit_potentials:
         dict(kernel_ms, launches, iterations, restarts, worst_residual)"""
-        ms, n, it, rs, w = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
-        self._chk(self.lib.gnx_circuit_info(self.h, C.byref(ms), C.byref(n), C.byref(it),
-                                            C.byref(rs), C.byref(w)))
-        return dict(kernel_ms=ms.value, launches=int(n.value), iterations=int(it.value),
-                    restarts=int(rs.value), worst_residual=w.value)
+        return self._outs(self.lib.gnx_circuit_info, ('kernel_ms', 'launches', 'iterations',
+                                                      'restarts', 'worst_residual'))
 
     # -- fine-scale spatial genetic structure (csrc/gnx_sgs.hip) ---------------------------
     def sgs_sums(self, edges, slots=None, locus_mask=None, locus_weight=None, perm=None,
@@ -1286,10 +1197,8 @@ class Device:
         work = np.zeros(1, np.int64)
         nz = np.zeros(1, np.int64)
         self._chk(self.lib.gnx_sgs_sums(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), C.c_int32(max(nb, -1)),
-            _ptr(e if e.size else np.zeros(1), C.c_double), _ptr(wt, C.c_double),
-            _ptr(p, C.c_int32), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
-            _ptr(isums, C.c_int64), _ptr(fsums, C.c_double), _ptr(nz, C.c_int64)))
+            self.h, n, _ptr(s), _ptr(m), max(nb, -1), _ptr(e if e.size else np.zeros(1)), _ptr(wt),
+            _ptr(p), int(max_work), _ptr(work), _ptr(isums), _ptr(fsums), _ptr(nz)))
         if max_work <= 0:
             return dict(work=int(work[0]), isums=None, fsums=None, n_zero=None)
         return dict(work=int(work[0]), isums=isums, fsums=fsums, n_zero=int(nz[0]))
@@ -1315,12 +1224,10 @@ class Device:
         fs = np.zeros((rows, 4), np.float64)
         work = np.zeros(1, np.int64)
         self._chk(self.lib.gnx_ld_bins(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), C.c_int32(int(loci.size)),
-            _ptr(loci if loci.size else np.zeros(1, np.int32), C.c_int32),
-            _ptr(pos if pos.size else np.zeros(1), C.c_double), C.c_int32(int(e.size)),
-            _ptr(e if e.size else np.zeros(1), C.c_double), C.c_int32(int(min_minor)),
-            C.c_int32(int(bool(morgans))), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
-            _ptr(c1, C.c_int64), _ptr(pairs, C.c_int64), _ptr(fs, C.c_double)))
+            self.h, n, _ptr(s), int(loci.size), _ptr(loci if loci.size else np.zeros(1, np.int32)),
+            _ptr(pos if pos.size else np.zeros(1)), int(e.size), _ptr(e if e.size else np.zeros(1)),
+            int(min_minor), int(bool(morgans)), int(max_work), _ptr(work), _ptr(c1), _ptr(pairs),
+            _ptr(fs)))
         if max_work <= 0:
             return dict(work=int(work[0]), c1=None, pairs=None, sum_r2=None, sum_r4=None,
                         sum_d=None, sum_w=None)
@@ -1329,13 +1236,11 @@ class Device:
 
     def ld_budget(self, n_bytes):
         """bytes of transposed bit rows ld_bins keeps resident (0: the default, 256 MiB)"""
-        self._chk(self.lib.gnx_ld_budget(self.h, C.c_int64(int(n_bytes))))
+        self._chk(self.lib.gnx_ld_budget(self.h, int(n_bytes)))
 
     def ld_info(self):
         """of the last ld_bins: dict(kernel_ms, launches, locus_blocks)"""
-        ms, n, nb = C.c_double(), C.c_int64(), C.c_int64()
-        self._chk(self.lib.gnx_ld_info(self.h, C.byref(ms), C.byref(n), C.byref(nb)))
-        return dict(kernel_ms=ms.value, launches=int(n.value), locus_blocks=int(nb.value))
+        return self._outs(self.lib.gnx_ld_info, ('kernel_ms', 'launches', 'locus_blocks'))
 
     # -- model-based ancestry (csrc/gnx_admix.hip) -------------------------------------------
     def admix_sweep(self, Q, F, slots=None, locus_mask=None, want_loglik=True, budget=None,
@@ -1370,23 +1275,15 @@ class Device:
         ll = C.c_double(0.0)
         torch.cuda.current_stream(Q.device).synchronize()
         self._chk(self.lib.gnx_admix_sweep(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64), C.c_int32(K),
-            C.c_void_p(Q.data_ptr() or None), C.c_void_p(F.data_ptr() or None),
-            C.c_void_p(A.data_ptr() or None),
-            C.c_void_p(B1.data_ptr() or None) if want_B else None,
-            C.c_void_p(B0.data_ptr() or None) if want_B else None,
-            C.byref(ll) if want_loglik else None, C.c_int32(0 if want_B else 1),
-            C.c_int64(int(budget or 0))))
+            self.h, n, _ptr(s), _ptr(m), K, _dev_ptr(Q), _dev_ptr(F), _dev_ptr(A), _dev_ptr(B1),
+            _dev_ptr(B0), C.byref(ll) if want_loglik else None, 0 if want_B else 1,
+            int(budget or 0)))
         return dict(A=A, B1=B1, B0=B0, loglik=float(ll.value) if want_loglik else None)
 
     def admix_info(self):
         """of the last admix_sweep: dict(kernel_ms, launches, chunks (over the individuals),
         instance (the K of the template instance that ran))"""
-        ms, n, nc, inst = C.c_double(), C.c_int64(), C.c_int64(), C.c_int32()
-        self._chk(self.lib.gnx_admix_info(self.h, C.byref(ms), C.byref(n), C.byref(nc),
-                                          C.byref(inst)))
-        return dict(kernel_ms=ms.value, launches=int(n.value), chunks=int(nc.value),
-                    instance=int(inst.value))
+        return self._outs(self.lib.gnx_admix_info, ('kernel_ms', 'launches', 'chunks', 'instance'))
 
     # -- local ancestry along the genome (csrc/gnx_lai.hip) ------------------------------------
     def lai_paint(self, F, sw, stay, Q, slots=None, loci=None, by=None, n_groups=0, budget=None,
@@ -1432,13 +1329,9 @@ class Device:
         calls = np.zeros((T, L_u), np.uint8) if post and wc else None
         nb, ms = C.c_int64(0), C.c_double(0.0)
         self._chk(self.lib.gnx_lai_paint(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), C.c_int32(K), C.c_int32(L_u),
-            _ptr(lo, C.c_int32), _ptr(F, C.c_double), _ptr(sw, C.c_double),
-            _ptr(stay, C.c_double), _ptr(Q, C.c_double), _ptr(b, C.c_int32),
-            C.c_int32(int(n_groups)), C.c_int64(int(budget or 0)), C.c_int32(int(post)),
-            C.c_int32(int(wc)), _ptr(ll, C.c_double), _ptr(ah, C.c_double),
-            _ptr(al, C.c_double), _ptr(sn, C.c_int32), _ptr(calls, C.c_uint8), C.byref(nb),
-            C.byref(ms)))
+            self.h, n, _ptr(s), K, L_u, _ptr(lo), _ptr(F), _ptr(sw), _ptr(stay), _ptr(Q), _ptr(b),
+            int(n_groups), int(budget or 0), int(post), int(wc), _ptr(ll), _ptr(ah), _ptr(al),
+            _ptr(sn), _ptr(calls), C.byref(nb), C.byref(ms)))
         return dict(loglik=ll[:T], anc_hap=ah, anc_locus=al,
                     switches=None if sn is None else sn[:T], calls=calls,
                     batches=int(nb.value), kernel_ms=ms.value)
@@ -1463,8 +1356,7 @@ class Device:
         s1, s2 = np.zeros(self.L, np.int64), np.zeros(self.L, np.int64)
         per, cnt, ms = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
         self._chk(self.lib.gnx_assoc_cross(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), C.c_int32(m), _ptr(Y, C.c_double),
-            _ptr(out, C.c_double), _ptr(s1, C.c_int64), _ptr(s2, C.c_int64), C.byref(per),
+            self.h, n, _ptr(s), m, _ptr(Y), _ptr(out), _ptr(s1), _ptr(s2), C.byref(per),
             C.byref(cnt), C.byref(ms)))
         return dict(DtY=out, s1=s1, s2=s2, stretch=int(per.value), stretches=int(cnt.value),
                     kernel_ms=ms.value)
@@ -1483,8 +1375,8 @@ class Device:
         out = np.zeros(self.L, np.float64)
         ms = C.c_double(0.0)
         self._chk(self.lib.gnx_assoc_quad(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(mk, C.c_uint64), _ptr(v, C.c_float),
-            C.c_int32(int(M.shape[0])), _ptr(M, C.c_float), _ptr(out, C.c_double), C.byref(ms)))
+            self.h, n, _ptr(s), _ptr(mk), _ptr(v), int(M.shape[0]), _ptr(M), _ptr(out),
+            C.byref(ms)))
         return dict(q=out, kernel_ms=ms.value)
 
     # -- identity tracts of the phased genomes (csrc/gnx_tracts.hip) ------------------------
@@ -1520,10 +1412,8 @@ class Device:
         per = np.zeros((n if 1 <= n <= 2 ** 25 else 1, 4), np.int64)
         cov = np.zeros(self.L, np.int64) if cover else None
         self._chk(self.lib.gnx_tracts_self(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(pos, C.c_int64), _ptr(b, C.c_uint64),
-            C.c_int32(int(min_loci)), C.c_int64(int(min_len)),
-            C.c_int32(0 if edges is None else int(np.size(edges))), _ptr(e, C.c_int64),
-            _ptr(per, C.c_int64), _ptr(hist, C.c_int64), _ptr(cov, C.c_int64)))
+            self.h, n, _ptr(s), _ptr(pos), _ptr(b), int(min_loci), int(min_len),
+            0 if edges is None else int(np.size(edges)), _ptr(e), _ptr(per), _ptr(hist), _ptr(cov)))
         return dict(per=per, hist=hist, cover=cov)
 
     def tracts_pairs(self, pos, brk=None, min_loci=1, min_len=0, edges=None, slots=None,
@@ -1543,12 +1433,9 @@ class Device:
         cov = np.zeros(self.L, np.int64) if cover else None
         work = np.zeros(1, np.int64)
         self._chk(self.lib.gnx_tracts_pairs(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(pos, C.c_int64), _ptr(b, C.c_uint64),
-            C.c_int32(int(min_loci)), C.c_int64(int(min_len)),
-            C.c_int32(0 if edges is None else int(np.size(edges))), _ptr(e, C.c_int64),
-            C.c_int64(int(max_work)), _ptr(work, C.c_int64), _ptr(cnt, C.c_int32),
-            _ptr(tot, C.c_int64), _ptr(longest, C.c_int64), _ptr(hist, C.c_int64),
-            _ptr(cov, C.c_int64)))
+            self.h, n, _ptr(s), _ptr(pos), _ptr(b), int(min_loci), int(min_len),
+            0 if edges is None else int(np.size(edges)), _ptr(e), int(max_work), _ptr(work),
+            _ptr(cnt), _ptr(tot), _ptr(longest), _ptr(hist), _ptr(cov)))
         if max_work <= 0:
             return dict(work=int(work[0]), cnt=None, len=None, longest=None, hist=None,
                         cover=None)
@@ -1556,9 +1443,7 @@ class Device:
 
     def tracts_info(self):
         """of the last tracts_self / tracts_pairs: dict(kernel_ms, launches, bytes_read)"""
-        ms, n, nb = C.c_double(), C.c_int64(), C.c_int64()
-        self._chk(self.lib.gnx_tracts_info(self.h, C.byref(ms), C.byref(n), C.byref(nb)))
-        return dict(kernel_ms=ms.value, launches=int(n.value), bytes_read=int(nb.value))
+        return self._outs(self.lib.gnx_tracts_info, ('kernel_ms', 'launches', 'bytes_read'))
 
     # -- close-kin pairs (csrc/gnx_kin.hip) ---------------------------------------------------
     def kin_matrix(self, slots=None, locus_mask=None):
@@ -1573,9 +1458,8 @@ class Device:
         hh = np.zeros((k, k), np.int32)
         ib = np.zeros((k, k), np.int32)
         self._chk(self.lib.gnx_kin_matrix(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64),
-            _ptr(nhet, C.c_int32), _ptr(hh if k else None, C.c_int32),
-            _ptr(ib if k else None, C.c_int32)))
+            self.h, n, _ptr(s), _ptr(m), _ptr(nhet), _ptr(hh if k else None),
+            _ptr(ib if k else None)))
         return dict(nhet=nhet[:k], hh=hh, ibs0=ib)
 
     def kin_pairs(self, T, max_dist=None, slots=None, locus_mask=None, max_pairs=1 << 22,
@@ -1603,12 +1487,9 @@ class Device:
         work, nc, nf = (np.zeros(1, np.int64) for _ in range(3))
         try:
             self._chk(self.lib.gnx_kin_pairs(
-                self.h, C.c_int64(n), _ptr(s, C.c_int64), _ptr(m, C.c_uint64),
-                C.c_double(0.0 if max_dist is None else float(max_dist)), C.c_int64(int(T)),
-                C.c_int64(max_pairs), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
-                _ptr(nc, C.c_int64), _ptr(nf, C.c_int64), _ptr(pa, C.c_int32),
-                _ptr(pb, C.c_int32), _ptr(hh, C.c_int32), _ptr(ib, C.c_int32),
-                _ptr(nhet, C.c_int32)))
+                self.h, n, _ptr(s), _ptr(m), 0.0 if max_dist is None else float(max_dist), int(T),
+                max_pairs, int(max_work), _ptr(work), _ptr(nc), _ptr(nf), _ptr(pa), _ptr(pb),
+                _ptr(hh), _ptr(ib), _ptr(nhet)))
         except GnxError as err:
             if 'exceed max_pairs' in str(err):
                 err.n_found = int(nf[0])
@@ -1622,9 +1503,7 @@ class Device:
 
     def kin_info(self):
         """of the last kin_matrix / kin_pairs: dict(kernel_ms, launches, tasks)"""
-        ms, n, nt = C.c_double(), C.c_int64(), C.c_int64()
-        self._chk(self.lib.gnx_kin_info(self.h, C.byref(ms), C.byref(n), C.byref(nt)))
-        return dict(kernel_ms=ms.value, launches=int(n.value), tasks=int(nt.value))
+        return self._outs(self.lib.gnx_kin_info, ('kernel_ms', 'launches', 'tasks'))
 
     # -- haplotype sweep scans (csrc/gnx_sweeps.hip) -------------------------------------------
     def sweeps_scan(self, loci, pos, brk=None, cls=None, cores=None, slots=None, min_minor=2,
@@ -1665,23 +1544,17 @@ class Device:
         cv = np.zeros((2, 2, m), np.int64) if curve else None
         work = np.zeros(1, np.int64)
         self._chk(self.lib.gnx_sweeps_scan(
-            self.h, C.c_int64(n), _ptr(s, C.c_int64), C.c_int32(int(loci.size)),
-            _ptr(loci if loci.size else np.zeros(1, np.int32), C.c_int32),
-            _ptr(pos if pos.size else np.zeros(1, np.int64), C.c_int64), _ptr(b, C.c_uint8),
-            _ptr(k, C.c_uint8), C.c_int32(n_cores), _ptr(co, C.c_int32),
-            C.c_int32(int(min_minor)), C.c_int32(int(cut_num)), C.c_int32(int(cut_den)),
-            C.c_int64(int(max_gap)), C.c_int64(int(max_extent)), C.c_int64(int(max_work)),
-            _ptr(work, C.c_int64), _ptr(c1, C.c_int64), _ptr(area, C.c_int64),
-            _ptr(steps, C.c_int32), _ptr(status, C.c_uint8), _ptr(cv, C.c_int64)))
+            self.h, n, _ptr(s), int(loci.size), _ptr(loci if loci.size else np.zeros(1, np.int32)),
+            _ptr(pos if pos.size else np.zeros(1, np.int64)), _ptr(b), _ptr(k), n_cores, _ptr(co),
+            int(min_minor), int(cut_num), int(cut_den), int(max_gap), int(max_extent),
+            int(max_work), _ptr(work), _ptr(c1), _ptr(area), _ptr(steps), _ptr(status), _ptr(cv)))
         if max_work <= 0:
             return dict(work=int(work[0]), c1=c1, area=None, steps=None, status=None, curve=None)
         return dict(work=int(work[0]), c1=c1, area=area, steps=steps, status=status, curve=cv)
 
     def sweeps_info(self):
         """of the last sweeps_scan: dict(kernel_ms, launches, steps_total)"""
-        ms, n, ns = C.c_double(), C.c_int64(), C.c_int64()
-        self._chk(self.lib.gnx_sweeps_info(self.h, C.byref(ms), C.byref(n), C.byref(ns)))
-        return dict(kernel_ms=ms.value, launches=int(n.value), steps_total=int(ns.value))
+        return self._outs(self.lib.gnx_sweeps_info, ('kernel_ms', 'launches', 'steps_total'))
 
     # -- lineages through the recorded pedigree (csrc/gnx_lineage.hip) -------------------
     @staticmethod
@@ -1704,9 +1577,8 @@ class Device:
         nodes = _arr(nodes, np.int32).ravel()
         loci = _arr(loci, np.int32).ravel()
         keep = (tab, bt, nodes, loci)
-        args = (self.h, C.c_int64(bt.size), _ptr(tab, C.c_int32), _ptr(bt, C.c_int32),
-                C.c_int64(nodes.size), _ptr(nodes, C.c_int32), int(loci.size),
-                _ptr(loci, C.c_int32), int(t_curr), int(bool(drop_before_sim)),
+        args = (self.h, bt.size, _ptr(tab), _ptr(bt), nodes.size, _ptr(nodes), int(loci.size),
+                _ptr(loci), int(t_curr), int(bool(drop_before_sim)),
                 self._ago(min_time_ago, -2 ** 31, True), self._ago(max_time_ago, 2 ** 31 - 1, False))
         return keep, args, (int(loci.size), int(nodes.size))
 
@@ -1728,7 +1600,7 @@ class Device:
             out['locus_lo'] = np.zeros(shape[0], np.int32)
             out['locus_hi'] = np.zeros(shape[0], np.int32)
         self._chk(self.lib.gnx_lineage_trace(
-            *args, *[_ptr(out.get(k), C.c_int32)
+            *args, *[_ptr(out.get(k))
                      for k in ('root', 'first', 'last', 'n_kept', 'locus_lo', 'locus_hi')]))
         return out
 
@@ -1749,19 +1621,17 @@ class Device:
         offsets = np.zeros(n_kept.size + 1, np.int64)
         np.cumsum(n_kept.ravel(), dtype=np.int64, out=offsets[1:])
         chain = np.zeros(int(offsets[-1]), np.int32)
-        self._chk(self.lib.gnx_lineage_chains(*args, _ptr(offsets, C.c_int64),
-                                              _ptr(chain, C.c_int32)))
+        self._chk(self.lib.gnx_lineage_chains(*args, _ptr(offsets), _ptr(chain)))
         return offsets, chain
 
     def lineage_budget(self, n_bytes):
         """bytes of output per launch of the lineage calls (0: the default, 256 MiB)"""
-        self._chk(self.lib.gnx_lineage_budget(self.h, C.c_int64(int(n_bytes))))
+        self._chk(self.lib.gnx_lineage_budget(self.h, int(n_bytes)))
 
     def lineage_info(self):
         """of the last lineage call: dict(kernel_ms, launches, uploaded)"""
-        ms, n, up = C.c_double(), C.c_int64(), C.c_int64()
-        self._chk(self.lib.gnx_lineage_info(self.h, C.byref(ms), C.byref(n), C.byref(up)))
-        return dict(kernel_ms=ms.value, launches=int(n.value), uploaded=bool(up.value))
+        info = self._outs(self.lib.gnx_lineage_info, ('kernel_ms', 'launches', 'uploaded'))
+        return dict(info, uploaded=bool(info['uploaded']))
 
     # -- simplification of the recorded pedigree (csrc/gnx_simplify.hip) ------------------
     def pedigree_reach(self, node_tab, birth_t, sample_rows, masks_of=None):
@@ -1781,10 +1651,8 @@ class Device:
             masks = np.zeros((req.size, self.W64), np.uint64)
         n_req = 0 if req is None else int(req.size)
         self._chk(self.lib.gnx_pedigree_reach(
-            self.h, C.c_int64(bt.size), _ptr(tab, C.c_int32), _ptr(bt, C.c_int32),
-            C.c_int64(rows.size), _ptr(rows, C.c_int32), _ptr(node_loci, C.c_int32),
-            C.c_int64(n_req), _ptr(req if n_req else None, C.c_int32),
-            _ptr(masks if n_req else None, C.c_uint64)))
+            self.h, bt.size, _ptr(tab), _ptr(bt), rows.size, _ptr(rows), _ptr(node_loci), n_req,
+            _ptr(req if n_req else None), _ptr(masks if n_req else None)))
         return node_loci if masks_of is None else (node_loci, masks)
 
     def lineage_forget(self):
@@ -1802,9 +1670,8 @@ class Device:
             raise ValueError('node_tab: int32 [2 n_rows][2] with birth_t [n_rows]')
         nodes = _arr(nodes, np.int32).ravel()
         loci = _arr(loci, np.int32).ravel()
-        args = (self.h, C.c_int64(bt.size), _ptr(tab, C.c_int32), _ptr(bt, C.c_int32),
-                C.c_int64(nodes.size), _ptr(nodes, C.c_int32), int(loci.size),
-                _ptr(loci, C.c_int32))
+        args = (self.h, bt.size, _ptr(tab), _ptr(bt), nodes.size, _ptr(nodes), int(loci.size),
+                _ptr(loci))
         # (the library refuses fewer than 2 and more than 4096 nodes before it writes)
         n = int(nodes.size) if 2 <= nodes.size <= 4096 else 1
         return (tab, bt, nodes, loci), args, n, int(loci.size)
@@ -1846,12 +1713,9 @@ class Device:
         for k in want:
             out[k] = np.zeros(*shapes[k])
         work = np.zeros(1, np.int64)
-        ct = dict(pair_cnt=C.c_int32, locus_max=C.c_int32, mrca=C.c_int32)
         self._chk(self.lib.gnx_coal_times(
-            *args, int(t_curr), max_ago,
-            C.c_int32(0 if time_edges is None else int(np.size(time_edges))),
-            _ptr(e, C.c_int32), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
-            *[_ptr(out.get(k), ct.get(k, C.c_int64)) for k in self.COAL_TIMES_OUT]))
+            *args, int(t_curr), max_ago, 0 if time_edges is None else int(np.size(time_edges)),
+            _ptr(e), int(max_work), _ptr(work), *[_ptr(out.get(k)) for k in self.COAL_TIMES_OUT]))
         if not run:
             return dict(work=int(work[0]))
         return dict(out, work=int(work[0]))
@@ -1889,12 +1753,9 @@ class Device:
         cov = np.zeros(max(nl, 1), np.int64) if cover else None
         work = np.zeros(1, np.int64)
         self._chk(self.lib.gnx_coal_segments(
-            *args, _ptr(pos, C.c_int64), _ptr(b, C.c_uint8), int(t_curr),
-            self._coal_max_ago(max_time_ago), C.c_int32(int(min_loci)),
-            C.c_int64(int(min_len)), C.c_int32(0 if edges is None else int(np.size(edges))),
-            _ptr(e, C.c_int64), C.c_int64(int(max_work)), _ptr(work, C.c_int64),
-            _ptr(cnt, C.c_int32), _ptr(tot, C.c_int64), _ptr(longest, C.c_int64),
-            _ptr(hist, C.c_int64), _ptr(cov, C.c_int64)))
+            *args, _ptr(pos), _ptr(b), int(t_curr), self._coal_max_ago(max_time_ago), int(min_loci),
+            int(min_len), 0 if edges is None else int(np.size(edges)), _ptr(e), int(max_work),
+            _ptr(work), _ptr(cnt), _ptr(tot), _ptr(longest), _ptr(hist), _ptr(cov)))
         if not run:
             return dict(work=int(work[0]), cnt=None, len=None, longest=None, hist=None,
                         cover=None)
@@ -1914,9 +1775,8 @@ class Device:
         if not (x.size == slots.size and y.size == slots.size):
             raise ValueError('slots, x and y: one entry per newcomer')
         out = np.zeros(4, np.int64)
-        rc = self.lib.gnx_transplant(self.h, src.h, C.c_int64(slots.size), _ptr(slots, C.c_int64),
-                                     _ptr(x, C.c_float), _ptr(y, C.c_float),
-                                     C.c_int64(int(first_id)), _ptr(out, C.c_int64))
+        rc = self.lib.gnx_transplant(self.h, src.h, slots.size, _ptr(slots), _ptr(x), _ptr(y),
+                                     int(first_id), _ptr(out))
         if rc:
             e = GnxError(self.lib.gnx_last_error().decode())
             e.code = int(rc)
@@ -1932,10 +1792,7 @@ class Device:
     def kernel_times(self):
         out = {}
         for k, name in enumerate(KERNELS):
-            ms, n, by = C.c_double(), C.c_int64(), C.c_double()
-            self._chk(self.lib.gnx_kernel_time(self.h, k, C.byref(ms), C.byref(n),
-                                               C.byref(by)))
-            out[name] = dict(ms=ms.value, launches=n.value, bytes=by.value)
+            out[name] = self._outs(self.lib.gnx_kernel_time, ('ms', 'launches', 'bytes'), k)
         return out
 
 
@@ -1944,7 +1801,7 @@ def measure_copy(nbytes=8 << 30, reps=5):
     device: the box's streaming rate beside the 8 TB/s of the data sheet"""
     lib = load()
     out = C.c_double()
-    if lib.gnx_measure_copy(C.c_int64(int(nbytes)), int(reps), C.byref(out)):
+    if lib.gnx_measure_copy(int(nbytes), int(reps), C.byref(out)):
         raise GnxError(lib.gnx_last_error().decode())
     return out.value
 
@@ -1998,8 +1855,8 @@ def walk_many(devs, T, burn, with_selection):
     if not devs:
         return
     arr = (C.c_void_p * len(devs))(*[d.h for d in devs])
-    devs[0]._chk(devs[0].lib.gnx_walk_many(arr, len(devs), C.c_int64(int(T)), int(bool(burn)),
-                                            int(bool(with_selection))))
+    devs[0]._chk(devs[0].lib.gnx_walk_many(arr, len(devs), int(T), int(bool(burn)),
+                                           int(bool(with_selection))))
 
 
 def default_species_params(**kw):

@@ -242,10 +242,10 @@ def test_every_refusal_leaves_the_handle_alone(small):
         o = [np.full(nx * ny, -7, np.int32), np.full(nx * ny, -7, np.int32),
              np.full(nx * ny, -7, np.int64), np.full(nx * ny, -7, np.int64)] if outs is None else outs
         rc = dev.lib.gnx_divmap_sums(
-            dev.h, C.c_int64(n), nat._ptr(slots, C.c_int32), C.c_int32(nx), C.c_int32(ny),
-            nat._ptr(cs, C.c_int64), C.c_int32(r), None, C.c_int64(0),
-            nat._ptr(o[0], C.c_int32), nat._ptr(o[1], C.c_int32), nat._ptr(o[2], C.c_int64),
-            nat._ptr(o[3], C.c_int64))
+            dev.h, C.c_int64(n), nat._ptr(slots), C.c_int32(nx), C.c_int32(ny),
+            nat._ptr(cs), C.c_int32(r), None, C.c_int64(0),
+            nat._ptr(o[0]), nat._ptr(o[1]), nat._ptr(o[2]),
+            nat._ptr(o[3]))
         assert all(a is None or (a == -7).all() for a in o)
         return rc, dev.lib.gnx_last_error()
     one = np.zeros(1, np.int32)

@@ -213,16 +213,16 @@ def test_every_refusal_leaves_the_handle_alone(small):
     import ctypes as C
     one, gs = np.zeros(1, np.int32), np.array([0, 2 ** 30], np.int64)
     o1, oh = np.full(1, -7, np.int32), np.full(1, -7, np.int32)
-    rc = dev.lib.gnx_stats_group_counts(dev.h, C.c_int64(2 ** 30), nat._ptr(one, C.c_int32),
-                                        C.c_int32(1), nat._ptr(gs, C.c_int64),
-                                        nat._ptr(o1, C.c_int32), nat._ptr(oh, C.c_int32))
+    rc = dev.lib.gnx_stats_group_counts(dev.h, C.c_int64(2 ** 30), nat._ptr(one),
+                                        C.c_int32(1), nat._ptr(gs),
+                                        nat._ptr(o1), nat._ptr(oh))
     assert rc == 1 and o1[0] == oh[0] == -7
     assert b'group 0 holds 2^30 individuals or more' in dev.lib.gnx_last_error()
     gs[1] = 2 ** 30 - 1                              # one fewer passes that check: the slots
     rc = dev.lib.gnx_stats_group_counts(dev.h, C.c_int64(2 ** 30 - 1),     # are looked at next
-                                        nat._ptr(np.full(1, -1, np.int32), C.c_int32),
-                                        C.c_int32(1), nat._ptr(gs, C.c_int64),
-                                        nat._ptr(o1, C.c_int32), nat._ptr(oh, C.c_int32))
+                                        nat._ptr(np.full(1, -1, np.int32)),
+                                        C.c_int32(1), nat._ptr(gs),
+                                        nat._ptr(o1), nat._ptr(oh))
     assert rc == 1 and b'slot out of range' in dev.lib.gnx_last_error() and o1[0] == -7
     # G * L above the cap of 2^26 counts per table: a handle with L = 70 000 and 1000 groups
     wide = nat.Device(16, 16, 1, L=70000, cap_inds=64, cap_rows=64, seed=1)
