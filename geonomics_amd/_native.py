@@ -69,9 +69,9 @@ _CTYPES.update((t + '*', C.POINTER(c)) for t, c in _SCALARS.items())
 _NP_PTR = {np.dtype(c): C.POINTER(c) for c in _SCALARS.values()}
 
 
-def parse_prototypes(text):
+def parse_prototypes(text, header='include/gnx_hip.h'):
     """{name: (restype, [argtypes])} of every `ret gnx_name(args);` in the header `text`;
-    a type outside _CTYPES raises, naming the prototype"""
+    a type outside _CTYPES raises, naming the header and the prototype"""
     text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
     protos = {}
     for ret, name, args in re.findall(r'^[ \t]*([\w \t*]+?)\b(gnx_\w+)\s*\(([^)]*)\)\s*;', text,
@@ -81,8 +81,8 @@ def parse_prototypes(text):
         for k, decl in enumerate([ret + ' _'] + args):
             m = re.fullmatch(r'\s*(\w+)\s*(\**)\s*\w*\s*', re.sub(r'\bconst\b', ' ', decl))
             if not m or m.group(1) + m.group(2) not in _CTYPES:
-                raise TypeError('include/gnx_hip.h, %s: no ctypes type for "%s"'
-                                % (name, ' '.join(decl.split()) if k else ret.strip()))
+                raise TypeError('%s, %s: no ctypes type for "%s"'
+                                % (header, name, ' '.join(decl.split()) if k else ret.strip()))
             types.append(_CTYPES[m.group(1) + m.group(2)])
         protos[name] = (types[0], types[1:])
     return protos
@@ -91,12 +91,15 @@ def parse_prototypes(text):
 with open(os.path.join(_HERE, '..', 'include', 'gnx_hip.h')) as _f:
     PROTOTYPES = parse_prototypes(_f.read())
 EXPORTS = list(PROTOTYPES)
+# the entry points declared in headers of their own (include/gnx_glm.h), read the same way
+with open(os.path.join(_HERE, '..', 'include', 'gnx_glm.h')) as _f:
+    PROTOTYPES_EXT = parse_prototypes(_f.read(), 'include/gnx_glm.h')
 
 _lib = None
 
 
 def load():
-    """Load libgnxhip.so and declare every prototype of the header on it; raises if it has
+    """Load libgnxhip.so and declare every prototype of the headers on it; raises if it has
     not been built."""
     global _lib
     if _lib is not None:
@@ -107,7 +110,7 @@ def load():
             '`python -m geonomics_amd.build` (hipcc, gfx950). There is no CPU '
             'fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_EXT}.items():
         fn = getattr(lib, name, None)       # (None: an older build behind GNX_LIB lacks it)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -1378,6 +1381,32 @@ class Device:
             self.h, n, _ptr(s), _ptr(mk), _ptr(v), int(M.shape[0]), _ptr(M), _ptr(out),
             C.byref(ms)))
         return dict(q=out, kernel_ms=ms.value)
+
+    # -- the sums of a Newton step of m logistic fits (csrc/gnx_glm.hip) ---------------------
+    def glm_sweep(self, X, B, info=False):
+        """per fit k the sums [s, A, I] of a binomial GLM with the logit link at the coefficients
+        B[k] over the design X (include/gnx_glm.h, gnx_glm_sweep): X fp64 [n][p], B fp64 [m][p]
+        on the host, finite, 1 <= p <= 8 -> (sums fp64 [m][1 + p + p (p + 1) / 2], kernel_ms);
+        info: a dict(sums, kernel_ms, stretch, stretches (the summation order:
+        sim/glm.stretch_rule)) instead"""
+        X = _arr(X, np.float64)
+        B = _arr(B, np.float64)
+        if X.ndim != 2 or B.ndim != 2 or X.shape[1] != B.shape[1]:
+            raise ValueError('X [n][p] and B [m][p] (got %s and %s)' % (X.shape, B.shape))
+        (n, p), m = X.shape, int(B.shape[0])
+        # (the library refuses p outside 1..8 before it writes)
+        out = np.zeros((m, 1 + p + p * (p + 1) // 2 if 1 <= p <= 8 else 0))
+        per, cnt, ms = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+        self._chk(self.lib.gnx_glm_sweep(self.h, n, p, _ptr(X), m, _ptr(B), _ptr(out),
+                                         C.byref(per), C.byref(cnt), C.byref(ms)))
+        if info:
+            return dict(sums=out, kernel_ms=ms.value, stretch=int(per.value),
+                        stretches=int(cnt.value))
+        return out, ms.value
+
+    def glm_budget(self, n_bytes):
+        """bytes of device scratch one batch of fits of glm_sweep may take (0: the default)"""
+        self._chk(self.lib.gnx_glm_budget(self.h, int(n_bytes)))
 
     # -- identity tracts of the phased genomes (csrc/gnx_tracts.hip) ------------------------
     def _tract_args(self, pos, brk, edges):

@@ -354,6 +354,7 @@ struct gnx_state {
   int64_t lin_budget = 0;        // output bytes per launch (0: the default)
   double lin_ms = 0.0;           // kernel time, launches and upload of the last call
   int64_t lin_launches = 0, lin_uploaded = 0;
+  int64_t glm_budget = 0;        // gnx_glm_sweep: bytes of partial sums per batch (0: the default)
 
   // linkage disequilibrium (gnx_ld.hip): bytes of transposed bit rows resident at a time (0: the
   // default), and the kernel time, launches and locus blocks of the last call

@@ -908,6 +908,53 @@ class Model:
                              individs=self._test_sample(spp, individs, n), loci=loci,
                              min_maf=min_maf, calibrate=calibrate)
 
+    def run_logistic_gea(self, spp=0, env_lyrs=None, env=None, covars=(), n_pcs=0, individs=None,
+                         n=None, loci=None, min_maf=0.01, calibrate=False, tol=1e-8, max_iter=25):
+        """logistic genotype-environment association scan (Sambada: Joost et al. 2007, Stucki et
+        al. 2017; an extension: the reference has no such analysis): for every locus the binomial
+        model dosage ~ Binomial(2, mu), logit mu = intercept + covariates + environment, so that
+        an effect is a log-odds of the allele per unit of environment and the fitted frequency
+        stays inside 0..1.  The tested columns are the layers env_lyrs (default: the layers the
+        Traits are tied to, or all) or a table env [n][r] in ascending-id order; they are tested
+        together by the likelihood ratio (the G score, on r degrees of freedom) and each by Wald.
+        covars and n_pcs as run_gwas; at most 7 columns beside the intercept, and none may be
+        constant or a combination of the others.  The genomes are read once on the device
+        (gnx_assoc_cross: X^T D in fp64); every Newton step of the fits that have not converged
+        is one device sweep over the design (gnx_glm_sweep), the 2 x 2 .. 8 x 8 solves run on the
+        host.  individs, or a random sample of n, restrict the rows; loci selects rows of the
+        result after the full scan.  Loci that are monomorphic or below min_maf are not fitted
+        (NaN); a locus that has not converged after max_iter steps (separation: the allele is
+        absent on one side of a threshold) is reported with converged False, not raised.
+        calibrate: p from lrt / gif
+        -> dict: loci, beta, se, z, p_wald [n_loci][r], lrt, p, q, maf, tested, converged, n_iter
+        [n_loci], gif, df, ids, trait_loci (per layer), kernel_ms, n_sweeps, seconds"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._run_logistic_gea(env_lyrs=env_lyrs, env=env, covars=covars, n_pcs=n_pcs,
+                                     individs=self._test_sample(spp, individs, n), loci=loci,
+                                     min_maf=min_maf, calibrate=calibrate, tol=tol,
+                                     max_iter=max_iter)
+
+    def calc_clines(self, spp=0, axis='x', covars=(), individs=None, n=None, loci=None,
+                    min_maf=0.01, sigma=None, tol=1e-8, max_iter=25):
+        """the sigmoid cline of every locus along a transect (an extension: the reference has no
+        such analysis): p(x) = 1 / (1 + exp(-4 (x - c) / w)) fitted by maximum likelihood as the
+        binomial model of run_logistic_gea with the axis as its one tested column, centre
+        c = -b0 / b1 and width w = 4 / |b1| with delta-method standard errors.  axis: 'x', 'y',
+        ('env', lyr), an angle in degrees (the coordinates projected on that direction), or
+        values [n] in ascending-id order; covars as run_gwas (centred: the cline at their means).
+        Concordant centres and narrow widths mark the loci under selection along a gradient or
+        across a secondary contact (add_individuals, calc_local_ancestry); with the dispersal
+        distance sigma (find_kin estimates it) a width becomes s_hat = 8 sigma^2 / w^2.
+        individs, n, loci, min_maf, tol, max_iter as run_logistic_gea
+        -> dict: loci, centre, width, se_centre, se_width, beta [n_loci][2 + c], delta_p,
+        in_range, slope_sign, lrt, p, q, maf, tested, converged [n_loci], axis_range, ids,
+        trait_loci, concordance (the median and MAD of centre and width over the loci that are
+        tested, converged, in range and have q <= 0.05), kernel_ms, n_sweeps, s_hat (with sigma)"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_clines(axis=axis, covars=covars,
+                                individs=self._test_sample(spp, individs, n), loci=loci,
+                                min_maf=min_maf, sigma=sigma, tol=tol, max_iter=max_iter)
+
     def calc_grm(self, spp=0, individs=None, n=None, loci=None, kind='additive', method='gcta',
                  alpha=-1.0, min_maf=0.01, weights=None):
         """the standardised genomic relationship matrix of at most 8192 individuals (an

@@ -72,6 +72,22 @@ def _solver_opts(who, tol, max_iter):
         raise ValueError('%s: max_iter: at least 1 iteration (got %r)' % (who, max_iter))
 
 
+def _newton_opts(who, tol, max_iter):
+    """refuse a tolerance or an iteration limit the Newton iteration of sim/glm.fit cannot take"""
+    try:
+        ok = not isinstance(tol, bool) and 0 < float(tol) < 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('%s: tol: a relative step in (0, 1) (got %r)' % (who, tol))
+    try:
+        ok = not isinstance(max_iter, bool) and int(max_iter) == max_iter and max_iter >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('%s: max_iter: at least 1 iteration (got %r)' % (who, max_iter))
+
+
 # -- the request checks the analyses share: functions of the Species like _split_predictors, not
 # methods, so that an object that borrows single analysis methods of the class can run them -----
 def _need_genomes(spp, who=None, assigned=True):
@@ -549,6 +565,160 @@ class SpeciesAnalyses:
         res = _as.scan(lambda Y: self._dev.assoc_cross(Y, slots), n, X, U, 'gea', True, min_maf,
                        collinear_tol, calibrate)
         return self._assoc_result(res, ids, loci, trait_loci, U=U)
+
+    # -- per-locus logistic fits (sim/glm.py; csrc/gnx_glm.hip, csrc/gnx_assoc.hip) ----------
+    def _logistic_covars(self, who, covars, n_pcs, n, n_other):
+        """the covariates of a logistic scan as _run_gwas reads them, counted (with the n_other
+        other columns beside the intercept) before the device is asked -> fetch(ids, slots)"""
+        from ..sim import glm as _glm
+        if isinstance(n_pcs, bool) or int(n_pcs) != n_pcs or n_pcs < 0:
+            raise ValueError('%s: n_pcs: a number of genetic PCs >= 0 (got %r)' % (who, n_pcs))
+        cov = self._assoc_covars(who, covars, n)
+        n_cov = sum(len(self._env_layers(who, None)) if c is None else c for c, _ in cov)
+        _glm.check_columns(n_cov + int(n_pcs) + n_other, who)
+
+        def fetch(ids, slots):
+            pcs = np.zeros((n, 0))
+            if n_pcs:
+                pcs = np.asarray(self._calc_genetic_PCA(int(n_pcs), individs=ids)[1], np.float64)
+            return np.column_stack([f(slots) for _, f in cov] + [pcs])
+        return fetch
+
+    def _logistic_scan(self, who, slots, n, X, C, min_maf, tol, max_iter, calibrate):
+        """sim/glm.scan over the device: one gnx_assoc_cross and the sweeps of gnx_glm_sweep"""
+        from ..sim import glm as _glm
+        return _glm.scan(lambda Y: self._dev.assoc_cross(Y, slots),
+                         lambda Z, B: self._dev.glm_sweep(Z, B), n, X, C, min_maf, tol, max_iter,
+                         calibrate, who)
+
+    def _run_logistic_gea(self, env_lyrs=None, env=None, covars=(), n_pcs=0, individs=None,
+                          loci=None, min_maf=0.01, calibrate=False, tol=1e-8, max_iter=25):
+        """a logistic genotype-environment association scan (Sambada: Joost et al. 2007, Stucki
+        et al. 2017) over the living individuals asked for (all by default): per locus the
+        binomial GLM d_i ~ Binomial(2, mu_i), logit mu_i = b0 + covariates + env_i . beta, fitted
+        by Newton's method (sim/glm.fit; tol, max_iter), the tested columns (env_lyrs; default: the
+        layers the Traits are tied to, or all; env: a table [n][r] in ascending-id order instead)
+        tested together by the likelihood ratio against the model without them and each by Wald.
+        Covariates and genetic PCs as _run_gwas; at most 7 columns beside the intercept.  One
+        pass of gnx_assoc_cross over the packed genomes (X^T D, s1, s2), then one gnx_glm_sweep
+        per Newton step over the fits that have not converged.  loci selects rows of the result on
+        the host
+        -> dict: loci, beta, se, z, p_wald [n_loci][r], lrt, p, q, maf, tested, converged, n_iter
+        [n_loci], gif, df (= r), ids, trait_loci (per layer, as _run_lfmm), kernel_ms (cross and
+        sweeps), n_sweeps, seconds"""
+        import time
+        who = 'run_logistic_gea'
+        _need_genomes(self, who)
+        _newton_opts(who, tol, max_iter)
+        ids, slots = self._geno_sample(individs)
+        n = int(ids.size)
+        if env is not None:
+            if env_lyrs is not None:
+                raise ValueError('%s: give env_lyrs or env, not both' % who)
+            X = np.asarray(env, dtype=np.float64)
+            X = X[:, None] if X.ndim == 1 else X
+            if X.ndim != 2 or X.shape[0] != n or X.shape[1] < 1 or not np.isfinite(X).all():
+                raise ValueError('%s: env: finite values [n = %d][r] in ascending-id order '
+                                 '(got %s)' % (who, n, X.shape))
+            lyrs, r = None, X.shape[1]
+        else:
+            lyrs = self._env_layers(who, env_lyrs)
+            r = len(lyrs)
+        fetch = self._logistic_covars(who, covars, n_pcs, n, r)
+        # ---- from here on the device is asked (sim/glm.scan checks the design's rank first)
+        t0 = time.perf_counter()
+        trait_loci = None
+        if lyrs is not None:
+            X = self._field(nat.F_E)[lyrs][:, slots].T.astype(np.float64)
+            traits = self.gen_arch.traits or {}
+            trait_loci = [np.unique(np.concatenate(
+                [np.asarray(t.loci, dtype=np.int64).ravel() for t in traits.values()
+                 if int(t.lyr_num) == l] + [np.zeros(0, np.int64)])) for l in lyrs]
+        res = self._logistic_scan(who, slots, n, X, fetch(ids, slots), min_maf, tol, max_iter,
+                                  calibrate)
+        loci_u, _ = self._geno_loci(loci)
+        if loci_u is None:
+            loci_u = np.arange(self._dev.L, dtype=np.int64)
+        out = {k: res[k][loci_u] for k in ('beta', 'se', 'z', 'p_wald', 'lrt', 'p', 'q', 'maf',
+                                           'tested', 'converged', 'n_iter')}
+        out.update(loci=loci_u, gif=res['gif'], df=res['df'], ids=ids, trait_loci=trait_loci,
+                   kernel_ms=res['kernel_ms'], n_sweeps=res['n_sweeps'],
+                   seconds=time.perf_counter() - t0)
+        return out
+
+    def _calc_clines(self, axis='x', covars=(), individs=None, loci=None, min_maf=0.01,
+                     sigma=None, tol=1e-8, max_iter=25):
+        """the sigmoid cline of every locus along one axis over the living individuals asked for
+        (all by default): p(x) = 1 / (1 + exp(-4 (x - c) / w)), the binomial GLM of
+        _run_logistic_gea with the axis as its one tested column (and the covariates, centred, so
+        that the cline is the one at their means).  axis: 'x', 'y', ('env', lyr), an angle in
+        degrees (the coordinates projected on that direction, 0 = x, 90 = y), or values [n] in
+        ascending-id order.  sigma: the dispersal distance per generation (find_kin estimates
+        it), which turns a width into a selection coefficient s_hat = 8 sigma^2 / w^2
+        -> dict: loci, centre, width, se_centre, se_width, beta [n_loci][2 + c] (intercept, axis,
+        covariates), delta_p (the fitted frequency at the upper end of the axis minus that at the
+        lower), in_range (the centre lies inside axis_range), slope_sign, lrt, p, q, maf, tested,
+        converged [n_loci], axis_range (lo, hi), ids, trait_loci (every Trait's loci),
+        concordance (sim/glm.concordance over the loci that are tested, converged, in_range and
+        have q <= 0.05), kernel_ms, n_sweeps, and with sigma s_hat [n_loci]"""
+        from ..sim import glm as _glm
+        who = 'calc_clines'
+        _need_genomes(self, who)
+        _newton_opts(who, tol, max_iter)
+        if sigma is not None and (isinstance(sigma, bool) or not np.isfinite(sigma)
+                                  or not sigma > 0):
+            raise ValueError('%s: sigma: a positive dispersal distance (got %r)' % (who, sigma))
+        ids, slots = self._geno_sample(individs)
+        n = int(ids.size)
+        bad_axis = ValueError("%s: axis: 'x', 'y', ('env', lyr), an angle in degrees or finite "
+                              "values [n = %d] in ascending-id order (got %r)" % (who, n, axis))
+        if isinstance(axis, str):
+            if axis not in ('x', 'y'):
+                raise bad_axis
+            get = lambda: self._field(nat.F_X if axis == 'x' else nat.F_Y)[slots]  # noqa: E731
+        elif isinstance(axis, tuple) and len(axis) == 2 and axis[0] == 'env':
+            lyr = self._env_layers(who, [axis[1]])
+            get = lambda: self._field(nat.F_E)[lyr][0][slots]                       # noqa: E731
+        elif isinstance(axis, (int, float, np.integer, np.floating)) and \
+                not isinstance(axis, bool) and np.isfinite(axis):
+            th = np.deg2rad(float(axis))
+            get = lambda: (np.cos(th) * self._field(nat.F_X)[slots].astype(np.float64)  # noqa: E731
+                           + np.sin(th) * self._field(nat.F_Y)[slots].astype(np.float64))
+        else:
+            try:
+                a = np.asarray(axis, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise bad_axis from None
+            if a.shape != (n,) or not np.isfinite(a).all():
+                raise bad_axis
+            get = lambda: a                                                         # noqa: E731
+        fetch = self._logistic_covars(who, covars, 0, n, 1)
+        # ---- from here on the device is asked (sim/glm.scan checks the design's rank first)
+        x = np.asarray(get(), np.float64)
+        C = fetch(ids, slots)
+        C = C - C.mean(axis=0)
+        c = C.shape[1]
+        res = self._logistic_scan(who, slots, n, x, C, min_maf, tol, max_iter, False)
+        lo, hi = float(x.min()), float(x.max())
+        ends = [0, 1 + c]                                    # the design is [1, C, x]
+        st = _glm.cline_stats(res['coef'][:, ends], res['cov'][:, ends][:, :, ends], lo, hi)
+        loci_u, _ = self._geno_loci(loci)
+        if loci_u is None:
+            loci_u = np.arange(self._dev.L, dtype=np.int64)
+        use = res['tested'] & res['converged'] & st['in_range'] & (res['q'] <= 0.05)
+        traits = self.gen_arch.traits or {}
+        out = {k: st[k][loci_u] for k in st}
+        out.update({k: res[k][loci_u] for k in ('lrt', 'p', 'q', 'maf', 'tested', 'converged')})
+        out.update(loci=loci_u, beta=res['coef'][:, ends + list(range(1, 1 + c))][loci_u],
+                   axis_range=(lo, hi), ids=ids,
+                   trait_loci=np.unique(np.concatenate(
+                       [np.asarray(t.loci, dtype=np.int64).ravel() for t in traits.values()]
+                       + [np.zeros(0, np.int64)])),
+                   concordance=_glm.concordance(st['centre'], st['width'], use),
+                   kernel_ms=res['kernel_ms'], n_sweeps=res['n_sweeps'])
+        if sigma is not None:
+            out['s_hat'] = 8.0 * float(sigma) ** 2 / out['width'] ** 2
+        return out
 
     # -- relationship matrices, heritability and breeding values (sim/quantgen.py;
     # csrc/gnx_grm.hip) ---------------------------------------------------------------------

@@ -88,6 +88,11 @@ _NOT_TILED = {
                  'model on one GPU',
     '_run_lfmm': 'run_lfmm with a Species tiled over several GPUs is not implemented; run the '
                  'model on one GPU',
+    # per-locus logistic fits (the cross-products of run_gwas, and one design for all tiles)
+    '_run_logistic_gea': 'run_logistic_gea with a Species tiled over several GPUs is not '
+                         'implemented; run the model on one GPU',
+    '_calc_clines': 'calc_clines with a Species tiled over several GPUs is not implemented; run '
+                    'the model on one GPU',
     # relationship matrices and what rests on them (a gather of the sample, as the Gram matrix)
     '_calc_grm': 'calc_grm with a Species tiled over several GPUs is not implemented; run the '
                  'model on one GPU',
