@@ -1204,12 +1204,32 @@ extern "C" int gnx_step_begin(gnx_state* h, int32_t burn) {
 extern "C" int gnx_step_mid(gnx_state* h, int32_t burn, int32_t with_selection) {
   GnxStepTimer timer(false);
   int64_t P = 0, B = 0;
-  GNXCHK(gnx_l_find_pairs_finish(h, &P));
+  const bool counted = h->pairs_wait;
+  GNXCHK(gnx_l_find_pairs_count(h, &P));
+  // The last step's crossover held back for this pair list (xo_launch_late) goes on its stream
+  // BEHIND the births' enqueue: the births head the step's chain (births -> density -> death
+  // probabilities -> death draws), nobody but the next crossover reads this one's rows, and handing
+  // it over costs the host a wait, one or two launches and one or two records - the time the
+  // births used to become runnable later than a crossover that fills the chip.  It still waits
+  // for the pair list alone (ev_pairs, recorded behind k_pair_compact), not for the births.
+  // (Offspring that nobody gave their crossover - xo_deferred, a step cut short - make gnx_l_mate
+  // launch the held-back one itself, and Poisson births make the host wait for their sum - the
+  // crossover would stand idle meanwhile: the old order for both.)
+  const bool held = counted && h->xo_launch_late && h->xo_ready_buf >= 0;
+  const bool births_first =
+      held && h->pairs_ev && !h->xo_deferred && !h->tiled && h->sp.n_births_fixed;
+  if (held && !births_first) GNXCHK(gnx_xo_launch_pending(h, GNX_PC_XO_P2));
   if (P > 0 && !h->spl_P.valid)
     GNXCHK(gnx_l_density(h, P, h->mid_x, h->mid_y, &h->spl_P, nullptr));
   // births: dispersal, alleles at the selected loci, phenotype (tile-major offspring ids,
   // gnx_set_id_order: the pairs' offsets from this device's own counts - gnx_l_mate)
-  GNXCHK(gnx_l_mate(h, burn != 0, false, 0, &B));
+  int rc = gnx_l_mate(h, burn != 0, false, 0, &B);
+  // (whatever became of the births - none, or too many for the handle: once, here)
+  if (births_first) {
+    const int rc_xo = gnx_xo_launch_pending(h, GNX_PC_XO_P2, h->ev_pairs);
+    if (!rc) rc = rc_xo;
+  }
+  GNXCHK(rc);
   h->last_births = B;
   // N density of everyone incl. offspring (structs/species.py:845-882); d at each
   // individual's cell, fitness, death probability; mortality

@@ -607,6 +607,7 @@ struct gnx_state {
   hipEvent_t ev_pairs = nullptr, ev_latP = nullptr, ev_perm = nullptr, ev_binsN = nullptr;
   bool binsN_inflight = false;       // the adults are being counted on stream3
   bool latP_inflight = false;        // spl_P is being written on stream3
+  bool pairs_ev = false;             // ev_pairs stands right behind the current pair list's k_pair_compact
   // An index of the slots in ascending id order (ord[k] = slot of the k-th smallest id, k <
   // ord_n; slots appended since - this step's offspring - follow in slot order).  With it the
   // cell sort is a STABLE radix sort of that sequence by cell alone (2 passes instead of 4-5:
@@ -808,6 +809,9 @@ int gnx_l_find_pairs(gnx_state* h, const uint8_t* d_keep, int64_t* n_pairs_out,
 // ... in two halves: everything enqueued / the pair count read
 int gnx_l_find_pairs_enqueue(gnx_state* h, const uint8_t* d_keep, bool with_density);
 int gnx_l_find_pairs_finish(gnx_state* h, int64_t* n_pairs_out);
+// ... the pair count alone: a crossover held back for this pair list (xo_launch_late) stays
+// pending, the caller launches it behind the births (gnx_step_mid)
+int gnx_l_find_pairs_count(gnx_state* h, int64_t* n_pairs_out);
 int gnx_l_births(gnx_state* h, int64_t* births_out);
 int gnx_l_pair_cls(gnx_state* h, int64_t P, bool local);
 int gnx_vt_buffers(gnx_state* h);      // (allocated by gnx_set_id_order: never inside a stream capture)
@@ -835,8 +839,9 @@ int gnx_xo_flush_deferred(gnx_state* h);
 // launch the crossover whose jobs are ready (no-op otherwise).  site (gnx_path_counts):
 // GNX_PC_XO_P2 from launch policy 2's site (xo_launch_late: behind the next pair list), -1 right
 // behind the job builder, GNX_PC_XO_FLUSH (the default) from anybody else - a join, a genome
-// access, a wait
-int gnx_xo_launch_pending(gnx_state* h, int site = GNX_PC_XO_FLUSH);
+// access, a wait.  after: an event already recorded on `stream` that the crossover waits for
+// in place of everything `stream` has been given so far (null: a record of its own, here)
+int gnx_xo_launch_pending(gnx_state* h, int site = GNX_PC_XO_FLUSH, hipEvent_t after = nullptr);
 // `stream` waits for the crossover in flight (not for one that is not launched yet)
 int gnx_xo_wait_inflight(gnx_state* h);
 int gnx_xo_prepare_jobs(gnx_state* h, int32_t** zero);

@@ -336,15 +336,19 @@ int gnx_l_crossover_pending(gnx_state* h, int64_t first_slot, int64_t B) {
   return 0;
 }
 
-int gnx_xo_launch_pending(gnx_state* h, int site) {
+int gnx_xo_launch_pending(gnx_state* h, int site, hipEvent_t after) {
   const int buf = h->xo_ready_buf;
   if (buf < 0) return 0;
   h->xo_ready_buf = -1;
   if (site == GNX_PC_XO_P2 || site == GNX_PC_XO_FLUSH) ++h->pc[site];     // (gnx_path_counts)
   // behind everything `stream` has been given so far (the jobs, and with the late launch
-  // the sort that is meant to run alone)
-  HIPCHK(hipEventRecord(h->ev_jobs, h->stream));
-  HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_jobs, 0));
+  // the sort that is meant to run alone) - or, `after`, up to the pair list: the births that
+  // gnx_step_mid has enqueued since are not waited for
+  if (!after) {
+    HIPCHK(hipEventRecord(h->ev_jobs, h->stream));
+    after = h->ev_jobs;
+  }
+  HIPCHK(hipStreamWaitEvent(h->stream2, after, 0));
   hipStream_t main = h->stream;
   h->stream = h->stream2;                        // the timer events go where the kernel goes
   // Split launch (xo_split / 1024 of the jobs): the first share at full width, alone on the

@@ -2023,32 +2023,46 @@ k_pair_compact(int64_t N, const int32_t* focal, const int32_t* mate, const int32
   const int64_t base = (int64_t)blockIdx.x * GNX_CB;
   bool f[4];
   int sc[4] = {0, 0, 0, 0};
-  // (Every load of this kernel issued up front, level by level, as k_pair_flags does it: 13 - 15
-  // us alone against 17 - 19, measured and removed.  Workgroup 0 hands the host the pair count
-  // when this kernel STARTS, and the host has until its end to enqueue the births in front of
-  // the crossover that waits for the pair list; at 11.7 us instead of 15.8 in the step it lost
-  // that race in every second run of bench.py - births beside the crossover, 109 us against 58,
-  // a step of 0.49 - 0.53 ms against 0.47: profiles/rounds_ab_runs.txt, session 3)
+  // Every load of this kernel by dependency level, each level for all four rounds before the
+  // next one starts, as k_pair_flags does it: 13 - 15 us alone against 17 - 19.  Every load is
+  // unconditional, from an index that is legal whatever the lane holds: items past N repeat
+  // item N - 1, an item without a mate stands in for its mate itself, and a block without a
+  // live item - N can be 0 under a capacity-sized grid - loads nothing.
+  // (Workgroup 0 hands the host the pair count when this kernel STARTS; the births no longer
+  // race the crossover for the time until it ends - gnx_step_mid enqueues them first -
+  // profiles/births_first_ab_runs.txt)
+  int32_t fl[4] = {0, 0, 0, 0}, mt[4] = {0, 0, 0, 0}, fo4[4] = {0, 0, 0, 0};
+  uint64_t pk[4] = {0, 0, 0, 0};
+  float fx[4] = {0.f, 0.f, 0.f, 0.f}, fy[4] = {0.f, 0.f, 0.f, 0.f};
+  float gx[4] = {0.f, 0.f, 0.f, 0.f}, gy[4] = {0.f, 0.f, 0.f, 0.f};
+  if (base < N) {
+    // level 1: by the item itself
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int64_t i = base + r * 256 + threadIdx.x;
-    f[r] = i < N && flag2[i] != 0;
-    if (vt.cls && i < N) sc[r] = vt.scls[i];     // (with the flags: no round trip of its own)
+    for (int r = 0; r < 4; ++r) {
+      const int64_t ic = min(base + r * 256 + (int64_t)threadIdx.x, N - 1);
+      fl[r] = flag2[ic];
+      mt[r] = mate[ic];
+      fo4[r] = focal ? focal[ic] : (int32_t)ic;
+      pk[r] = popkey[ic];
+      if (vt.cls) sc[r] = vt.scls[ic];           // (with the flags: no round trip of its own)
+    }
+    // level 2: by the focal individual (the item itself but for panmixia) and by the mate
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int32_t mc = mt[r] >= 0 ? mt[r] : fo4[r];
+      fx[r] = x[fo4[r]];
+      fy[r] = y[fo4[r]];
+      gx[r] = x[mc];
+      gy[r] = y[mc];
+    }
   }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) f[r] = base + r * 256 + threadIdx.x < N && fl[r] != 0;
   int rank[4], tot;
   gnx_block_ranks(f, rank, tot, lds);            // (barriers: vcnt is zero, vpre written)
   // tile-major offspring ids: the pair's virtual tile (by its focal individual's position), its
   // rank among the block's pairs of the same virtual tile, the block's count per virtual tile
   int vc[4] = {0, 0, 0, 0}, vrw[4] = {0, 0, 0, 0};
-  float fx[4], fy[4];
-  int fo4[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int64_t i = base + r * 256 + threadIdx.x;
-    fo4[r] = f[r] ? (focal ? focal[i] : (int)i) : 0;
-    fx[r] = f[r] ? x[fo4[r]] : 0.f;
-    fy[r] = f[r] ? y[fo4[r]] : 0.f;
-  }
   if (vt.cls) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -2061,18 +2075,15 @@ k_pair_compact(int64_t N, const int32_t* focal, const int32_t* mate, const int32
   const int32_t bo = cnt ? self_off : blk_off[blockIdx.x];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int64_t i = base + r * 256 + threadIdx.x;
     int bin = 0;
     if (f[r]) {
       const int p = bo + rank[r];
-      const int m = mate[i];
-      const int fo = fo4[r];
-      pairs[2 * p] = fo;
-      pairs[2 * p + 1] = m;
-      const float mx = (fx[r] + x[m]) / 2.0f, my = (fy[r] + y[m]) / 2.0f;
+      pairs[2 * p] = fo4[r];
+      pairs[2 * p + 1] = mt[r];
+      const float mx = (fx[r] + gx[r]) / 2.0f, my = (fy[r] + gy[r]) / 2.0f;
       mid_x[p] = mx;
       mid_y[p] = my;
-      const uint64_t k = popkey[i];
+      const uint64_t k = pk[r];
       key[p] = ((k >> idbits) << 40) | (k & ((1ull << idbits) - 1ull));
       if (bins.bins) bin = gnx_bin_of(bins, mx, my);
       if (vt.cls) {
@@ -2121,6 +2132,7 @@ int gnx_l_find_pairs_enqueue(gnx_state* h, const uint8_t* d_keep, bool with_dens
   int64_t N = h->N;
   h->n_pairs = 0;
   h->pairs_wait = false;
+  h->pairs_ev = false;
   if (N == 0) return 0;
   const gnx_species_params& sp = h->sp;
   GnxSoA s = h->soa[h->cur];
@@ -2173,7 +2185,15 @@ int gnx_l_find_pairs_enqueue(gnx_state* h, const uint8_t* d_keep, bool with_dens
   HIPCHK(hipGetLastError());
   // the pair midpoints' density (ops/demography.py:60-91): on one GPU bins + lattice run on
   // stream3 beside k_offspring and the death probabilities wait for them
-  if (with_density && gnx_fused_bins(h)) {
+  const bool fused = with_density && gnx_fused_bins(h);
+  // (ev_pairs right behind k_pair_compact: what a crossover held back for this pair list waits
+  // for - gnx_step_mid.  gnx_l_lattice_P_async records it first thing)
+  h->pairs_ev = fused;
+  if (!fused && h->xo_launch_late && h->xo_ready_buf >= 0 && !h->tiled && !h->tile2_mode) {
+    HIPCHK(hipEventRecord(h->ev_pairs, h->stream));
+    h->pairs_ev = true;
+  }
+  if (fused) {
     GNXCHK(gnx_l_lattice_P_async(h, N));
   } else if (with_density) {
     // the density of the pair midpoints reads the pair count on the device (at most N
@@ -2192,6 +2212,13 @@ int gnx_l_find_pairs_enqueue(gnx_state* h, const uint8_t* d_keep, bool with_dens
 }
 
 int gnx_l_find_pairs_finish(gnx_state* h, int64_t* n_pairs_out) {
+  const bool waited = h->pairs_wait;
+  GNXCHK(gnx_l_find_pairs_count(h, n_pairs_out));
+  if (waited && h->xo_launch_late) GNXCHK(gnx_xo_launch_pending(h, GNX_PC_XO_P2));
+  return 0;
+}
+
+int gnx_l_find_pairs_count(gnx_state* h, int64_t* n_pairs_out) {
   *n_pairs_out = 0;
   if (!h->pairs_wait) return 0;
   h->pairs_wait = false;
@@ -2203,7 +2230,6 @@ int gnx_l_find_pairs_finish(gnx_state* h, int64_t* n_pairs_out) {
   *n_pairs_out = h->n_pairs;
   if (!h->pairs_with_density) h->spl_P.valid = false;
   else if (h->n_pairs == 0) h->spl_P.valid = false;
-  if (h->xo_launch_late) GNXCHK(gnx_xo_launch_pending(h, GNX_PC_XO_P2));
   return 0;
 }
 
