@@ -94,6 +94,9 @@ EXPORTS = list(PROTOTYPES)
 # the entry points declared in headers of their own (include/gnx_glm.h), read the same way
 with open(os.path.join(_HERE, '..', 'include', 'gnx_glm.h')) as _f:
     PROTOTYPES_EXT = parse_prototypes(_f.read(), 'include/gnx_glm.h')
+# (include/gnx_ldwin.h)
+with open(os.path.join(_HERE, '..', 'include', 'gnx_ldwin.h')) as _f:
+    PROTOTYPES_LDWIN = parse_prototypes(_f.read(), 'include/gnx_ldwin.h')
 
 _lib = None
 
@@ -110,7 +113,7 @@ def load():
             '`python -m geonomics_amd.build` (hipcc, gfx950). There is no CPU '
             'fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_EXT}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_EXT, **PROTOTYPES_LDWIN}.items():
         fn = getattr(lib, name, None)       # (None: an older build behind GNX_LIB lacks it)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -1244,6 +1247,57 @@ class Device:
     def ld_info(self):
         """of the last ld_bins: dict(kernel_ms, launches, locus_blocks)"""
         return self._outs(self.lib.gnx_ld_info, ('kernel_ms', 'launches', 'locus_blocks'))
+
+    # -- windowed linkage disequilibrium (csrc/gnx_ldwin.hip) --------------------------------
+    def ld_window(self, loci, pos, window, slots=None, min_minor=1, r2_min=0.0, max_edges=0,
+                  max_work=0, scores=True):
+        """per locus of `loci` the kept loci within `window` of it (partners) and the sum of its
+        r^2 with them (score), and with max_edges > 0 the in-window pairs with r^2 >= r2_min,
+        sorted by (ei, ej) (include/gnx_ldwin.h, gnx_ld_window).  loci int32 [n_loci] distinct;
+        pos float64 [n_loci] non-decreasing; window >= 0, inf allowed.  scores=False: the edges
+        only.  max_work <= 0: only the work is computed.  More pairs than max_edges: GnxError
+        with the attribute n_found
+        -> dict(work, c1, partners int64 [n_loci], score float64 [n_loci], n_edges, ei, ej int32
+        [n_edges], er2 float64 [n_edges]); partners and score are None without scores, the edge
+        entries None with max_edges = 0, all but work None when max_work <= 0"""
+        s, n = self._geno_slots(slots)
+        loci = _arr(loci, np.int32).ravel()
+        pos = _arr(pos, np.float64).ravel()
+        if pos.size != loci.size:
+            raise ValueError('pos: %d entries for %d loci' % (pos.size, loci.size))
+        max_edges = int(max_edges)
+        run = max_work > 0
+        edges = run and 0 < max_edges <= 2 ** 26      # (the library refuses the rest)
+        c1 = np.zeros(loci.size, np.int64)
+        partners = np.zeros(loci.size, np.int64) if scores else None
+        score = np.zeros(loci.size, np.float64) if scores else None
+        k = max_edges if edges else 1
+        ei, ej, er2 = np.empty(k, np.int32), np.empty(k, np.int32), np.empty(k, np.float64)
+        work, nf = np.zeros(1, np.int64), np.zeros(1, np.int64)
+        try:
+            self._chk(self.lib.gnx_ld_window(
+                self.h, n, _ptr(s), int(loci.size),
+                _ptr(loci if loci.size else np.zeros(1, np.int32)),
+                _ptr(pos if pos.size else np.zeros(1)), float(window), int(min_minor),
+                float(r2_min), max_edges, int(max_work), _ptr(work), _ptr(c1), _ptr(partners),
+                _ptr(score), _ptr(nf), _ptr(ei), _ptr(ej), _ptr(er2)))
+        except GnxError as err:
+            if 'exceed max_edges' in str(err):
+                err.n_found = int(nf[0])
+            raise
+        out = dict(work=int(work[0]), c1=None, partners=None, score=None, n_edges=None, ei=None,
+                   ej=None, er2=None)
+        if not run:
+            return out
+        out.update(c1=c1, partners=partners, score=score)
+        if edges:
+            k = int(nf[0])
+            out.update(n_edges=k, ei=ei[:k].copy(), ej=ej[:k].copy(), er2=er2[:k].copy())
+        return out
+
+    def ld_window_info(self):
+        """of the last ld_window: dict(kernel_ms, launches, locus_blocks)"""
+        return self._outs(self.lib.gnx_ld_window_info, ('kernel_ms', 'launches', 'locus_blocks'))
 
     # -- model-based ancestry (csrc/gnx_admix.hip) -------------------------------------------
     def admix_sweep(self, Q, F, slots=None, locus_mask=None, want_loglik=True, budget=None,

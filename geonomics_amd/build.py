@@ -19,7 +19,7 @@ SOURCES = ['gnx_api.hip', 'gnx_kernels_pop.hip', 'gnx_kernels_genome.hip',
            'gnx_simplify.hip', 'gnx_mantel.hip', 'gnx_group_counts.hip', 'gnx_sgs.hip', 'gnx_ld.hip',
            'gnx_tracts.hip', 'gnx_cost.hip', 'gnx_admix.hip', 'gnx_sweeps.hip', 'gnx_divmap.hip',
            'gnx_circuit.hip', 'gnx_kin.hip', 'gnx_lai.hip', 'gnx_assoc.hip', 'gnx_coal.hip',
-           'gnx_grm.hip', 'gnx_quad.hip', 'gnx_glm.hip']
+           'gnx_grm.hip', 'gnx_quad.hip', 'gnx_glm.hip', 'gnx_ldwin.hip']
 
 
 def _headers():

@@ -361,6 +361,9 @@ struct gnx_state {
   int64_t ld_budget = 0;
   double ld_ms = 0.0;
   int64_t ld_launches = 0, ld_blocks = 0;
+  // windowed LD (gnx_ldwin.hip): the same three of the last gnx_ld_window
+  double ldw_ms = 0.0;
+  int64_t ldw_launches = 0, ldw_blocks = 0;
 
   // identity tracts (gnx_tracts.hip): the kernel time and launches of the last call, and the
   // genome bytes its scan read (blocks shared by both homologues are not read)
@@ -1051,6 +1054,14 @@ int gnx_ld_bit_rows(gnx_state* h, GnxScratch& s, GnxCallTimer& tm, const int32_t
                     int64_t n_chrom, int32_t n_loci, const int32_t* loci,
                     const std::vector<int32_t>& jof, unsigned long long** T, int64_t* pitch,
                     long long** c1);
+// gnx_ld.hip: the same kernels on a stretch of the request, for gnx_ldwin.hip.  buf [buf_words],
+// zeroed here, = the bit rows of the request's indices ja .. ja + nj - 1 in that layout (nq words
+// of chromosomes, row pitch `pitch`); d_lines [n_lines]: the 128-byte genome lines (locus >> 10)
+// that hold one of them, d_jof as jof above; c1 != null: c1[0 .. nj) = the popcounts.
+// Launches on h->stream without waiting -> kernels launched
+int ld_transpose(gnx_state* h, int64_t n_chrom, int64_t nq, int64_t pitch, int n_lines,
+                 const int32_t* d_lines, const int32_t* d_rows, const int32_t* d_jof, int ja,
+                 int nj, unsigned long long* buf, int64_t buf_words, long long* c1);
 
 // ---- lineage calls (gnx_lineage.hip, gnx_simplify.hip) -----------------------------------
 #define LIN_BUDGET (256ll << 20)  // bytes of output per launch unless gnx_lineage_budget says so

@@ -282,9 +282,9 @@ __global__ void k_ld_total(int blocks, const long long* __restrict__ ipart,
 // buf [buf_words], zeroed here, = the bit rows of the request's indices ja .. ja + nj - 1 (row
 // pitch `pitch` words; rows past nj and words past the sample stay 0); lines[n_lines]: the genome
 // lines that hold one of them; c1 != null: c1[0 .. nj) = their popcounts.  -> kernels launched
-static int ld_transpose(gnx_state* h, int64_t n_chrom, int64_t nq, int64_t pitch, int n_lines,
-                        const int32_t* d_lines, const int32_t* d_rows, const int32_t* d_jof,
-                        int ja, int nj, u64* buf, int64_t buf_words, long long* c1) {
+int ld_transpose(gnx_state* h, int64_t n_chrom, int64_t nq, int64_t pitch, int n_lines,
+                 const int32_t* d_lines, const int32_t* d_rows, const int32_t* d_jof, int ja,
+                 int nj, u64* buf, int64_t buf_words, long long* c1) {
   (void)hipMemsetAsync(buf, 0, (size_t)buf_words * sizeof(u64), h->stream);
   hipLaunchKernelGGL(k_ld_bits, dim3((unsigned)((nq + 3) / 4), (unsigned)std::min(n_lines, 64)),
                      dim3(256), 0, h->stream, n_chrom, nq, pitch, n_lines, d_lines, d_rows,

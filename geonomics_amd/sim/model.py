@@ -1238,6 +1238,65 @@ class Model:
         return spp._calc_ne(method=method, min_c=min_c, min_maf=min_maf,
                             individs=self._test_sample(spp, individs, n), loci=loci)
 
+    def prune_ld(self, spp=0, r2=0.2, window=50, unit='loci', min_maf=0.05, individs=None,
+                 n=None, loci=None, max_edges=None, max_work=None):
+        """loci in approximate linkage equilibrium (an extension: the reference has no such
+        analysis; PLINK's --indep-pairwise), the list that calc_genetic_PCA, calc_ancestry,
+        calc_grm, calc_relatedness and find_kin expect as loci=: among the loci with a
+        minor-allele frequency of at least min_maf, no two within `window` of each other keep
+        an r^2 of r2 or more.  unit as calc_ld_decay: 'loci' (locus numbers), 'morgans' or 'c'.
+        The pairs above r2 are found on the device (gnx_ld_window, no L x L matrix); the greedy
+        choice - the commonest locus first, each claiming its later neighbours - runs on the
+        host.  individs, or a random sample of n, and loci restrict the analysis; max_edges
+        bounds the pair list and max_work the tile-words of the device call, a request above
+        either raises ValueError
+        -> dict: loci (kept, ascending), removed, claimed_by, n_edges, c1, n_chrom, ids, work,
+        kernel_ms"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._prune_ld(r2=r2, window=window, unit=unit, min_maf=min_maf,
+                             individs=self._test_sample(spp, individs, n), loci=loci,
+                             max_edges=max_edges, max_work=max_work)
+
+    def clump(self, result, r=0, p1=1e-4, p2=1e-2, r2=0.5, window=250, unit='loci', spp=0,
+              individs=None, max_edges=None, max_work=None):
+        """the hits of run_gwas, run_lmm, run_lfmm or run_logistic_gea as independent signals (an
+        extension; PLINK's --clump): the tested loci with p <= p2 (column r of p) in the order
+        of p, each unclaimed one claiming the later ones within `window` of it with r^2 >= r2
+        among the scan's individuals (or individs); index loci above p1 are dropped with their
+        members.  The pairs come from the device (gnx_ld_window), the greedy step runs on the
+        host
+        -> dict: index_loci, index_p, members (a list of arrays), n_clumps, n_candidates,
+        n_edges, work, kernel_ms, and trait_loci_hit (which clumps hold a causal locus) when
+        the result carries trait_loci"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._clump(result, r=r, p1=p1, p2=p2, r2=r2, window=window, unit=unit,
+                          individs=individs, max_edges=max_edges, max_work=max_work)
+
+    def calc_ld_scores(self, spp=0, window=100, unit='loci', min_maf=0.05, adjust=True,
+                       individs=None, n=None, loci=None, max_work=None):
+        """the LD score of every locus (an extension; Bulik-Sullivan et al. 2015): 1 + the sum
+        of its r^2 with the loci within `window` of it (unit as calc_ld_decay), adjusted for the
+        sample's size when adjust, summed on the device (gnx_ld_window).  weights is 1 /
+        max(ld_score, 1) over the whole genome, the weights= of calc_grm; with run_ldsc the
+        scores tell inflation by structure from polygenic signal.  individs, or a random sample
+        of n, and loci restrict the analysis; loci below min_maf are left out
+        -> dict: ld_score, partners, score [n_loci], weights [L], loci, c1, n_chrom, ids, work,
+        kernel_ms"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._calc_ld_scores(window=window, unit=unit, min_maf=min_maf, adjust=adjust,
+                                   individs=self._test_sample(spp, individs, n), loci=loci,
+                                   max_work=max_work)
+
+    def run_ldsc(self, result, scores, r=0, n_blocks=200, spp=0):
+        """LD-score regression on the host (an extension; Bulik-Sullivan et al. 2015): the
+        chi-square of an association scan (result: t^2 of column r, or lrt) regressed on the LD
+        scores of calc_ld_scores with LDSC's two weights, standard errors by a jackknife over
+        n_blocks contiguous blocks of loci (at most the loci there are)
+        -> dict: intercept, slope, h2, intercept_se, slope_se, h2_se, ratio, mean_chi2, n_loci,
+        n_blocks"""
+        spp = self.comm[self._get_spp_num(spp)]
+        return spp._run_ldsc(result, scores, r=r, n_blocks=n_blocks)
+
     def calc_ancestry(self, K, spp=0, individs=None, n=None, loci=None, init='pca', seed=None,
                       accelerate=True, tol=1e-4, max_sweeps=2000, fixed_F=None):
         """model-based ancestry (an extension: the reference has no such analysis): the

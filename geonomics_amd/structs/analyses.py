@@ -1469,6 +1469,191 @@ class SpeciesAnalyses:
                     n_loci_kept=int((np.minimum(c1, n_chrom - c1) >= mm).sum()),
                     min_c=float(min_c))
 
+    # -- windowed LD: pruning, clumping, LD scores (sim/ldwin.py; csrc/gnx_ldwin.hip) ---------
+    # pairs the edge list of one call may hold by default (16 bytes each on the host)
+    _LDW_MAX_EDGES = 1 << 24
+
+    def _ldw_call(self, who, loci, pos, window, slots, min_minor, r2_min, max_edges, max_work,
+                  scores):
+        """one gnx_ld_window call with its kernel time; the library's refusals of a request
+        above max_work or max_edges become ValueErrors with advice"""
+        max_work = _work_limit(who, max_work, self._LD_MAX_WORK, 'tile-words')
+        if max_edges is None:
+            max_edges = self._LDW_MAX_EDGES
+        if isinstance(max_edges, bool) or int(max_edges) != max_edges or \
+                not (0 if scores else 1) <= max_edges <= 1 << 26:
+            raise ValueError('%s: max_edges: a positive integer, at most 2^26 (got %r)'
+                             % (who, max_edges))
+        try:
+            got = _within_max_work(
+                who, lambda: self._dev.ld_window(loci, pos, window, slots, min_minor, r2_min,
+                                                 int(max_edges), max_work, scores),
+                'analyse a sample (n=...), fewer loci (loci=...) or a smaller window, or raise '
+                'max_work')
+        except nat.GnxError as err:
+            if 'exceed max_edges' not in str(err):
+                raise
+            raise ValueError('%s: n_found = %d pairs of loci above the r2 threshold exceed '
+                             'max_edges = %d: ask for a higher r2, a smaller window or fewer '
+                             'loci, or a larger max_edges'
+                             % (who, getattr(err, 'n_found', -1), max_edges)) from None
+        got['kernel_ms'] = self._dev.ld_window_info()['kernel_ms']
+        return got
+
+    def _prune_ld(self, r2=0.2, window=50, unit='loci', min_maf=0.05, individs=None, loci=None,
+                  max_edges=None, max_work=None):
+        """loci in approximate linkage equilibrium (PLINK's --indep-pairwise): of the loci asked
+        for (all by default) with a minor-allele frequency of at least min_maf among the living
+        individuals asked for, a set no two of which, within `window` of each other (unit as
+        _calc_ld_decay), have r^2 >= r2.  The pairs come from the device (gnx_ld_window); the
+        choice is greedy on the host (sim/ldwin.greedy_independent) in the order of the
+        minor-allele count, the commonest first, ties by locus number
+        -> dict: loci (kept, ascending), removed (ascending; the loci below min_maf are in
+        neither), claimed_by (per removed locus, the kept locus that removed it), n_edges, c1
+        (1-alleles per locus of the request), n_chrom, ids, work, kernel_ms"""
+        from ..sim import ldwin as _lw
+        who = 'prune_ld'
+        r2 = _lw.check_r2(r2, who)
+        ids, slots, loci_u, pos, mm = self._ld_request(who, individs, loci, unit, min_maf)
+        w = _lw.check_window(window, unit, who)
+        got = self._ldw_call(who, loci_u, pos, w, slots, mm, r2, max_edges, max_work, False)
+        n_chrom = 2 * ids.size
+        c1 = got['c1']
+        kept = np.minimum(c1, n_chrom - c1) >= mm
+        keep, claimed = _lw.greedy_independent(loci_u.size, got['ei'], got['ej'],
+                                               _lw.maf_rank(c1, n_chrom))
+        gone = kept & ~keep
+        return dict(loci=loci_u[kept & keep], removed=loci_u[gone],
+                    claimed_by=loci_u[claimed[gone]], n_edges=got['n_edges'], c1=c1,
+                    n_chrom=n_chrom, ids=ids, work=got['work'], kernel_ms=got['kernel_ms'])
+
+    def _clump(self, result, r=0, p1=1e-4, p2=1e-2, r2=0.5, window=250, unit='loci',
+               individs=None, max_edges=None, max_work=None):
+        """the hits of an association scan as independent signals (PLINK's --clump).  result: a
+        dict of _run_gwas, _run_lmm, _run_lfmm or _run_logistic_gea (column r of a two-
+        dimensional p).  The tested loci with p <= p2 are visited in the order of p (ties by
+        locus number); a locus that no earlier one has claimed becomes an index locus and claims
+        every later one within `window` of it (unit as _calc_ld_decay) with r^2 >= r2 among the
+        individuals of the scan (or individs); index loci with p > p1 are then dropped with
+        their members.  Pairs from the device (gnx_ld_window), the greedy step on the host
+        -> dict: index_loci, index_p (ascending p), members (a list of ascending arrays of
+        loci, the index locus not among them), n_clumps, n_candidates, n_edges, work,
+        kernel_ms, and trait_loci_hit (per clump, whether it holds a locus of
+        result['trait_loci']) when the result carries them"""
+        from ..sim import ldwin as _lw
+        who = 'clump'
+        if not isinstance(result, dict) or 'p' not in result or 'loci' not in result:
+            raise ValueError("%s: result: the dict of an association scan ('p', 'loci')" % who)
+        p = np.asarray(result['p'], dtype=np.float64)
+        if p.ndim == 2:
+            if isinstance(r, bool) or int(r) != r or not 0 <= r < p.shape[1]:
+                raise ValueError('%s: r: a column of p in 0..%d (got %r)'
+                                 % (who, p.shape[1] - 1, r))
+            p = p[:, int(r)]
+        res_loci = np.asarray(result['loci'], dtype=np.int64).ravel()
+        if p.ndim != 1 or p.size != res_loci.size:
+            raise ValueError('%s: result: p and loci differ in length' % who)
+        if not 0.0 <= float(p1) <= float(p2) <= 1.0:
+            raise ValueError('%s: 0 <= p1 <= p2 <= 1 (got %r, %r)' % (who, p1, p2))
+        r2 = _lw.check_r2(r2, who)
+        w = _lw.check_window(window, unit, who)
+        tested = np.asarray(result.get('tested', np.isfinite(p)), bool)
+        with np.errstate(invalid='ignore'):
+            sel = tested & np.isfinite(p) & (p <= p2)
+        out = dict(index_loci=np.zeros(0, np.int64), index_p=np.zeros(0), members=[],
+                   n_clumps=0, n_candidates=int(sel.sum()), n_edges=0, work=0, kernel_ms=0.0)
+        tl = result.get('trait_loci')
+        if isinstance(tl, (list, tuple)):
+            tl = tl[int(r)] if int(r) < len(tl) else None
+        if sel.any():
+            if individs is None:
+                individs = result.get('ids')
+            if (np.diff(res_loci) <= 0).any():
+                raise ValueError('%s: result: loci must be ascending' % who)
+            # (ascending and distinct: the request's loci are res_loci[sel] in that order)
+            ids, slots, loci_u, pos, mm = self._ld_request(who, individs, res_loci[sel], unit,
+                                                           0.0)
+            pr = p[sel]
+            got = self._ldw_call(who, loci_u, pos, w, slots, mm, r2, max_edges, max_work, False)
+            keep, claimed = _lw.greedy_independent(loci_u.size, got['ei'], got['ej'],
+                                                   _lw.p_rank(pr))
+            idx, mem = _lw.clumps(pr, keep, claimed, float(p1))
+            out.update(index_loci=loci_u[idx], index_p=pr[idx],
+                       members=[loci_u[m] for m in mem], n_clumps=int(idx.size),
+                       n_edges=got['n_edges'], work=got['work'], kernel_ms=got['kernel_ms'])
+        if tl is not None:
+            tl = np.asarray(tl, dtype=np.int64).ravel()
+            out['trait_loci_hit'] = np.array(
+                [bool(np.isin(np.r_[i, m], tl).any())
+                 for i, m in zip(out['index_loci'].tolist(), out['members'])], dtype=bool)
+        return out
+
+    def _calc_ld_scores(self, window=100, unit='loci', min_maf=0.05, adjust=True, individs=None,
+                        loci=None, max_work=None):
+        """the LD score of every locus asked for (all by default): 1 + the sum of its r^2 with
+        the loci within `window` of it (unit as _calc_ld_decay) that reach min_maf among the
+        living individuals asked for, each r^2 adjusted for the sample's size when adjust
+        (sim/ldwin.ld_scores); the counts and the sums come from the device (gnx_ld_window)
+        -> dict: ld_score [n_loci] (NaN below min_maf), partners, score (the plain sum), weights
+        [L] (1 / max(ld_score, 1), 0 for every other locus: the weights argument of _calc_grm),
+        loci, c1, n_chrom, ids, work, kernel_ms"""
+        from ..sim import ldwin as _lw
+        who = 'calc_ld_scores'
+        ids, slots, loci_u, pos, mm = self._ld_request(who, individs, loci, unit, min_maf)
+        w = _lw.check_window(window, unit, who)
+        n_chrom = 2 * ids.size
+        if adjust and n_chrom <= 2:
+            raise ValueError('%s: adjust needs at least two individuals' % who)
+        got = self._ldw_call(who, loci_u, pos, w, slots, mm, 0.0, 0, max_work, True)
+        c1 = got['c1']
+        kept = np.minimum(c1, n_chrom - c1) >= mm
+        ls = _lw.ld_scores(got['partners'], got['score'], kept, n_chrom, bool(adjust))
+        weights = np.zeros(self._dev.L)
+        weights[loci_u] = _lw.score_weights(ls)
+        return dict(ld_score=ls, partners=got['partners'], score=got['score'], weights=weights,
+                    loci=loci_u, c1=c1, n_chrom=n_chrom, ids=ids, work=got['work'],
+                    kernel_ms=got['kernel_ms'])
+
+    def _run_ldsc(self, result, scores, r=0, n_blocks=200):
+        """LD-score regression (Bulik-Sullivan et al. 2015) on the host: the chi-square of an
+        association scan (result: t^2 of column r, or lrt) over its tested loci regressed on
+        their LD scores (scores: a dict of _calc_ld_scores), sim/ldwin.ldsc.  An intercept above
+        1 is inflation that every locus shares (structure); the slope is polygenic signal
+        -> dict: intercept, slope, h2 (slope M / n), intercept_se, slope_se, h2_se, ratio,
+        mean_chi2, n_loci, n_blocks"""
+        from ..sim import ldwin as _lw
+        who = 'run_ldsc'
+        if not isinstance(result, dict) or 'loci' not in result or \
+                not ('lrt' in result or 't' in result):
+            raise ValueError("%s: result: the dict of an association scan ('loci' and 't' or "
+                             "'lrt')" % who)
+        if not isinstance(scores, dict) or 'ld_score' not in scores or 'loci' not in scores:
+            raise ValueError("%s: scores: the dict of calc_ld_scores" % who)
+        if 'lrt' in result:
+            chi2 = np.asarray(result['lrt'], dtype=np.float64)
+        else:
+            t = np.asarray(result['t'], dtype=np.float64)
+            if t.ndim == 2:
+                if isinstance(r, bool) or int(r) != r or not 0 <= r < t.shape[1]:
+                    raise ValueError('%s: r: a column of t in 0..%d (got %r)'
+                                     % (who, t.shape[1] - 1, r))
+                t = t[:, int(r)]
+            chi2 = t * t
+        res_loci = np.asarray(result['loci'], dtype=np.int64).ravel()
+        if chi2.ndim != 1 or chi2.size != res_loci.size:
+            raise ValueError('%s: result: the statistic and loci differ in length' % who)
+        ls = np.full(self._dev.L, np.nan)
+        ls[np.asarray(scores['loci'], dtype=np.int64)] = scores['ld_score']
+        x = ls[res_loci]
+        use = np.asarray(result.get('tested', np.ones(chi2.size, bool)), bool) & \
+            np.isfinite(chi2) & np.isfinite(x)
+        n = len(result['ids']) if 'ids' in result else scores['n_chrom'] // 2
+        try:
+            return _lw.ldsc(chi2[use], x[use], n, int(np.isfinite(scores['ld_score']).sum()),
+                            n_blocks)
+        except ValueError as err:
+            raise ValueError('%s: %s' % (who, err)) from None
+
     # -- model-based ancestry (sim/ancestry.py; csrc/gnx_admix.hip) ---------------------------
     def _calc_ancestry(self, K, individs=None, loci=None, init='pca', seed=None, accelerate=True,
                        tol=1e-4, max_sweeps=2000, fixed_F=None, budget=None):

@@ -77,6 +77,16 @@ _NOT_TILED = {
                       'implemented; run the model on one GPU',
     '_calc_ne': 'calc_ne with a Species tiled over several GPUs is not '
                 'implemented; run the model on one GPU',
+    # windowed LD (one bit row holds the whole sample: a gather)
+    '_prune_ld': 'prune_ld with a Species tiled over several GPUs is not implemented; run the '
+                 'model on one GPU',
+    '_clump': 'clump with a Species tiled over several GPUs is not implemented; run the model '
+              'on one GPU',
+    '_calc_ld_scores': 'calc_ld_scores with a Species tiled over several GPUs is not '
+                       'implemented; run the model on one GPU',
+    # (host arithmetic, but on the two results above)
+    '_run_ldsc': 'run_ldsc with a Species tiled over several GPUs is not implemented; run the '
+                 'model on one GPU',
     '_calc_ancestry': 'calc_ancestry with a Species tiled over several GPUs is not '
                       'implemented; run the model on one GPU',
     # local ancestry (row-local like the sweep above, but anc_locus adds over tiles in a fixed
